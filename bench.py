@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native linux-fg hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pipeline|scale]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pipeline|scale] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): interpolated frames/s at 1080p -> 4K RGBA8, with the achieved rate of the
 dominant kernel against its roofline.  A "step" is one pass of the hot path over one synthetic
@@ -21,7 +21,7 @@ Frames in flight (--in-flight N, default 3; include/linuxfg_hip.h "Lanes", DESIG
 the context -- its own stream, motion workspace and curr / mv / out buffers -- so that one step's upscale, hints and first
 motion units fill the CUs that the previous step's last long motion units leave idle.  The dependencies of a stream of
 frames are kept (a step's motion waits for the previous step's upscale on the other lane); `value` is still steps over
-wall time between two device-wide synchronisations.  Per-stage durations (`stages`, `roofline.dominant_stage`) then come
+wall time between two device-wide synchronisations.  Per-stage durations (`stages`, `roofline.dominant_stage`; --full) come
 from a second pass on ONE lane, where an event pair around a stage times that stage alone.  --in-flight 1 is strictly
 one step at a time.
 
@@ -32,7 +32,11 @@ the one the path really has: the batch's shared previous frame is broadcast from
 every rank upscales itself (one more 13 us scale per step than at N = 1; 33 MB of upscaled frame per
 0.5 ms step would cost more on xGMI than that).  Weak scaling.
 
-Besides the headline line's `value`, rank 0 at N = 1 measures in the same run (short, after the timed region): the
+A plain run times exactly K steps after W warm-up steps (`value`, `ms_per_step`) and prints a line that says what was
+timed, nothing more.  --dump-outputs DIR then writes what the last timed step computed (dump_outputs).  Everything below
+is measured or checked only with --full.
+
+Besides the headline line's `value`, with --full rank 0 at N = 1 measures in the same run (short, after the timed region): the
 scale-only (BASELINE config 2) and scale + interpolate rates -- the two configurations SURVEY.md 8(d) says HBM is
 the right bound for -- and `content_sweep`, the pipeline on every other synthetic content, because the motion
 stage's run time depends on the content by more than an order of magnitude (results never do) and the default
@@ -48,6 +52,7 @@ import json
 import os
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -84,6 +89,11 @@ def parse_args():
                     help="frames in flight on one GPU (lanes of the C-ABI): each has its own stream, motion workspace and output "
                          "buffers, so one frame's scale / hints / first prefilter units fill the CUs that the previous frame's last "
                          "long units leave idle; 1 = strictly one frame at a time")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: repeated regions, the check of what was timed, per-stage durations, the roofline, "
+                         "the extras and the CPU baseline (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, a seeded sample of pixels: dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fused-motion-interpolate", action="store_true",
                     help="pipeline workload, one factor: lfg_interpolate_frames in the north-star order (lfg_set_fused_motion_interpolate: the motion "
@@ -96,7 +106,7 @@ def parse_args():
     ap.add_argument("--config5", action="store_true", help="only BASELINE config 5 on this GPU, short (extras.config5; see measure_config5)")
     ap.add_argument("--with-communicator", action="store_true",
                     help="only the N > 1 step with a one-rank communicator on this GPU (extras.with_communicator; see measure_with_communicator)")
-    ap.add_argument("--no-extras", action="store_true", help="skip scale_only / scale_interpolate / content_sweep (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip scale_only / scale_interpolate / content_sweep (profiling runs)")
     return ap.parse_args()
 
 
@@ -726,6 +736,22 @@ def measure_pcie_inclusive(torch, capi, ctx, dev, w_in, h_in, w, h):
     return out
 
 
+DUMP_PIXELS = 1 << 20          # pixels of a frame --dump-outputs writes at most (a 4K frame has 8.3 M)
+DUMP_BYTES = 60_000_000        # all files together stay under 64 MB
+DUMP_SEED = 20241016
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: `frames` ({name: (H, W, C) uint8 or int8 array}, what the last timed step computed) as out_dir/<name>.npy, float32
+    of shape (n, C): every channel of n pixels drawn without replacement by a fixed seed, in raster order -- the same pixels in every
+    run with the same arguments, so that two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_max = min(DUMP_PIXELS, DUMP_BYTES // (4 * sum(a.shape[-1] for a in frames.values())))
+    for name, a in frames.items():
+        flat = a.reshape(-1, a.shape[-1])
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.shape[0], min(n_max, flat.shape[0]), replace=False))
+        np.save(os.path.join(out_dir, name + ".npy"), flat[idx].astype(np.float32))
+
 
 def gather_ranks(dist, world, dev_index, rccl_ranks, verified):
     """What rank 0 needs from the other ranks for the line, over the control plane (gloo): which card every rank drove, the size of
@@ -742,14 +768,45 @@ def gather_ranks(dist, world, dev_index, rccl_ranks, verified):
     return devices, ranks, verified
 
 
+def headline_line(r):
+    """What a plain run prints: the headline figure and what was timed (`r` as in assemble_line)."""
+    args, world, factors, w_in, h_in, w, h, in_res = r.args, r.world, r.factors, r.w_in, r.h_in, r.w, r.h, r.in_res
+    size_name = {"540p": "540p->1080p", "1080p": "1080p->4K", "4k": "4K->8K", "8k": "8K->16K"}[args.input]
+    return {
+        "metric": (f"interpolated frames/s, {size_name} RGBA8" if args.workload == "pipeline"
+                   else f"interpolated frames/s, {size_name} RGBA8 (variant: motion + interpolate at input resolution)" if in_res
+                   else f"upscaled frames/s, {size_name} RGBA8 (Lanczos only)"),
+        "value": round(r.value, 3),
+        "unit": "frames/s",
+        "n_gpus": world, "steps": r.steps, "warmup": r.warmup,
+        "ms_per_step": round(r.elapsed / r.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 arithmetic on u8 RGBA (u8 in, u8 out; int8 motion vectors)",
+        "data": "synthetic",
+        "config": {"workload": (f"{args.input}->{2 * h_in}p " + ("scale+motion(8,16)+interpolate" if args.workload == "pipeline"
+                                                                else "motion(8,16)+interpolate at input resolution, then scale real and generated frame" if in_res
+                                                                else "scale only")),
+                   "input": [w_in, h_in], "output": [w, h], "factors": factors if args.workload != "scale" else [],
+                   "order": ("north-star, fused: lfg_interpolate_frames with lfg_set_fused_motion_interpolate -- the motion kernels write the generated frame, "
+                             "no interpolate dispatch, no motion-vector frame (a labelled variant)" if r.fused_mi else "one call per stage"),
+                   "semantics": args.semantics,       # "reference": the shaders as written; "intended": the opt-in lfg_set_semantics mode (a labelled variant)
+                   "frames_in_flight": r.n_lanes,     # lanes of the C-ABI (DESIGN.md 4.5); 1 = strictly one frame at a time
+                   "devices": r.devices,              # HIP device ordinal of every rank, in rank order
+                   "content": args.content + (" (the motion stage's best case but `static`; see content_sweep)" if args.content == "translated" and args.workload != "scale" else ""),
+                   "parallelism": f"one frame pair per GPU x{world}" + (", lfg_broadcast_frame_lane (RCCL, 8 CUs kept for it) of the shared previous input frame per step, upscaled on every rank" if world > 1 else ""),
+                   "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")},      # (HIP's default of 4 makes streams share hardware queues)
+        "rccl_ranks": r.rccl_ranks,            # lfg_comm_ranks(): the size of the RCCL communicator every rank joined (0: one GPU, none)
+        "library_sha16": library_sha16(),
+    }
+
+
 def assemble_line(r):
-    """The ONE JSON line rank 0 prints, from plain values (`r`: a namespace filled by main(); no GPU, no torch in here, so that
+    """The ONE JSON line rank 0 prints with --full, from plain values (`r`: a namespace filled by main(); no GPU, no torch in here, so that
     tests/test_bench_helpers.py can build the line of an N > 1 run on CPU ranks and hold its keys)."""
     args, world, stage_ms, factors = r.args, r.world, r.stage_ms, r.factors
     w_in, h_in, w, h, mw, mh, in_res, share_input = r.w_in, r.h_in, r.w, r.h, r.mw, r.mh, r.in_res, r.share_input
-    steps, warmup, elapsed, regions, value = r.steps, r.warmup, r.elapsed, r.regions, r.value
-    exact_only, motion_stats, n_lanes, devices, rccl_ranks = r.exact_only, r.motion_stats, r.n_lanes, r.devices, r.rccl_ranks
-    fused_mi, extras, stage_pass = r.fused_mi, r.extras, r.stage_pass
+    steps, elapsed, regions = r.steps, r.elapsed, r.regions
+    exact_only, motion_stats, extras, stage_pass = r.exact_only, r.motion_stats, r.extras, r.stage_pass
     stages = {}
     for name, avg in stage_ms.items():
         b = algorithmic_bytes(name, w_in, h_in, w if name == "scale" else mw, h if name == "scale" else mh)
@@ -812,7 +869,6 @@ def assemble_line(r):
         else:
             md["motion_mode"] = "exact kernel only"
         roofline["dominant_stage"] = md
-    size_name = {"540p": "540p->1080p", "1080p": "1080p->4K", "4k": "4K->8K", "8k": "8K->16K"}[args.input]
     if args.input == "1080p" and not in_res and len(factors) == 1:
         t, src = pmc_traffic("lfg::scale_2x" if args.workload == "scale" else "lfg::")
         if t is not None:
@@ -821,41 +877,18 @@ def assemble_line(r):
                                           "--pmc passes with this very library; FETCH_SIZE raw (uncalibrated for 4-byte-per-lane loads)")
         else:
             roofline["traffic_note"] = src
-    line = {
-        "metric": (f"interpolated frames/s, {size_name} RGBA8" if args.workload == "pipeline"
-                   else f"interpolated frames/s, {size_name} RGBA8 (variant: motion + interpolate at input resolution)" if in_res
-                   else f"upscaled frames/s, {size_name} RGBA8 (Lanczos only)"),
-        "value": round(value, 3),
-        "unit": "frames/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(elapsed / steps * 1e3, 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32 arithmetic on u8 RGBA (u8 in, u8 out; int8 motion vectors)",
-        "data": "synthetic",
-        "config": {"workload": (f"{args.input}->{2 * h_in}p " + ("scale+motion(8,16)+interpolate" if args.workload == "pipeline"
-                                                                else "motion(8,16)+interpolate at input resolution, then scale real and generated frame" if in_res
-                                                                else "scale only")),
-                   "input": [w_in, h_in], "output": [w, h], "factors": factors if args.workload != "scale" else [],
-                   "order": ("north-star, fused: lfg_interpolate_frames with lfg_set_fused_motion_interpolate -- the motion kernels write the generated frame, "
-                             "no interpolate dispatch, no motion-vector frame (a labelled variant)" if fused_mi else "one call per stage"),
-                   "semantics": args.semantics,       # "reference": the shaders as written; "intended": the opt-in lfg_set_semantics mode (a labelled variant)
-                   "frames_in_flight": n_lanes,       # lanes of the C-ABI; 1 = strictly one frame at a time
-                   "devices": devices,                # HIP device ordinal of every rank, in rank order
-                   "content": args.content + (" (the motion stage's best case but `static`; see content_sweep)" if args.content == "translated" and args.workload != "scale" else ""),
-                   "parallelism": f"one frame pair per GPU x{world}" + (", lfg_broadcast_frame_lane (RCCL, 8 CUs kept for it) of the shared previous input frame per step, upscaled on every rank" if world > 1 else ""),
-                   "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")},      # (HIP's default of 4 makes streams share hardware queues)
-        "rccl_ranks": rccl_ranks,              # lfg_comm_ranks(): the size of the RCCL communicator every rank joined (0: one GPU, none)
-        "repeats": {"regions": len(regions), "steps_per_region": steps, "median_ms_per_step": round(elapsed / steps * 1e3, 5),
+    line = headline_line(r)
+    line.update({
+        "repeats": {"regions": len(regions), "steps_per_region": steps, "median_ms_per_step": round(float(np.median(regions)) / steps * 1e3, 5),
                     "min_ms_per_step": round(min(regions) / steps * 1e3, 5), "max_ms_per_step": round(max(regions) / steps * 1e3, 5),
                     "first_region_ms_per_step": round(regions[0] / steps * 1e3, 5),
                     "how": "every region is exactly `steps` steps between its own barrier + device-synchronisation pairs (max over ranks); "
-                           "a region shorter than 0.25 s is repeated until 0.25 s have been timed (25 regions at most) and `value` / "
-                           "`ms_per_step` are the MEDIAN region's"},
+                           "`value` / `ms_per_step` are the FIRST region's; --full repeats a region shorter than 0.25 s until 0.25 s have "
+                           "been timed (25 regions at most) for the spread"},
         "roofline": roofline,
         "stages": stages,
         "stages_how": stage_pass,
-        "library_sha16": library_sha16(),
-    }
+    })
     line["verified"] = r.verified          # what the timed kernels produced, checked after the timed regions (every rank's; None: not applicable)
     line.update(extras)
     # the CPU baseline is timed on rank 0 at N = 1 only (the driver's contract); the key is there at every N
@@ -975,7 +1008,7 @@ def main():
     # broadcast slot the next shared frame is about to land in.
     n_lanes = max(1, min(args.in_flight, capi.MAX_LANES)) if args.workload == "pipeline" else 1
     lane_bufs = [(f_curr4, f_mv, f_outs, f_prev4)]
-    lane_tensors = [(t_mv, [t for t, _ in outs])]      # (the same buffers as torch tensors: `verified` reads them back)
+    lane_tensors = [(t_curr4, t_mv, [t for t, _ in outs])]      # (the same buffers as torch tensors: `verified` and --dump-outputs read them back)
     keep_alive = []
     if n_lanes > 1:
         ctx.lanes(n_lanes)
@@ -987,7 +1020,7 @@ def main():
                 fp4 = bufs[-1][1]
             keep_alive.append(bufs)
             lane_bufs.append((bufs[0][1], bufs[1][1], [f for _, f in bufs[2:2 + len(factors)]], fp4))
-            lane_tensors.append((bufs[1][0], [t for t, _ in bufs[2:2 + len(factors)]]))
+            lane_tensors.append((bufs[0][0], bufs[1][0], [t for t, _ in bufs[2:2 + len(factors)]]))
 
     fused_mi = bool(args.fused_motion_interpolate) and args.workload == "pipeline" and len(factors) == 1
     if args.semantics == "intended":
@@ -1054,7 +1087,7 @@ def main():
     for k in range(warmup):
         step(k)
     ctx.profile_reset()
-    ctx.profile_enable(args.workload != "scale" and n_lanes == 1)     # events around every stage launch (ms-scale kernels)
+    ctx.profile_enable(args.full and args.workload != "scale" and n_lanes == 1)     # events around every stage launch (ms-scale kernels)
 
     def timed_region(first):
         """EXACTLY `steps` steps between two barrier + device-synchronisation pairs; seconds, max over ranks."""
@@ -1070,16 +1103,40 @@ def main():
             dt = float(tt.item())
         return dt
 
-    # A short region (the driver asks for 20 steps: 7 ms) is mostly ramp-up of the frames in flight and timer noise, so it is
-    # REPEATED -- every region is exactly `steps` steps between its own barriers -- until a quarter of a second has been
-    # timed (25 regions at most) and the MEDIAN region gives `value`; `repeats` reports the spread and the first region.
+    # `value` and `ms_per_step` are the first region's: exactly `steps` steps.  A short region is mostly ramp-up of the frames in
+    # flight and timer noise, so --full repeats it -- every region exactly `steps` steps between its own barriers -- until a
+    # quarter of a second has been timed (25 regions at most); `repeats` reports the spread.
     regions = [timed_region(warmup)]
-    n_regions = 1 if regions[0] >= 0.25 else int(min(25, max(3, np.ceil(0.25 / max(regions[0], 1e-6)))))
+    n_regions = 1 if not args.full or regions[0] >= 0.25 else int(min(25, max(3, np.ceil(0.25 / max(regions[0], 1e-6)))))
     for r in range(1, n_regions):
         regions.append(timed_region(warmup + r * steps))
-    elapsed = float(np.median(regions))
+    elapsed = regions[0]
     shared_prev.drain()
     torch.cuda.synchronize(dev)
+    last = warmup + len(regions) * steps - 1          # the last timed step: its lane's buffers hold what it computed
+    in_res = args.workload == "pipeline_input_res"
+    units_per_step = 1 if args.workload == "scale" else len(factors)
+    value = world * steps * units_per_step / elapsed
+
+    if args.dump_outputs and rank == 0:
+        t_c4, t_mv_l, t_outs_l = lane_tensors[last % n_lanes]
+        frames = {"upscaled": t_c4}
+        if args.workload != "scale":
+            if not fused_mi:                          # (the fused call writes no motion-vector frame)
+                frames["motion_vectors"] = (t_mv_in if in_res else t_mv_l).view(torch.int8)
+            frames.update({f"generated_{i}": t for i, t in enumerate(t_outs_l)})
+        dump_outputs(args.dump_outputs, {name: t.cpu().numpy() for name, t in frames.items()})
+
+    if not args.full:
+        devices, rccl_ranks, _ = gather_ranks(dist if world > 1 else None, world, dev_index, ctx.comm_ranks(), None)
+        if rank == 0:
+            print(json.dumps(headline_line(SimpleNamespace(
+                args=args, world=world, factors=factors, w_in=w_in, h_in=h_in, w=w, h=h, in_res=in_res, steps=steps, warmup=warmup,
+                elapsed=elapsed, value=value, fused_mi=fused_mi, n_lanes=n_lanes, devices=devices, rccl_ranks=rccl_ranks))), flush=True)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- what the timed kernels produced, looked at (no oracle: the HIP path against itself and against what the content
     # implies).  The LAST timed step's vectors and generated frame, as they lie in its lane's buffers, must equal -- byte for
@@ -1088,8 +1145,7 @@ def main():
     # rim must be minus the translation.
     verified = None
     if args.workload == "pipeline" and not fused_mi and os.environ.get("LFG_MOTION_MODE", "0") != "1":
-        last = warmup + len(regions) * steps - 1
-        t_mv_last, t_outs_last = lane_tensors[last % n_lanes]
+        _, t_mv_last, t_outs_last = lane_tensors[last % n_lanes]
         got_mv = t_mv_last.cpu().numpy().view(np.int8).copy()
         got_out = [t.cpu().numpy().copy() for t in t_outs_last]
         chk_mv_t, chk_mv = empty_frame(w, h, capi.FORMAT_MV_S8X2)
@@ -1166,10 +1222,7 @@ def main():
     # what RCCL saw, and which card every rank drove (the driver checks its N against these)
     devices, rccl_ranks, verified = gather_ranks(dist if world > 1 else None, world, dev_index, ctx.comm_ranks(), verified)
 
-    units_per_step = 1 if args.workload == "scale" else len(factors)
-    in_res = args.workload == "pipeline_input_res"
     mw, mh = (w_in, h_in) if in_res else (w, h)        # resolution motion and interpolate run at
-    value = world * steps * units_per_step / elapsed
 
     # ---- the same run, rank 0, one GPU: the two HBM-bound configurations and the other contents
     extras = {}
@@ -1374,7 +1427,7 @@ def main():
             per = {nm: round(ctx.profile_get(sid)[0] / max(ctx.profile_get(sid)[1], 1), 4)
                    for nm, sid in (("scale", capi.STAGE_SCALE), ("motion", capi.STAGE_MOTION), ("interpolate", capi.STAGE_INTERPOLATE))}
             ctx.profile_enable(False)
-            moved = interpolate_bytes_moved(lane_tensors[0][0].cpu().numpy().view(np.int8), factors, intended=True)
+            moved = interpolate_bytes_moved(lane_tensors[0][1].cpu().numpy().view(np.int8), factors, intended=True)
             used, tiles, left = ctx.motion_lean_stats()
             intended[label] = {"frames_per_s": round(n_i * len(factors) / t_i, 1), "ms_per_step": round(t_i / n_i * 1e3, 5), "steps": n_i,
                                "stage_ms_one_call_at_a_time": per, "interpolate_bytes_moved": moved,
@@ -1397,7 +1450,6 @@ def main():
                                            "search range: `value` is on the SURVEY-prescribed pure pan, its best case bar `static`"}
 
     if rank == 0:
-        from types import SimpleNamespace
         interp_moved = None
         if "interpolate" in stage_ms:
             interp_moved = interpolate_bytes_moved((t_mv_in if in_res else t_mv).cpu().numpy().view(np.int8), factors, intended=args.semantics == "intended")

@@ -208,3 +208,42 @@ def test_the_line_of_an_n_gt_1_run_has_every_key():
     assert rf["algorithmic_bytes_per_step"] == 2 * 41472000 + 82944000 + 116121600
     assert line["stages"]["interpolate"]["bytes_moved"] == 6 * 3840 * 2160
     assert line["verified"]["ok"] is True and line["verified"]["per_rank_ok"] == [True, True]
+
+
+def test_dump_outputs_is_a_fixed_float32_sample_under_64_mb(tmp_path):
+    """--dump-outputs: a frame smaller than the sample comes out whole, in raster order, signed vectors kept; a 4K step with three
+    factors comes out as the same pixels in every run, all files together under 64 MB."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(5)
+    small = {"upscaled": rng.integers(0, 256, (36, 64, 4), dtype=np.uint8), "motion_vectors": rng.integers(-16, 17, (36, 64, 2)).astype(np.int8)}
+    b.dump_outputs(str(tmp_path / "small"), small)
+    for name, a in small.items():
+        got = np.load(tmp_path / "small" / f"{name}.npy")
+        assert got.dtype == np.float32 and (got == a.reshape(-1, a.shape[-1]).astype(np.float32)).all()
+
+    h, w = 2160, 3840
+    up = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    big = {"upscaled": up, "motion_vectors": np.zeros((h, w, 2), np.int8), **{f"generated_{i}": up for i in range(3)}}
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), big)
+    total = 0
+    for name in big:
+        a, again = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape[0] > 100_000 and (a == again).all()
+        total += (tmp_path / "a" / f"{name}.npy").stat().st_size
+    assert total <= 64_000_000
+
+
+def test_the_plain_line_holds_the_headline_keys(monkeypatch):
+    """A plain run's line: the headline figure and what was timed; `ms_per_step` is the one region of exactly `steps` steps."""
+    import types
+    b = _bench()
+    monkeypatch.setattr(b, "library_sha16", lambda: "0123456789abcdef")
+    args = types.SimpleNamespace(workload="pipeline", input="1080p", content="translated", semantics="reference")
+    line = b.headline_line(types.SimpleNamespace(
+        args=args, world=1, factors=[0.5], w_in=1920, h_in=1080, w=3840, h=2160, in_res=False, steps=20, warmup=5,
+        elapsed=0.0053, value=20 / 0.0053, fused_mi=False, n_lanes=3, devices=[0], rccl_ranks=0))
+    assert line["metric"] == "interpolated frames/s, 1080p->4K RGBA8" and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32 arithmetic on u8 RGBA (u8 in, u8 out; int8 motion vectors)"
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["ms_per_step"] == 0.265 and line["value"] == round(20 / 0.0053, 3)

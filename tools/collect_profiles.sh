@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 stats() {   # $1 = name, rest = bench args [env prefix via LFG_MOTION_MODE]
   local name=$1; shift
   rm -rf /tmp/prof_$name
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python3 $R/bench.py "$@" --no-cpu-baseline --no-extras \
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python3 $R/bench.py --full "$@" --no-cpu-baseline --no-extras \
       > $OUT/${TAG}_${name}_bench_under_rocprof.json 2> /tmp/prof_$name.err
   cp $(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_${name}_kernel_stats.csv
 }
@@ -40,13 +40,13 @@ LFG_MOTION_MODE=1 stats pipeline_exact_only --steps 5 --warmup 1
 stats config5_one_lane --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --steps 40 --warmup 4     # BASELINE config 5 on one GPU: 4K -> 8K, three generated frames per pair
 stats config5 --input 4k --factors 0.25,0.5,0.75 --steps 60 --warmup 6
 echo "kernel stats done"
-python3 $R/bench.py > $OUT/${TAG}_pipeline_bench.json 2> /tmp/bench.err
-python3 $R/bench.py --workload scale > $OUT/${TAG}_scale_bench.json 2>> /tmp/bench.err
-python3 $R/bench.py --in-flight 1 --no-extras --no-cpu-baseline > $OUT/${TAG}_pipeline_one_lane_bench.json 2>> /tmp/bench.err   # one frame at a time
-python3 $R/bench.py --workload pipeline_input_res --no-extras --no-cpu-baseline > $OUT/${TAG}_pipeline_input_res_bench.json 2>> /tmp/bench.err   # labelled variant: motion + interpolate at input resolution, then scale
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_pipeline_bench_driver_shape.json 2>> /tmp/bench.err   # the driver's command: a 7 ms region, repeated (the `repeats` field)
-python3 $R/bench.py --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --no-extras --no-cpu-baseline --steps 200 --warmup 10 > $OUT/${TAG}_config5_one_lane_bench.json 2>> /tmp/bench.err
-python3 $R/bench.py --input 4k --factors 0.25,0.5,0.75 --no-extras --no-cpu-baseline --steps 300 --warmup 12 > $OUT/${TAG}_config5_bench.json 2>> /tmp/bench.err
+python3 $R/bench.py --full > $OUT/${TAG}_pipeline_bench.json 2> /tmp/bench.err
+python3 $R/bench.py --full --workload scale > $OUT/${TAG}_scale_bench.json 2>> /tmp/bench.err
+python3 $R/bench.py --full --in-flight 1 --no-extras --no-cpu-baseline > $OUT/${TAG}_pipeline_one_lane_bench.json 2>> /tmp/bench.err   # one frame at a time
+python3 $R/bench.py --full --workload pipeline_input_res --no-extras --no-cpu-baseline > $OUT/${TAG}_pipeline_input_res_bench.json 2>> /tmp/bench.err   # labelled variant: motion + interpolate at input resolution, then scale
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_pipeline_bench_driver_shape.json 2>> /tmp/bench.err   # the driver's step counts: a 7 ms region, repeated for the spread (the `repeats` field)
+python3 $R/bench.py --full --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --no-extras --no-cpu-baseline --steps 200 --warmup 10 > $OUT/${TAG}_config5_one_lane_bench.json 2>> /tmp/bench.err
+python3 $R/bench.py --full --input 4k --factors 0.25,0.5,0.75 --no-extras --no-cpu-baseline --steps 300 --warmup 12 > $OUT/${TAG}_config5_bench.json 2>> /tmp/bench.err
 rc=0; python3 $R/bench.py --gpus 2 --steps 5 > $OUT/${TAG}_gpus2_on_one_gpu.txt 2>&1 || rc=$?; echo "exit code $rc" >> $OUT/${TAG}_gpus2_on_one_gpu.txt   # the launcher's refusal on a box with one GPU
 echo "bench done"
 echo "pmc done"; ls -la $OUT

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 for n in 3 1; do for rep in 1 2 3; do for v in ${VARIANTS:-new mvuniform mvnostore}; do
-  LFG_LIB=$R/build_variants/lib_$v.so timeout -k 10 200 python3 bench.py --in-flight $n --steps 1500 --warmup 20 --no-extras --no-cpu-baseline > /tmp/fb.json 2> /tmp/fb.err || { echo "bench $v failed"; tail -3 /tmp/fb.err; }
+  LFG_LIB=$R/build_variants/lib_$v.so timeout -k 10 200 python3 bench.py --full --in-flight $n --steps 1500 --warmup 20 --no-extras --no-cpu-baseline > /tmp/fb.json 2> /tmp/fb.err || { echo "bench $v failed"; tail -3 /tmp/fb.err; }
   python3 - $v $n <<'PY'
 import json, sys
 d = json.loads(open('/tmp/fb.json').read().strip().splitlines()[-1])

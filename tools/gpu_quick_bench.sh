@@ -5,7 +5,7 @@ cd $R
 for rep in 1 2; do for e in "$@"; do
   [ "$e" = "-" ] && e=""
   for lanes in ${LANES:-3 1}; do
-    env $e timeout -k 10 200 python3 bench.py --content ${CONTENT:-translated} --in-flight $lanes --steps ${STEPS:-600} --warmup 12 --no-extras --no-cpu-baseline > /tmp/qb.json 2> /tmp/qb.err || { echo "bench failed"; tail -3 /tmp/qb.err; }
+    env $e timeout -k 10 200 python3 bench.py --full --content ${CONTENT:-translated} --in-flight $lanes --steps ${STEPS:-600} --warmup 12 --no-extras --no-cpu-baseline > /tmp/qb.json 2> /tmp/qb.err || { echo "bench failed"; tail -3 /tmp/qb.err; }
     python3 - "$e" $lanes <<'PY'
 import json, sys
 d = json.loads(open('/tmp/qb.json').read().strip().splitlines()[-1])

@@ -6,8 +6,8 @@ O=$R/gpurun_out/r3p1
 mkdir -p $O
 cd $R
 set -o pipefail
-echo "== config 5, one frame at a time"; timeout -k 10 240 python3 bench.py --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --steps 30 --warmup 4 --no-extras --no-cpu-baseline > $O/c5_lane1.json 2> $O/c5_lane1.err || { echo FAILED lane1; tail -5 $O/c5_lane1.err; }
-echo "== config 5, three frames in flight"; timeout -k 10 240 python3 bench.py --input 4k --factors 0.25,0.5,0.75 --in-flight 3 --steps 30 --warmup 6 --no-extras --no-cpu-baseline > $O/c5_lane3.json 2> $O/c5_lane3.err || { echo FAILED lane3; tail -5 $O/c5_lane3.err; }
+echo "== config 5, one frame at a time"; timeout -k 10 240 python3 bench.py --full --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --steps 30 --warmup 4 --no-extras --no-cpu-baseline > $O/c5_lane1.json 2> $O/c5_lane1.err || { echo FAILED lane1; tail -5 $O/c5_lane1.err; }
+echo "== config 5, three frames in flight"; timeout -k 10 240 python3 bench.py --full --input 4k --factors 0.25,0.5,0.75 --in-flight 3 --steps 30 --warmup 6 --no-extras --no-cpu-baseline > $O/c5_lane3.json 2> $O/c5_lane3.err || { echo FAILED lane3; tail -5 $O/c5_lane3.err; }
 python3 - <<'PY' > $O/ws.txt 2>&1
 import sys; sys.path.insert(0, '.')
 from linux_fg_amd import capi
@@ -21,7 +21,7 @@ PY
 cat $O/ws.txt
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/p5
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p5 -- python3 $R/bench.py --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --steps 20 --warmup 3 --no-extras --no-cpu-baseline > $O/c5_lane1_under_rocprof.json 2> $O/c5_prof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p5 -- python3 $R/bench.py --full --input 4k --factors 0.25,0.5,0.75 --in-flight 1 --steps 20 --warmup 3 --no-extras --no-cpu-baseline > $O/c5_lane1_under_rocprof.json 2> $O/c5_prof.err
 cp $(find /tmp/p5 -name "*kernel_stats.csv" | head -1) $O/c5_lane1_kernel_stats.csv
 cd $R
 for c in objects occluded noisy; do

@@ -12,7 +12,7 @@ print("standalone, queues", os.environ.get("GPU_MAX_HW_QUEUES"), {k[:12]: v["fra
 PY
 for q in 8 16; do GPU_MAX_HW_QUEUES=$q python3 /tmp/one.py 2>/dev/null | grep standalone; done
 for q in 8 16 24; do
-  GPU_MAX_HW_QUEUES=$q python3 bench.py --no-cpu-baseline 2>/dev/null | python3 -c "
+  GPU_MAX_HW_QUEUES=$q python3 bench.py --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=d['with_communicator']
 print('in bench.py, queues', d['config']['gpu_max_hw_queues'], 'value', d['value'], {k[:12]: v['frames_per_s'] for k, v in w['by_content'].items()}, 'config5', d['config5']['interpolated_frames_per_s'], 'stream', d['stream']['paced']['frames_per_s'])"

@@ -1,7 +1,7 @@
 #!/bin/bash
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; O=$R/gpurun_out/r5_strip_diag; mkdir -p $O
 for l in 1 3; do
-python3 bench.py --in-flight $l --steps 200 --warmup 6 --no-extras --no-cpu-baseline > $O/b$l.json 2>$O/b$l.err
+python3 bench.py --full --in-flight $l --steps 200 --warmup 6 --no-extras --no-cpu-baseline > $O/b$l.json 2>$O/b$l.err
 python3 -c "
 import json; d=json.loads(open('$O/b$l.json').read().strip().splitlines()[-1]); print('lanes $l value', d['value'], 'fallback', d['roofline']['dominant_stage'].get('fallback_tiles'), 'stages', {k:v['avg_ms'] for k,v in d['stages'].items()})"
 done
