@@ -179,6 +179,10 @@ int  lfg_ring_fence_slot(lfg_ring *ring, uint32_t slot);
  * Lanczos-3 resample of `in` to `out`'s size; push constants inputSize/outputSize are taken
  * from the frames (src/scaler.cpp:348-351).  Any sizes; out == 2 x in takes the LDS-tiled path. */
 int  lfg_scale(lfg_context *ctx, const lfg_frame *in, lfg_frame *out);
+/* Which scale kernel the context's last lfg_scale or lfg_interpolate_scale launched: 0 the generic kernel (any sizes; also
+ * 2x when the pitch or alignment rules fail, or a frame spans 2 GiB or more), 1 the exact-2x kernel, 2 the fused
+ * interpolate -> 2x scale kernel; -1 before any scale.  Tests and reporting only. */
+int  lfg_scale_last_kernel(const lfg_context *ctx);
 
 /* shaders/motion.comp as dispatched by FrameManager::InterpolateFrames
  * (src/frame_manager.cpp:325-344): per-pixel full-search block match of `curr` against `prev`.

@@ -106,6 +106,7 @@ SIGNATURES = {
     "lfg_broadcast_frame_lane": (_i, [_vp, _FP, _i]),
     "lfg_comm_probe_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "lfg_motion_last_variant": (_i, [_vp]),
+    "lfg_scale_last_kernel": (_i, [_vp]),
     "lfg_diag_scale_2x_strip": (_i, [_u32, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_profile_enable": (_i, [_vp, _i]),
     "lfg_profile_reset": (_i, [_vp]),
@@ -325,6 +326,10 @@ class Context:
         n = ctypes.c_uint64()
         self._check(self.lib.lfg_motion_workspace_size(self.h, width, height, ctypes.byref(n)), "lfg_motion_workspace_size")
         return n.value
+
+    def scale_last_kernel(self) -> int:
+        """Which kernel the context's last scale or interpolate_scale launched: 0 generic, 1 exact 2x, 2 fused interpolate -> 2x; -1 none yet."""
+        return int(self.lib.lfg_scale_last_kernel(self.h))
 
     def motion_last_variant(self) -> int:
         """Which variant of the persistent kernel the context's last lfg_motion launched: 0 the default, 1 the one for moderate sensor noise."""

@@ -772,8 +772,11 @@ LFG_EXPORT int lfg_scale(lfg_context *ctx, const lfg_frame *in, lfg_frame *out) 
     hipError_t e = fast ? lfg::launch_scale_2x(ctx->stream, *in, *out, *tx, *ty)
                         : lfg::launch_scale_generic(ctx->stream, *in, *out, *tx, *ty);
     if (e != hipSuccess) return fail_hip(ctx, e, "scale kernel launch");
+    ctx->scale_last_kernel = fast ? 1 : 0;
     return LFG_OK;
 }
+
+LFG_EXPORT int lfg_scale_last_kernel(const lfg_context *ctx) { return ctx ? ctx->scale_last_kernel : -1; }
 
 // lfg_motion, and -- fused != nullptr -- the motion stage of lfg_interpolate_frames in the north-star order: the kernels
 // write the generated frame themselves (lfg_internal.hpp: FusedOut).  *fusedDone tells the caller whether they did (the
@@ -1208,6 +1211,7 @@ LFG_EXPORT int lfg_interpolate_scale(lfg_context *ctx, const lfg_frame *prev, co
         StageTimer timer(ctx, LFG_STAGE_SCALE);
         hipError_t e = lfg::launch_interpolate_scale_2x(ctx->stream, *prev, *curr, *mv, *out, *tx, *ty, factor, ctx->semantics != 0);
         if (e != hipSuccess) return fail_hip(ctx, e, "fused interpolate + scale kernel launch");
+        ctx->scale_last_kernel = 2;
         return LFG_OK;
     }
     // any other size ratio: the two stages, through a context-owned frame at input resolution

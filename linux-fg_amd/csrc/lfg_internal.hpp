@@ -222,6 +222,7 @@ struct lfg_context {
     hipEvent_t comm_ready = nullptr, comm_done = nullptr;
     bool comm_pending = false;                 // some broadcast has been issued on this communicator (comm_done has been recorded)
     hipEvent_t probe_begin = nullptr, probe_end = nullptr;     // lfg_comm_probe: device timestamps, ready and done
+    int scale_last_kernel = -1;                // 0 generic, 1 exact 2x, 2 fused interpolate -> 2x (lfg_scale_last_kernel)
     int motion_last_tier = 0;                  // the persistent kernel's variant of the last lfg_motion on any lane (lfg_motion_last_variant)
     int comm_cus = 0;                          // CUs the library's own streams leave to the communicator's kernels (0: none reserved)
     // profiling

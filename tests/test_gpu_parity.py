@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from linux_fg_amd import synth
+from oracle import scale_f64 as f64
 
 pytestmark = pytest.mark.gpu
 
@@ -67,6 +68,26 @@ def assert_within_1lsb(got, want, max_mismatch=0.05):
     return frac
 
 
+def assert_matches_f64(got, V, eps=1e-3, what=""):
+    """The kernel's bytes against the float64 model's unrounded values V (oracle/scale_f64.py): within half an LSB plus
+    eps everywhere, and exactly rint(clip(V)) wherever V is further than eps from a rounding boundary.  The kernels'
+    fp32 arithmetic stays within ~1e-4 LSB of V, so this is ~500 times tighter than +-1 LSB; with the bound on the
+    shader (tests/test_scale_model.py) it gives +-1 LSB against the shader for every input.  Returns the near-ties."""
+    c = np.clip(V, 0.0, 255.0)
+    d = np.abs(got.astype(np.float64) - c)
+    at = tuple(int(i) for i in np.unravel_index(d.argmax(), d.shape))
+    assert d.max() <= 0.5 + eps, f"{what}: |got - V| = {d.max():.5f} at {at} (got {got[at]}, V {V[at]:.5f})"
+    near = f64.near_half(V, eps)
+    bad = ~near & (got != np.rint(c))
+    if bad.any():
+        at = tuple(int(i) for i in np.argwhere(bad)[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {got.size} bytes differ from rint(V) away from a tie, "
+                             f"first at {at} (got {got[at]}, V {V[at]:.5f})")
+    ties = int(near.sum())
+    print(f"f64 model {what}: {ties} near-ties in {got.size} bytes")
+    return ties
+
+
 # ------------------------------------------------------------------------------ scale
 
 @pytest.mark.parametrize("in_wh,out_wh", [
@@ -83,6 +104,7 @@ def test_scale_matches_oracle(ctx, oracle, in_wh, out_wh):
     got = run_scale(ctx, f, *out_wh)
     want = oracle.scale(f, *out_wh)
     assert_within_1lsb(got, want)
+    assert_matches_f64(got, f64.scale_f64(f, *out_wh), what=f"{in_wh} -> {out_wh}")
 
 
 def test_scale_constant_colour(ctx):
@@ -116,6 +138,7 @@ def test_scale_config1_540p_to_1080p_full_frame(ctx, oracle):
     for src in (prev, synth.noise_bytes(960, 540, 540960)):
         got = run_scale(ctx, src, 1920, 1080)
         assert_within_1lsb(got, oracle.scale(src, 1920, 1080))
+        assert_matches_f64(got, f64.scale_f64(src, 1920, 1080), what="540p -> 1080p")
 
 
 def test_scale_1080p_to_4k_roi(ctx, oracle):
@@ -128,6 +151,7 @@ def test_scale_1080p_to_4k_roi(ctx, oracle):
         want = oracle.scale(prev, 3840, 2160, roi=roi)
         x0, y0, x1, y1 = roi
         assert_within_1lsb(got[y0:y1, x0:x1], want[y0:y1, x0:x1])
+        assert_matches_f64(got[y0:y1, x0:x1], f64.scale_f64(prev, 3840, 2160, roi=roi), what=f"1080p -> 4K {roi}")
 
 
 def test_scale_1080p_to_4k_every_pixel_repeated(ctx, oracle):
@@ -139,19 +163,134 @@ def test_scale_1080p_to_4k_every_pixel_repeated(ctx, oracle):
     prev, curr = synth.make_pair(1920, 1080, stream=0, shift=(3, -2))
     ups = []
     for src in (prev, curr):
-        want = oracle.scale(src, 3840, 2160)
+        want, V = oracle.scale(src, 3840, 2160), f64.scale_f64(src, 3840, 2160)
+        print(f"oracle bytes != rint(V) at 1080p -> 4K: {float((want != np.rint(np.clip(V, 0, 255))).mean()):.3%}")
         s, d = ctx.frame_from(src), ctx.create_frame(3840, 2160)
         for _ in range(4):
             ctx.scale(s, d)
             ctx.sync()
             got = ctx.download(d)
-            assert_within_1lsb(got, want)
+            frac = assert_within_1lsb(got, want)
+            assert_matches_f64(got, V, what="1080p -> 4K, benchmark frame")
+        print(f"kernel bytes != oracle at 1080p -> 4K: {frac:.3%}")
         ups.append(got)
         ctx.destroy_frame(s)
         ctx.destroy_frame(d)
     P, C = ups
     d = np.abs(C[16:2160 - 16, 16:3840 - 16].astype(np.int16) - P[16 + 4:2160 - 16 + 4, 16 - 6:3840 - 16 - 6].astype(np.int16))
     assert d.max() <= 1 and float((d != 0).mean()) < 1e-3
+
+
+# ------------------------------------------------------------------------------ scale against the float64 model
+#
+# Every pixel held to oracle/scale_f64.py with assert_matches_f64, and each case asserts which kernel ran
+# (lfg_scale_last_kernel: 0 generic, 1 exact 2x, 2 fused interpolate -> 2x), so a sweep cannot quietly test the other one.
+
+def _seam_rows(in_h):
+    """Input rows that straddle the 2x kernel's strip and XCD-band seams: an impulse at row first - 3 of a strip
+    reaches the last output rows of the strip above it and the first of its own."""
+    import ctypes
+    from linux_fg_amd import capi
+    lib = capi.load()
+    per, first, steps = ctypes.c_uint32(), ctypes.c_int32(), ctypes.c_int32()
+    assert lib.lfg_diag_scale_2x_strip(in_h, 0, 0, ctypes.byref(per), None, None) == 0
+    rows = set()
+    for x in range(8):
+        for i in range(per.value):
+            assert lib.lfg_diag_scale_2x_strip(in_h, x, i, None, ctypes.byref(first), ctypes.byref(steps)) == 0
+            if steps.value > 0:
+                rows.add(first.value - 3)
+    return sorted(r for r in rows if 0 <= r < in_h)
+
+
+def _scale_checked(ctx, src, ow, oh, kernel, what):
+    got = run_scale(ctx, src, ow, oh)
+    assert ctx.scale_last_kernel() == kernel, f"{what}: kernel {ctx.scale_last_kernel()}, expected {kernel}"
+    return assert_matches_f64(got, f64.scale_f64(src, ow, oh), what=what)
+
+
+def test_scale_last_kernel_before_any_scale():
+    from linux_fg_amd import capi
+    with capi.Context(0) as c:
+        assert c.scale_last_kernel() == -1
+
+
+@pytest.mark.parametrize("wh", f64.sweep_2x_shapes(), ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_scale_2x_kernel_sweep_against_the_model(ctx, wh):
+    """The exact-2x kernel at input widths around its 120 owned columns per wave and 480 per workgroup, and heights
+    from 1 to the strip lengths: every content, every pixel."""
+    w, h = wh
+    for name, src in f64.contents(w, h, seed=1000 * w + h, seam_rows=_seam_rows(h)).items():
+        _scale_checked(ctx, src, 2 * w, 2 * h, 1, f"2x {w}x{h} {name}")
+
+
+@pytest.mark.parametrize("in_wh,out_wh", f64.GENERIC_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_scale_generic_kernel_against_the_model(ctx, in_wh, out_wh):
+    """The generic kernel at ratios that ship, at 2x of an odd width, and at degenerate sizes, every pixel.  Large
+    frames take the ramps (x and y ramps, noise, checkerboard: one channel each); small ones every content."""
+    frames = f64.contents(*in_wh, seed=in_wh[0] + 7 * in_wh[1])
+    if in_wh[0] * in_wh[1] > 10_000:
+        frames = {"ramps": frames["ramps"]}
+    for name, src in frames.items():
+        _scale_checked(ctx, src, *out_wh, 0, f"{in_wh} -> {out_wh} {name}")
+
+
+@pytest.mark.parametrize("w,h", [(242, 35), (64, 36)])
+def test_scale_pitched_frames_against_the_model(ctx, w, h):
+    """Input rows 4(w+1) and 4(w+3) bytes apart; output rows a larger multiple of 16 bytes apart (the 2x kernel) or
+    8 mod 16 (the generic kernel: the 2x kernel stores 16 bytes at a time).  The padding is never written."""
+    src = f64.contents(w, h, seed=w * h)["ramps"]
+    V = f64.scale_f64(src, 2 * w, 2 * h)
+    for in_pad in (1, 3):
+        bi, vi = _pitched(ctx, src, in_pad)
+        for out_pad, kernel in ((4, 1), (2, 0)):
+            assert ((2 * w + out_pad) * 4) % 16 == (0 if kernel else 8)
+            bo, vo = _pitched(ctx, np.zeros((2 * h, 2 * w, 4), np.uint8), out_pad)
+            ctx.scale(vi, vo)
+            assert ctx.scale_last_kernel() == kernel, (in_pad, out_pad)
+            full = ctx.download(bo)
+            assert (full[:, 2 * w:] == 0x5A).all()
+            assert_matches_f64(full[:, :2 * w], V, what=f"{w}x{h} pitch +{in_pad} -> +{out_pad}")
+            ctx.destroy_frame(bo)
+        ctx.destroy_frame(bi)
+
+
+def test_scale_full_size_1080p_to_4k_against_the_model(ctx):
+    """The benchmark pair's size, every pixel, on the benchmark frame, on noise and on the checkerboard."""
+    prev, _ = synth.make_pair(1920, 1080, stream=0)
+    frames = f64.contents(1920, 1080, seed=2160)
+    for name, src in (("benchmark", prev), ("noise", frames["noise"]), ("checker", frames["checker"])):
+        _scale_checked(ctx, src, 3840, 2160, 1, f"1080p -> 4K {name}")
+
+
+@pytest.mark.parametrize("big", ["output", "input"])
+def test_scale_frames_of_2_gib_and_more_take_the_generic_kernel(ctx, big):
+    """The 2x kernel addresses with 32-bit byte offsets; a 2x upscale whose input or output view spans 2 GiB or more
+    (wrapped views with rows tens of MB apart, as in the motion test) must take the size_t-indexed generic kernel,
+    and still match the model."""
+    from linux_fg_amd import capi
+    w, h = 64, 40
+    src = f64.contents(w, h, seed=2 ** 31)["ramps"]
+    alloc = ctx.create_frame(24000, 24000)                        # 2.304e9 bytes
+    if big == "input":
+        pitch = 57_600_000                                        # 39 * pitch + 256 < 2.304e9
+        vin = capi.Context.wrap(alloc.data, w, h, capi.FORMAT_RGBA8, pitch=pitch)
+        assert vin.height * vin.pitch >= 2 ** 31
+        ctx.upload(vin, src)
+        out = ctx.create_frame(2 * w, 2 * h)
+        ctx.scale(vin, out)
+        frames = [out]
+    else:
+        pitch = 27_000_000                                        # a multiple of 16; 79 * pitch + 512 < 2.304e9
+        inp = ctx.frame_from(src)
+        out = capi.Context.wrap(alloc.data, 2 * w, 2 * h, capi.FORMAT_RGBA8, pitch=pitch)
+        assert out.height * out.pitch >= 2 ** 31
+        ctx.scale(inp, out)
+        frames = [inp]
+    assert ctx.scale_last_kernel() == 0
+    assert_matches_f64(ctx.download(out), f64.scale_f64(src, 2 * w, 2 * h), what=f"2 GiB {big}")
+    for f in frames + [alloc]:
+        ctx.destroy_frame(f)
 
 
 # ------------------------------------------------------------------------------ motion
@@ -633,6 +772,10 @@ def test_three_stages_at_8k(ctx, oracle):
     for roi in rois:
         x0, y0, x1, y1 = roi
         assert_within_1lsb(Cn[y0:y1, x0:x1], oracle.scale(cin, W, H, roi=roi)[y0:y1, x0:x1], max_mismatch=0.08)
+        assert_matches_f64(Cn[y0:y1, x0:x1], f64.scale_f64(cin, W, H, roi=roi), what=f"4K -> 8K {roi}")
+    # every pixel of the config-5 input's upscale against the float64 model (in bands of rows: bounded memory)
+    for y0 in range(0, H, 540):
+        assert_matches_f64(Pn[y0:y0 + 540], f64.scale_f64(pin, W, H, roi=(0, y0, W, y0 + 540)), what=f"4K -> 8K rows {y0}..")
     inner = Mn[48:H - 48, 48:W - 48]
     assert (inner[..., 0] == 4).all() and (inner[..., 1] == -10).all()
     # ... and against the ORACLE itself where the oracle can afford it at this size (round 3 checked 8K vectors by the
@@ -945,10 +1088,13 @@ def test_interpolate_scale_equals_the_two_stages(ctx, oracle, wh, out_wh):
                     ctx.set_fused_interpolate_scale(fuse)
                     ctx.interpolate_scale(p, c, m, fused, t)
                     b = ctx.download(fused)
+                    assert ctx.scale_last_kernel() == ((2 if fuse else 1) if (ow, oh) == (2 * w, 2 * h) else 0)
                     assert (a == b).all(), f"{(a != b).any(-1).sum()} pixels differ (semantics {sem}, t {t}, fused {fuse})"
                 if sem == capi.SEMANTICS_REFERENCE:
-                    want = oracle.scale(oracle.interpolate(prev, curr, mv.astype(np.float32), t), ow, oh)
+                    mid_want = oracle.interpolate(prev, curr, mv.astype(np.float32), t)
+                    want = oracle.scale(mid_want, ow, oh)
                     assert_within_1lsb(b, want)
+                    assert_matches_f64(b, f64.scale_f64(mid_want, ow, oh), what=f"interpolate -> scale {wh} -> {out_wh}")
         finally:
             ctx.set_semantics(capi.SEMANTICS_REFERENCE)
             ctx.set_fused_interpolate_scale(False)
@@ -962,7 +1108,7 @@ def test_interpolate_scale_equals_the_two_stages(ctx, oracle, wh, out_wh):
         ctx.destroy_frame(f)
 
 
-def test_interpolate_scale_1080p_to_4k(ctx):
+def test_interpolate_scale_1080p_to_4k(ctx, oracle):
     """The benchmark's input-resolution variant at full size: fused kernel == the two stages, on the device's own motion vectors."""
     from linux_fg_amd import capi
     prev, curr = synth.make_pair(1920, 1080, stream=0, shift=(3, -2))
@@ -975,9 +1121,14 @@ def test_interpolate_scale_1080p_to_4k(ctx):
     ctx.set_fused_interpolate_scale(True)
     try:
         ctx.interpolate_scale(p, c, m, fused, 0.5)
+        assert ctx.scale_last_kernel() == 2
     finally:
         ctx.set_fused_interpolate_scale(False)
-    assert (ctx.download(staged) == ctx.download(fused)).all()
+    got = ctx.download(fused)
+    assert (ctx.download(staged) == got).all()
+    # and the fused kernel against the float64 model of the oracle's interpolated frame (interpolate is exact)
+    mid_want = oracle.interpolate(prev, curr, ctx.download(m).astype(np.float32), 0.5)
+    assert_matches_f64(got, f64.scale_f64(mid_want, 3840, 2160), what="fused interpolate -> scale 1080p -> 4K")
     for f in (p, c, m, mid, staged, fused):
         ctx.destroy_frame(f)
 
@@ -1153,6 +1304,8 @@ def test_all_stages_with_row_pitch_larger_than_width(ctx, oracle, pad):
     Pn, Cn, Mn, On = (_read_pitched(ctx, b, W) for b in (bP, bC, bM, bO))
     assert_within_1lsb(Pn, oracle.scale(prev, W, H))
     assert_within_1lsb(Cn, oracle.scale(curr, W, H))
+    assert_matches_f64(Pn, f64.scale_f64(prev, W, H), what=f"pitch +{pad}")
+    assert_matches_f64(Cn, f64.scale_f64(curr, W, H), what=f"pitch +{pad}")
     mv = oracle.motion(Pn, Cn)
     assert (Mn == mv.astype(np.int8)).all()
     assert (On == oracle.interpolate(Pn, Cn, mv, 0.5)).all()
