@@ -130,9 +130,8 @@ int build_axis_table(lfg_context *ctx, int in_size, int out_size, lfg::AxisTable
 
 // Everything the context has enqueued, on every lane (a resource shared by the lanes is about to go or to be read).
 hipError_t sync_lanes(lfg_context *ctx) {
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    for (size_t j = 0; j < ctx->lanes.size() && e == hipSuccess; ++j)
-        if ((int)j != ctx->lane && ctx->lanes[j].stream) e = hipStreamSynchronize(ctx->lanes[j].stream);
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < ctx->lanes.size() && e == hipSuccess; ++k) e = hipStreamSynchronize(ctx->from_selected(k).stream);
     return e;
 }
 
@@ -262,31 +261,25 @@ int motion_rim_split_lean(const lfg_context *ctx) {
     return (ctx->motion_lean && ctx->lanes.size() >= 2 && !ctx->rim_split_env) ? 48 : 0;
 }
 
-// Workgroups of the persistent kernel a launch of this context may have: what the device holds at once -- less the CUs a communicator
-// keeps, where the library's streams cannot place any (lfg_own_stream_create).
-int persistent_grid_most(const lfg_context *ctx) {
-    if (ctx->comm_cus <= 0 || ctx->device_cus <= ctx->comm_cus) return ctx->motion_slots;
-    return ctx->motion_slots / ctx->device_cus * (ctx->device_cus - ctx->comm_cus);
-}
-
 int ensure_motion_workspace(lfg_context *ctx, uint32_t width, uint32_t height) {
+    lfg_lane_state &cur = ctx->cur();
     const int rimSplit = motion_rim_split(ctx), rimSplit2 = motion_rim_split_lean(ctx);
-    if (ctx->motion_ws && ctx->motion_ws_w == width && ctx->motion_ws_h == height && ctx->motion_ws_layout.rimSplit == rimSplit &&
-        ctx->motion_ws_layout.rimSplit2 == rimSplit2) return LFG_OK;
+    if (cur.motion_ws && cur.motion_ws_w == width && cur.motion_ws_h == height && cur.motion_ws_layout.rimSplit == rimSplit &&
+        cur.motion_ws_layout.rimSplit2 == rimSplit2) return LFG_OK;
     lfg::MotionWorkspaceLayout layout;
     if (ctx->motion_slots == 0) {
         ctx->motion_slots = lfg::prefilter_slots();
         if (ctx->knobs.debug) fprintf(stderr, "lfg: motion prefilter: %d workgroups resident at once\n", ctx->motion_slots);
     }
     const size_t bytes = lfg::motion_workspace_bytes(width, height, ctx->motion_slots, rimSplit, rimSplit2, &layout);
-    if (bytes > ctx->motion_ws_bytes) {
-        LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));          // a queued kernel may still use the old one
-        if (ctx->motion_ws) (void)hipFree(ctx->motion_ws);
-        ctx->motion_ws = nullptr; ctx->motion_ws_bytes = 0; ctx->motion_ws_w = ctx->motion_ws_h = 0;
-        LFG_HIP(ctx, hipMalloc((void **)&ctx->motion_ws, bytes));
-        ctx->motion_ws_bytes = bytes;
+    if (bytes > cur.motion_ws_bytes) {
+        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // a queued kernel may still use the old one
+        if (cur.motion_ws) (void)hipFree(cur.motion_ws);
+        cur.motion_ws = nullptr; cur.motion_ws_bytes = 0; cur.motion_ws_w = cur.motion_ws_h = 0;
+        LFG_HIP(ctx, hipMalloc((void **)&cur.motion_ws, bytes));
+        cur.motion_ws_bytes = bytes;
     } else {
-        LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     }
     // work-unit tables of this frame size: unitMap | unitAux | tileMap
     const lfg::PrefilterPlanHost plan = lfg::prefilter_plan(width, height, ctx->motion_slots, rimSplit);
@@ -294,28 +287,28 @@ int ensure_motion_workspace(lfg_context *ctx, uint32_t width, uint32_t height) {
     tables.insert(tables.end(), plan.unitMap.begin(), plan.unitMap.end());
     tables.insert(tables.end(), plan.unitAux.begin(), plan.unitAux.end());
     tables.insert(tables.end(), plan.tileMap.begin(), plan.tileMap.end());
-    LFG_HIP(ctx, hipMemcpy(ctx->motion_ws + layout.plan, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    LFG_HIP(ctx, hipMemcpy(cur.motion_ws + layout.plan, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (rimSplit2) {        // the plan of the calls that go through the lean kernel, and that kernel's tiles
         const lfg::PrefilterPlanHost plan2 = lfg::prefilter_plan(width, height, ctx->motion_slots, rimSplit2);
         std::vector<uint32_t> t2;
         t2.insert(t2.end(), plan2.unitMap.begin(), plan2.unitMap.end());
         t2.insert(t2.end(), plan2.unitAux.begin(), plan2.unitAux.end());
         t2.insert(t2.end(), plan2.tileMap.begin(), plan2.tileMap.end());
-        LFG_HIP(ctx, hipMemcpy(ctx->motion_ws + layout.plan2, t2.data(), t2.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LFG_HIP(ctx, hipMemcpy(cur.motion_ws + layout.plan2, t2.data(), t2.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (!plan2.leanTiles.empty()) {
             std::vector<uint32_t> listed = plan2.leanTiles;
             listed.insert(listed.end(), plan2.leanPartial.begin(), plan2.leanPartial.end());
-            LFG_HIP(ctx, hipMemcpy(ctx->motion_ws + layout.leanTiles, listed.data(), listed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            LFG_HIP(ctx, hipMemcpy(cur.motion_ws + layout.leanTiles, listed.data(), listed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
     // what the kernels expect to find between calls: a cleared control area (the hint kernel's counter of finished
     // workgroups lies in it, and that kernel is what clears the rest per call) and the merge words of the flagged tiles all ones
-    LFG_HIP(ctx, hipMemset(ctx->motion_ws + layout.tileFlags, 0, layout.order - layout.tileFlags));
-    LFG_HIP(ctx, hipMemset(ctx->motion_ws + layout.merge, 0xFF, layout.mergeBytes));
-    ctx->motion_units = plan.units;
+    LFG_HIP(ctx, hipMemset(cur.motion_ws + layout.tileFlags, 0, layout.order - layout.tileFlags));
+    LFG_HIP(ctx, hipMemset(cur.motion_ws + layout.merge, 0xFF, layout.mergeBytes));
+    cur.motion_units = plan.units;
     layout.lastLean = 0;
-    ctx->motion_ws_layout = layout;
-    ctx->motion_ws_w = width; ctx->motion_ws_h = height;
+    cur.motion_ws_layout = layout;
+    cur.motion_ws_w = width; cur.motion_ws_h = height;
     return LFG_OK;
 }
 
@@ -329,11 +322,11 @@ struct StageTimer {
         if (!ctx->profile) return;
         if (!ctx->prof_free.empty()) { b = ctx->prof_free.back().first; e = ctx->prof_free.back().second; ctx->prof_free.pop_back(); }
         else if (hipEventCreate(&b) != hipSuccess || hipEventCreate(&e) != hipSuccess) { b = e = nullptr; return; }
-        (void)hipEventRecord(b, ctx->stream);
+        (void)hipEventRecord(b, ctx->cur().stream);
     }
     ~StageTimer() {
         if (!b) return;
-        (void)hipEventRecord(e, ctx->stream);
+        (void)hipEventRecord(e, ctx->cur().stream);
         lfg::ProfileSlot s; s.begin = b; s.end = e; s.stage = stage;
         ctx->prof_pending.push_back(s);
     }
@@ -361,8 +354,8 @@ struct lfg_ring {
     std::vector<hipEvent_t> done;            // last transfer touching each slot
     std::vector<uint8_t> busy;
     uint32_t next = 0;
-    hipStream_t copy = nullptr;              // transfers run here, next to the kernels on ctx->stream
-    hipEvent_t ready = nullptr;              // scratch event: "ctx->stream has reached this point"
+    hipStream_t copy = nullptr;              // transfers run here, next to the kernels on the selected lane's stream
+    hipEvent_t ready = nullptr;              // scratch event: "the selected lane's stream has reached this point"
 };
 
 // ================================================================== library / context
@@ -400,9 +393,10 @@ int lfg_restream(lfg_context *ctx) {
         own = fresh;
         return hipSuccess;
     };
-    LFG_HIP(ctx, again(ctx->own_stream, ctx->stream));
-    for (size_t j = 0; j < ctx->lanes.size(); ++j)
-        if ((int)j != ctx->lane) LFG_HIP(ctx, again(ctx->lanes[j].own_stream, ctx->lanes[j].stream));     // (the selected lane's are the context's own fields)
+    for (size_t k = 0; k < ctx->lanes.size(); ++k) {
+        lfg_lane_state &l = ctx->from_selected(k);
+        LFG_HIP(ctx, again(l.own_stream, l.stream));
+    }
     return LFG_OK;
 }
 
@@ -429,9 +423,11 @@ LFG_EXPORT int lfg_context_create(int device_ordinal, lfg_context **out_ctx) {
     if (!ctx) return fail(nullptr, LFG_ERR_NOMEM, "lfg_context_create: out of host memory");
     ctx->device = dev;
     (void)hipDeviceGetAttribute(&ctx->device_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    e = lfg_own_stream_create(ctx, &ctx->own_stream);
+    lfg_lane_state lane0;
+    e = lfg_own_stream_create(ctx, &lane0.own_stream);
     if (e != hipSuccess) { delete ctx; return fail_hip(nullptr, e, "hipStreamCreate"); }
-    ctx->stream = ctx->own_stream;
+    lane0.stream = lane0.own_stream;
+    ctx->lanes.push_back(lane0);
     ctx->tables.reserve(17);                 // AxisTable pointers handed out stay valid
     if (const char *m = getenv("LFG_MOTION_HINTS")) ctx->motion_hints = atoi(m) != 0;
     if (const char *m = getenv("LFG_MOTION_LEAN")) ctx->motion_lean = atoi(m) != 0;
@@ -456,20 +452,7 @@ LFG_EXPORT int lfg_context_create(int device_ordinal, lfg_context **out_ctx) {
     return LFG_OK;
 }
 
-// (lanes, further down: what a lane owns moves between the context's fields and its table entry)
 namespace {
-void lane_store(lfg_context *ctx, lfg_lane_state &l) {
-    l.own_stream = ctx->own_stream; l.stream = ctx->stream; l.mv_tmp = ctx->mv_tmp; l.mid_tmp = ctx->mid_tmp;
-    l.motion_ws = ctx->motion_ws; l.motion_ws_bytes = ctx->motion_ws_bytes; l.motion_ws_w = ctx->motion_ws_w; l.motion_ws_h = ctx->motion_ws_h;
-    l.motion_ws_layout = ctx->motion_ws_layout; l.motion_units = ctx->motion_units; l.mark = ctx->mark; l.marked = ctx->marked;
-    l.lean_flag = ctx->lean_flag; l.lean_ev = ctx->lean_ev; l.lean_ev_pending = ctx->lean_ev_pending; l.lean_predict = ctx->lean_predict; l.lean_seen = ctx->lean_seen; l.lean_request_guess = ctx->lean_request_guess;
-}
-void lane_load(lfg_context *ctx, const lfg_lane_state &l) {
-    ctx->own_stream = l.own_stream; ctx->stream = l.stream; ctx->mv_tmp = l.mv_tmp; ctx->mid_tmp = l.mid_tmp;
-    ctx->motion_ws = l.motion_ws; ctx->motion_ws_bytes = l.motion_ws_bytes; ctx->motion_ws_w = l.motion_ws_w; ctx->motion_ws_h = l.motion_ws_h;
-    ctx->motion_ws_layout = l.motion_ws_layout; ctx->motion_units = l.motion_units; ctx->mark = l.mark; ctx->marked = l.marked;
-    ctx->lean_flag = l.lean_flag; ctx->lean_ev = l.lean_ev; ctx->lean_ev_pending = l.lean_ev_pending; ctx->lean_predict = l.lean_predict; ctx->lean_seen = l.lean_seen; ctx->lean_request_guess = l.lean_request_guess;
-}
 void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
@@ -477,8 +460,8 @@ void lane_release(lfg_lane_state &l) {
     if (l.mid_tmp.data && l.mid_tmp.owned) (void)hipFree(l.mid_tmp.data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.mark) (void)hipEventDestroy(l.mark);
-    if (l.lean_ev) (void)hipEventDestroy(l.lean_ev);
-    if (l.lean_flag) (void)hipHostFree(l.lean_flag);
+    if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
+    if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
     if (l.own_stream) (void)hipStreamDestroy(l.own_stream);
     l = lfg_lane_state{};
 }
@@ -488,22 +471,13 @@ LFG_EXPORT void lfg_context_destroy(lfg_context *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)lfg_comm_destroy(ctx);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream != ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-    for (size_t j = 0; j < ctx->lanes.size(); ++j)
-        if ((int)j != ctx->lane) lane_release(ctx->lanes[j]);      // (the selected lane's resources are the context's own fields)
-    if (ctx->mark) (void)hipEventDestroy(ctx->mark);
-    if (ctx->lean_ev) (void)hipEventDestroy(ctx->lean_ev);
-    if (ctx->lean_flag) (void)hipHostFree(ctx->lean_flag);
+    (void)sync_lanes(ctx);
+    for (auto &l : ctx->lanes) lane_release(l);
     for (auto &s : ctx->prof_pending) { (void)hipEventDestroy(s.begin); (void)hipEventDestroy(s.end); }
     for (auto &p : ctx->prof_free) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &t : ctx->tables) { (void)hipFree(t.d_start); (void)hipFree(t.d_weight); (void)hipFree(t.d_class); (void)hipFree(t.d_palette); }
     for (auto &t : ctx->uv_tables) (void)hipFree(t.d_uv);
-    if (ctx->mv_tmp.data && ctx->mv_tmp.owned) (void)hipFree(ctx->mv_tmp.data);
-    if (ctx->mid_tmp.data && ctx->mid_tmp.owned) (void)hipFree(ctx->mid_tmp.data);
     if (ctx->motion_tables) (void)hipFree(ctx->motion_tables);
-    if (ctx->motion_ws) (void)hipFree(ctx->motion_ws);
-    (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
 
@@ -511,12 +485,12 @@ LFG_EXPORT int lfg_context_set_stream(lfg_context *ctx, void *hip_stream) {
     if (!ctx) return LFG_ERR_INVALID;
     int rc = drain_profile(ctx);
     if (rc != LFG_OK) return rc;
-    LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    LFG_HIP(ctx, hipStreamSynchronize(ctx->cur().stream));
+    ctx->cur().stream = hip_stream ? (hipStream_t)hip_stream : ctx->cur().own_stream;
     return LFG_OK;
 }
 
-LFG_EXPORT void *lfg_context_get_stream(lfg_context *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
+LFG_EXPORT void *lfg_context_get_stream(lfg_context *ctx) { return ctx ? (void *)ctx->cur().stream : nullptr; }
 
 // ------------------------------------------------------------------ lanes: several frames in flight on one GPU
 
@@ -524,11 +498,7 @@ LFG_EXPORT int lfg_lanes(lfg_context *ctx, int count) {
     if (!ctx) return LFG_ERR_INVALID;
     if (count < 1 || count > LFG_MAX_LANES) return fail(ctx, LFG_ERR_INVALID, "lfg_lanes: count must be 1 .. LFG_MAX_LANES");
     LFG_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->lanes.empty()) { ctx->lanes.resize(1); ctx->lane = 0; }
-    if (ctx->lane >= count) {                  // the selected lane is about to go: back to lane 0 first
-        int rc = lfg_lane_select(ctx, 0);
-        if (rc != LFG_OK) return rc;
-    }
+    if (ctx->lane >= count) ctx->lane = 0;     // the selected lane is about to go: back to lane 0 first
     while ((int)ctx->lanes.size() > count) { lane_release(ctx->lanes.back()); ctx->lanes.pop_back(); }
     while ((int)ctx->lanes.size() < count) {
         lfg_lane_state l;
@@ -540,15 +510,12 @@ LFG_EXPORT int lfg_lanes(lfg_context *ctx, int count) {
     return LFG_OK;
 }
 
-LFG_EXPORT int lfg_lane_count(const lfg_context *ctx) { return ctx ? std::max<int>(1, (int)ctx->lanes.size()) : 0; }
+LFG_EXPORT int lfg_lane_count(const lfg_context *ctx) { return ctx ? (int)ctx->lanes.size() : 0; }
 LFG_EXPORT int lfg_lane_current(const lfg_context *ctx) { return ctx ? ctx->lane : -1; }
 
 LFG_EXPORT int lfg_lane_select(lfg_context *ctx, int lane) {
     if (!ctx) return LFG_ERR_INVALID;
-    if (lane < 0 || lane >= std::max<int>(1, (int)ctx->lanes.size())) return fail(ctx, LFG_ERR_INVALID, "lfg_lane_select: no such lane (lfg_lanes first)");
-    if (lane == ctx->lane) return LFG_OK;
-    lane_store(ctx, ctx->lanes[(size_t)ctx->lane]);
-    lane_load(ctx, ctx->lanes[(size_t)lane]);
+    if (lane < 0 || lane >= (int)ctx->lanes.size()) return fail(ctx, LFG_ERR_INVALID, "lfg_lane_select: no such lane (lfg_lanes first)");
     ctx->lane = lane;
     return LFG_OK;
 }
@@ -556,26 +523,26 @@ LFG_EXPORT int lfg_lane_select(lfg_context *ctx, int lane) {
 LFG_EXPORT int lfg_lane_mark(lfg_context *ctx) {
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->mark) LFG_HIP(ctx, hipEventCreateWithFlags(&ctx->mark, hipEventDisableTiming));
-    LFG_HIP(ctx, hipEventRecord(ctx->mark, ctx->stream));
-    ctx->marked = true;
+    if (!ctx->cur().mark) LFG_HIP(ctx, hipEventCreateWithFlags(&ctx->cur().mark, hipEventDisableTiming));
+    LFG_HIP(ctx, hipEventRecord(ctx->cur().mark, ctx->cur().stream));
+    ctx->cur().marked = true;
     return LFG_OK;
 }
 
 LFG_EXPORT int lfg_lane_wait(lfg_context *ctx, int other) {
     if (!ctx) return LFG_ERR_INVALID;
-    if (other < 0 || other >= std::max<int>(1, (int)ctx->lanes.size())) return fail(ctx, LFG_ERR_INVALID, "lfg_lane_wait: no such lane");
+    if (other < 0 || other >= (int)ctx->lanes.size()) return fail(ctx, LFG_ERR_INVALID, "lfg_lane_wait: no such lane");
     if (other == ctx->lane) return LFG_OK;     // a stream is in order with itself
     const lfg_lane_state &o = ctx->lanes[(size_t)other];
     if (!o.marked) return LFG_OK;              // nothing to wait for yet
-    LFG_HIP(ctx, hipStreamWaitEvent(ctx->stream, o.mark, 0));
+    LFG_HIP(ctx, hipStreamWaitEvent(ctx->cur().stream, o.mark, 0));
     return LFG_OK;
 }
 
 LFG_EXPORT int lfg_lane_sync(lfg_context *ctx) {
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
-    LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the selected lane's stream IS the context's current one
+    LFG_HIP(ctx, hipStreamSynchronize(ctx->cur().stream));
     return LFG_OK;
 }
 
@@ -629,7 +596,7 @@ LFG_EXPORT int lfg_frame_copy(lfg_context *ctx, const lfg_frame *src, lfg_frame 
         return fail(ctx, LFG_ERR_INVALID, "Source and destination frame dimensions do not match");
     const size_t row = (size_t)src->width * bytes_per_pixel(src->format);
     LFG_HIP(ctx, hipMemcpy2DAsync(dst->data, dst->pitch, src->data, src->pitch, row, src->height,
-                                  hipMemcpyDeviceToDevice, ctx->stream));
+                                  hipMemcpyDeviceToDevice, ctx->cur().stream));
     return LFG_OK;
 }
 
@@ -654,7 +621,7 @@ LFG_EXPORT int lfg_frame_upload(lfg_context *ctx, lfg_frame *dst, const void *ho
         snprintf(msg, sizeof msg, "Captured image size (%zu) smaller than expected (%zu)", bytes, row * dst->height);
         return fail(ctx, LFG_ERR_INVALID, msg);
     }
-    LFG_HIP(ctx, hipMemcpy2DAsync(dst->data, dst->pitch, host, row, row, dst->height, hipMemcpyHostToDevice, ctx->stream));
+    LFG_HIP(ctx, hipMemcpy2DAsync(dst->data, dst->pitch, host, row, row, dst->height, hipMemcpyHostToDevice, ctx->cur().stream));
     return LFG_OK;
 }
 
@@ -662,7 +629,7 @@ LFG_EXPORT int lfg_frame_download(lfg_context *ctx, const lfg_frame *src, void *
     if (!ctx || !src || !src->data || !host) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_download: NULL argument");
     const size_t row = (size_t)src->width * bytes_per_pixel(src->format);
     if (bytes < row * src->height) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_download: host buffer too small");
-    LFG_HIP(ctx, hipMemcpy2DAsync(host, row, src->data, src->pitch, row, src->height, hipMemcpyDeviceToHost, ctx->stream));
+    LFG_HIP(ctx, hipMemcpy2DAsync(host, row, src->data, src->pitch, row, src->height, hipMemcpyDeviceToHost, ctx->cur().stream));
     return LFG_OK;
 }
 
@@ -710,10 +677,10 @@ LFG_EXPORT int lfg_ring_acquire(lfg_ring *ring, void **out_host_ptr, uint32_t *o
 }
 
 // Transfers run on the ring's own stream so they overlap the kernels:
-//   upload    copy stream waits for what ctx->stream has been given so far (earlier readers of `dst`),
-//             copies, and ctx->stream then waits for the copy -- kernels enqueued next see the pixels;
-//   download  copy stream waits for what ctx->stream has been given so far (the producers of `src`) and copies;
-//             ctx->stream does NOT wait: before a kernel overwrites `src` again, call lfg_ring_fence_slot.
+//   upload    copy stream waits for what the selected lane's stream has been given so far (earlier readers of `dst`),
+//             copies, and that stream then waits for the copy -- kernels enqueued next see the pixels;
+//   download  copy stream waits for what the selected lane's stream has been given so far (the producers of `src`) and copies;
+//             that stream does NOT wait: before a kernel overwrites `src` again, call lfg_ring_fence_slot.
 static int ring_transfer(lfg_ring *ring, uint32_t slot, const lfg_frame *f, bool upload) {
     lfg_context *ctx = ring->ctx;
     if (!f || !f->data) return fail(ctx, LFG_ERR_INVALID, "lfg_ring transfer: NULL frame");
@@ -721,13 +688,13 @@ static int ring_transfer(lfg_ring *ring, uint32_t slot, const lfg_frame *f, bool
     if (ring->slot_bytes < need) return fail(ctx, LFG_ERR_INVALID, "lfg_ring transfer: slot smaller than the frame");
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     uint8_t *host = ring->base + (size_t)slot * ring->slot_bytes;
-    LFG_HIP(ctx, hipEventRecord(ring->ready, ctx->stream));
+    LFG_HIP(ctx, hipEventRecord(ring->ready, ctx->cur().stream));
     LFG_HIP(ctx, hipStreamWaitEvent(ring->copy, ring->ready, 0));
     if (upload) LFG_HIP(ctx, hipMemcpy2DAsync(f->data, f->pitch, host, row, row, f->height, hipMemcpyHostToDevice, ring->copy));
     else LFG_HIP(ctx, hipMemcpy2DAsync(host, row, f->data, f->pitch, row, f->height, hipMemcpyDeviceToHost, ring->copy));
     LFG_HIP(ctx, hipEventRecord(ring->done[slot], ring->copy));
     ring->busy[slot] = 1;
-    if (upload) LFG_HIP(ctx, hipStreamWaitEvent(ctx->stream, ring->done[slot], 0));
+    if (upload) LFG_HIP(ctx, hipStreamWaitEvent(ctx->cur().stream, ring->done[slot], 0));
     return LFG_OK;
 }
 
@@ -749,7 +716,7 @@ LFG_EXPORT int lfg_ring_wait(lfg_ring *ring, uint32_t slot) {
 
 LFG_EXPORT int lfg_ring_fence_slot(lfg_ring *ring, uint32_t slot) {
     if (!ring || slot >= ring->slots) return LFG_ERR_INVALID;
-    if (ring->busy[slot]) LFG_HIP(ring->ctx, hipStreamWaitEvent(ring->ctx->stream, ring->done[slot], 0));
+    if (ring->busy[slot]) LFG_HIP(ring->ctx, hipStreamWaitEvent(ring->ctx->cur().stream, ring->done[slot], 0));
     return LFG_OK;
 }
 
@@ -769,8 +736,8 @@ LFG_EXPORT int lfg_scale(lfg_context *ctx, const lfg_frame *in, lfg_frame *out) 
     if (rc != LFG_OK) return rc;
     const bool fast = tx->pattern_2x && ty->pattern_2x && tx->palette_rows > 0 && ty->strips_per_xcd > 0 && lfg::scale_2x_supported(*in, *out);
     StageTimer timer(ctx, LFG_STAGE_SCALE);
-    hipError_t e = fast ? lfg::launch_scale_2x(ctx->stream, *in, *out, *tx, *ty)
-                        : lfg::launch_scale_generic(ctx->stream, *in, *out, *tx, *ty);
+    hipError_t e = fast ? lfg::launch_scale_2x(ctx->cur().stream, *in, *out, *tx, *ty)
+                        : lfg::launch_scale_generic(ctx->cur().stream, *in, *out, *tx, *ty);
     if (e != hipSuccess) return fail_hip(ctx, e, "scale kernel launch");
     ctx->scale_last_kernel = fast ? 1 : 0;
     return LFG_OK;
@@ -818,64 +785,52 @@ static int motion_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *
     hipError_t e;
     const lfg::FusedOut fo = (fused && tiled) ? *fused : lfg::FusedOut();
     if (tiled && ctx->motion_mode == LFG_MOTION_PREFILTERED) {
-        // The lean kernel (motion_lean.hip) and the plan that goes with it: with frames in flight only (one frame at a time it sits
-        // in front of the rim's long units: 2,620 -> 2,360 frames/s), under either tie order (round 5: the intended order's ranks go
-        // through rank2scan), and for content that suits it -- which the ORDER kernel knows (a pan, an object's motion: most sample blocks
-        // match nearly but not exactly) and the host learns one call late: the verdict of the lane's last finished call decides.
-        // A kernel that finds out on the device that it has nothing to do still has to be placed, 2,144 workgroups of 48 KB of LDS
-        // behind the other lanes' persistent kernels: -7 % on noisy frames, measured.
-        const bool leanPossible = ctx->motion_ws_layout.rimSplit2 != 0 && ctx->motion_hints;
-        // The same word also says whether most sample blocks had a match at all.  With frames in flight the persistent kernel then
-        // runs with 5/8 of the workgroups the device holds: each draws more units, fewer slots idle in a launch's tail, and the other
-        // lanes' kernels find room beside it -- pan 3,660 -> 3,800 frames/s, stills +8 %, noise +3.7 %, occlusions and moving objects
-        // +2 %; frames without a match anywhere (every segment searched in full: the slots are what they need) keep the full grid
-        // (5/8 there: -3.4 %).
-        const bool flagWanted = ctx->lanes.size() >= 2 && ctx->motion_hints;
-        if (flagWanted && !ctx->lean_flag) {
-            LFG_HIP(ctx, hipHostMalloc((void **)&ctx->lean_flag, sizeof(uint32_t), hipHostMallocDefault));
-            *ctx->lean_flag = 0u;
-            LFG_HIP(ctx, hipEventCreateWithFlags(&ctx->lean_ev, hipEventDisableTiming));
+        // The lean kernel, the persistent grid, its variant and the second pass's grid are decided by the verdict of the lane's last
+        // finished call (lfg_motion_verdict.hpp: motion_call_policy); here only what it takes from HIP.  The lean kernel's plan exists
+        // with frames in flight only (one frame at a time it sits in front of the rim's long units: 2,620 -> 2,360 frames/s), and
+        // serves either tie order (round 5: the intended order's ranks go through rank2scan).
+        lfg_lane_state &cur = ctx->cur();
+        lfg::MotionVerdictState &v = cur.verdict;
+        if (lfg::motion_verdict_wanted((int)ctx->lanes.size(), ctx->motion_hints) && !v.pinned) {
+            LFG_HIP(ctx, hipHostMalloc((void **)&v.pinned, sizeof(uint32_t), hipHostMallocDefault));
+            *v.pinned = 0u;
+            LFG_HIP(ctx, hipEventCreateWithFlags(&v.event, hipEventDisableTiming));
         }
-        if (ctx->lean_ev_pending && hipEventQuery(ctx->lean_ev) == hipSuccess) {
-            ctx->lean_predict = (int)*ctx->lean_flag; ctx->lean_ev_pending = false; ctx->lean_seen = true;
-            // (lfg_motion_prediction_stats) the call that delivered this word had been launched on lean_request_guess -- bit 0: it went
-            // through the lean kernel, bit 1: that kernel was available to it, bit 31: its persistent grid was sized for "most sample
-            // blocks match", bit 30: its second pass was the small looping grid -- and its own content said:
-            const uint32_t said = (uint32_t)ctx->lean_predict, guess = ctx->lean_request_guess;
+        if (v.pending && hipEventQuery(v.event) == hipSuccess) {
+            v.word = *v.pinned; v.pending = false; v.seen = true;
+            const lfg::MotionVerdictScore score = lfg::motion_verdict_score(v.launchedOn, v.word);      // (lfg_motion_prediction_stats)
             ctx->pred_verdicts += 1;
-            if ((guess & 2u) && ((guess ^ said) & 1u)) ctx->pred_lean_wrong += 1;
-            if (((guess ^ said) >> 31) || (((guess ^ said) >> 29) & 1u)) ctx->pred_grid_wrong += 1;      // (the persistent launch: its grid, or its variant)
-            if (((guess >> 30) & 1u) && ((said >> 30) & 1u)) ctx->pred_second_wrong += 1;       // (small grid, and tiles were flagged: the costly direction)
+            ctx->pred_lean_wrong += score.leanWrong;
+            ctx->pred_grid_wrong += score.gridWrong;
+            ctx->pred_second_wrong += score.secondWrong;
         }
-        if (ctx->knobs.leanForce >= 0) ctx->lean_predict = (ctx->lean_predict & ~1) | ctx->knobs.leanForce;          // (measurement: 1 = every call, 0 = none)
-        ctx->motion_ws_layout.lastLean = (leanPossible && ctx->motion_ws_layout.leanCount > 0 && (ctx->lean_predict & 1) != 0 && !fo.data && lfg::lean_frames_ok(*prev, *curr, *mv)) ? 1 : 0;
-        // (only while another lane has work queued or running -- a stream query each: a call that has the device to itself takes the
-        //  full grid, and is as long as on a context without lanes)
-        bool othersBusy = false;
-        for (size_t j = 0; j < ctx->lanes.size() && !othersBusy; ++j)
-            if ((int)j != ctx->lane && ctx->lanes[j].stream && hipStreamQuery(ctx->lanes[j].stream) == hipErrorNotReady) othersBusy = true;
-        int groupsCap = (flagWanted && othersBusy && ((uint32_t)ctx->lean_predict >> 31) != 0u) ? std::max(1, ctx->motion_slots * 5 / 8) : 0;
-        // ... and bit 30 whether that call sent a tile through the literal kernel (flat content under a fade, exact ties): if not, this
-        // call's fallback launch is 64 workgroups instead of 2,048 -- they take whatever it flags after all, in turns (1.4 % of the
-        // frame rate under a pan: workgroups of 42 KB of LDS that read a count and leave still have to be placed)
-        if (ctx->comm_cus > 0) groupsCap = groupsCap ? std::min(groupsCap, persistent_grid_most(ctx)) : persistent_grid_most(ctx);
-        // ... and bit 29 which variant of the persistent kernel: the one with the eight-point walk by SADs where half the sample blocks matched
-        // moderately well (sensor noise of +-3 .. +-6 levels at the input; motion_prefilter.hip, kTier)
-        const int tier = ctx->knobs.tierForce >= 0 ? ctx->knobs.tierForce : (flagWanted && ctx->lean_seen && (((uint32_t)ctx->lean_predict >> 29) & 1u)) ? 1 : 0;
-        ctx->motion_last_tier = fo.data ? 0 : tier;
-        const bool expectNoFallback = flagWanted && ctx->lean_seen && (((uint32_t)ctx->lean_predict >> 30) & 1u) == 0u && !ctx->knobs.fallbackFull /* (measurement) */;
-        e = lfg::launch_motion_prefiltered_8_16(ctx->stream, *prev, *curr, *mv, ctx->motion_ws, ctx->motion_ws_layout, ctx->motion_units,
+        lfg::MotionCallInputs in;
+        in.lanes = (int)ctx->lanes.size();
+        in.hints = ctx->motion_hints;
+        in.leanPlan = cur.motion_ws_layout.rimSplit2 != 0 && cur.motion_ws_layout.leanCount > 0;
+        in.fused = fo.data != nullptr;
+        in.leanFramesOk = lfg::lean_frames_ok(*prev, *curr, *mv);
+        // (only while another lane has work queued or running -- a stream query each)
+        for (size_t j = 0; j < ctx->lanes.size() && !in.othersBusy; ++j)
+            if ((int)j != ctx->lane && ctx->lanes[j].stream && hipStreamQuery(ctx->lanes[j].stream) == hipErrorNotReady) in.othersBusy = true;
+        in.slots = ctx->motion_slots;
+        in.deviceCus = ctx->device_cus;
+        in.commCus = ctx->comm_cus;
+        const lfg::MotionCall call = lfg::motion_call_policy(v, in, ctx->knobs);
+        cur.motion_ws_layout.lastLean = call.lean ? 1 : 0;
+        ctx->motion_last_tier = fo.data ? 0 : call.tier;
+        e = lfg::launch_motion_prefiltered_8_16(cur.stream, *prev, *curr, *mv, cur.motion_ws, cur.motion_ws_layout, cur.motion_units,
                                                 rank2scan, order32, order32 + lfg::kMotionTableWords,
                                                 ctx->motion_tables + 6 * lfg::kMotionTableWords, ctx->motion_hints, ctx->lanes.size() >= 2, fo,
-                                                ctx->motion_ws_layout.lastLean != 0, (flagWanted && !ctx->lean_ev_pending) ? ctx->lean_flag : nullptr, groupsCap, expectNoFallback, ctx->knobs, ctx->semantics == 0, tier);
-        if (e == hipSuccess && flagWanted && !ctx->lean_ev_pending && !fo.data) {
-            e = hipEventRecord(ctx->lean_ev, ctx->stream); ctx->lean_ev_pending = true;
-            ctx->lean_request_guess = (ctx->motion_ws_layout.lastLean ? 1u : 0u) | ((leanPossible && ctx->motion_ws_layout.leanCount > 0) ? 2u : 0u) |
-                                      ((uint32_t)ctx->lean_predict & 0x80000000u) | (expectNoFallback ? 1u << 30 : 0u) | (tier ? 1u << 29 : 0u);
+                                                call.lean, call.deliverWord ? v.pinned : nullptr, call.groupsCap, call.expectNoFallback, ctx->knobs,
+                                                ctx->semantics == 0, call.tier);
+        if (e == hipSuccess && call.awaitVerdict) {
+            e = hipEventRecord(v.event, cur.stream); v.pending = true;
+            v.launchedOn = call.launchedOn;
         }
     }
-    else if (tiled) e = lfg::launch_motion_tiled_8_16(ctx->stream, *prev, *curr, *mv, nullptr, rank2scan, nullptr, nullptr, fo);
-    else e = lfg::launch_motion_generic(ctx->stream, *prev, *curr, *mv, block_size, R, ctx->semantics != 0);
+    else if (tiled) e = lfg::launch_motion_tiled_8_16(ctx->cur().stream, *prev, *curr, *mv, nullptr, rank2scan, nullptr, nullptr, fo);
+    else e = lfg::launch_motion_generic(ctx->cur().stream, *prev, *curr, *mv, block_size, R, ctx->semantics != 0);
     if (e != hipSuccess) return fail_hip(ctx, e, "motion kernel launch");
     if (fusedDone) *fusedDone = fo.data != nullptr;
     return LFG_OK;
@@ -914,7 +869,7 @@ LFG_EXPORT int lfg_motion_workspace_size(lfg_context *ctx, uint32_t width, uint3
 LFG_EXPORT int lfg_motion_plan(const lfg_context *ctx, int *out_rim_split, int *out_workgroups) {
     if (!ctx) return LFG_ERR_INVALID;
     if (out_rim_split) *out_rim_split = motion_rim_split(ctx);
-    if (out_workgroups) *out_workgroups = persistent_grid_most(ctx);
+    if (out_workgroups) *out_workgroups = lfg::persistent_grid_most(ctx->motion_slots, ctx->device_cus, ctx->comm_cus);
     return LFG_OK;
 }
 
@@ -922,12 +877,13 @@ LFG_EXPORT int lfg_motion_plan(const lfg_context *ctx, int *out_rim_split, int *
 // frame has (64 x 64 tiles x 4).  A segment is listed once; tests hold the list to that.
 LFG_EXPORT int lfg_motion_open_segments(lfg_context *ctx, uint32_t *out_open, uint32_t *out_segments) {
     if (!ctx) return LFG_ERR_INVALID;
+    lfg_lane_state &cur = ctx->cur();
     if (!out_open || !out_segments) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_open_segments: NULL argument");
-    if (!ctx->motion_ws || ctx->motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_open_segments: the prefiltered path has not run");
-    LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t tx = (ctx->motion_ws_w + 55u) / 56u, ty = (ctx->motion_ws_h + 63u) / 64u;      // (prefilter tiles: 56 x 64 pixels)
+    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_open_segments: the prefiltered path has not run");
+    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
+    const uint32_t tx = (cur.motion_ws_w + 55u) / 56u, ty = (cur.motion_ws_h + 63u) / 64u;      // (prefilter tiles: 56 x 64 pixels)
     uint32_t open = 0;
-    LFG_HIP(ctx, hipMemcpy(&open, ctx->motion_ws + ctx->motion_ws_layout.ctrl + lfg::kCtrlOpenCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(&open, cur.motion_ws + cur.motion_ws_layout.ctrl + lfg::kCtrlOpenCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_open = open;
     *out_segments = tx * ty * 4u;
     return LFG_OK;
@@ -937,27 +893,29 @@ LFG_EXPORT int lfg_motion_open_segments(lfg_context *ctx, uint32_t *out_open, ui
 // interior tiles are listed for it at this frame size, and in how many of them it left a segment to the persistent kernel.
 LFG_EXPORT int lfg_motion_lean_stats(lfg_context *ctx, int *out_used, uint32_t *out_tiles, uint32_t *out_tiles_left) {
     if (!ctx) return LFG_ERR_INVALID;
+    lfg_lane_state &cur = ctx->cur();
     if (!out_used || !out_tiles || !out_tiles_left) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_lean_stats: NULL argument");
-    if (!ctx->motion_ws || ctx->motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_lean_stats: the prefiltered path has not run");
-    LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_lean_stats: the prefiltered path has not run");
+    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     uint32_t left = 0;
-    LFG_HIP(ctx, hipMemcpy(&left, ctx->motion_ws + ctx->motion_ws_layout.ctrl + lfg::kCtrlHardCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
-    *out_used = ctx->motion_ws_layout.lastLean;
-    *out_tiles = (uint32_t)ctx->motion_ws_layout.leanCount;
-    *out_tiles_left = ctx->motion_ws_layout.lastLean ? left : 0u;
+    LFG_HIP(ctx, hipMemcpy(&left, cur.motion_ws + cur.motion_ws_layout.ctrl + lfg::kCtrlHardCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *out_used = cur.motion_ws_layout.lastLean;
+    *out_tiles = (uint32_t)cur.motion_ws_layout.leanCount;
+    *out_tiles_left = cur.motion_ws_layout.lastLean ? left : 0u;
     return LFG_OK;
 }
 
 LFG_EXPORT int lfg_motion_strip_stats(lfg_context *ctx, uint32_t *out_rows, uint32_t *out_columns) {
     if (!ctx) return LFG_ERR_INVALID;
+    lfg_lane_state &cur = ctx->cur();
     if (!out_rows || !out_columns) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_strip_stats: NULL argument");
-    if (!ctx->motion_ws || ctx->motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_strip_stats: the prefiltered path has not run");
-    LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> t((size_t)ctx->motion_ws_h + ctx->motion_ws_w);
-    LFG_HIP(ctx, hipMemcpy(t.data(), ctx->motion_ws + ctx->motion_ws_layout.colBand, t.size() * 4, hipMemcpyDeviceToHost));
+    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_strip_stats: the prefiltered path has not run");
+    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
+    std::vector<uint32_t> t((size_t)cur.motion_ws_h + cur.motion_ws_w);
+    LFG_HIP(ctx, hipMemcpy(t.data(), cur.motion_ws + cur.motion_ws_layout.colBand, t.size() * 4, hipMemcpyDeviceToHost));
     uint32_t rows = 0, cols = 0;
-    for (uint32_t y = 0; y < ctx->motion_ws_h; ++y) rows += t[y] != 0u;
-    for (uint32_t x = 0; x < ctx->motion_ws_w; ++x) cols += t[ctx->motion_ws_h + x] != 0u;
+    for (uint32_t y = 0; y < cur.motion_ws_h; ++y) rows += t[y] != 0u;
+    for (uint32_t x = 0; x < cur.motion_ws_w; ++x) cols += t[cur.motion_ws_h + x] != 0u;
     *out_rows = rows; *out_columns = cols;
     return LFG_OK;
 }
@@ -975,31 +933,32 @@ LFG_EXPORT int lfg_motion_prediction_stats(const lfg_context *ctx, uint64_t *out
 LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint32_t *out_fallback_tiles,
                                      double *out_mean_recorded) {
     if (!ctx) return LFG_ERR_INVALID;
-    if (!ctx->motion_ws || ctx->motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_last_stats: the prefiltered path has not run");
-    LFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t tx = (ctx->motion_ws_w + 63u) / 64u, ty = (ctx->motion_ws_h + 63u) / 64u;
+    lfg_lane_state &cur = ctx->cur();
+    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_last_stats: the prefiltered path has not run");
+    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
+    const uint32_t tx = (cur.motion_ws_w + 63u) / 64u, ty = (cur.motion_ws_h + 63u) / 64u;
     std::vector<uint32_t> flags((size_t)tx * ty);
-    LFG_HIP(ctx, hipMemcpy(flags.data(), ctx->motion_ws + ctx->motion_ws_layout.tileFlags, flags.size() * 4, hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(flags.data(), cur.motion_ws + cur.motion_ws_layout.tileFlags, flags.size() * 4, hipMemcpyDeviceToHost));
     uint32_t fb = 0;
     for (uint32_t f : flags) fb += f != 0u;
     if (ctx->knobs.debug) {
         uint32_t handed[2] = {0, 0};
-        LFG_HIP(ctx, hipMemcpy(handed, ctx->motion_ws + ctx->motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(handed, cur.motion_ws + cur.motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
         fprintf(stderr, "lfg: motion prefilter: %u requests to hand a segment over (room for %d), %u tiles flagged for the exact kernel\n",
-                handed[0], ctx->motion_ws_layout.queueCap, handed[1]);
+                handed[0], cur.motion_ws_layout.queueCap, handed[1]);
         uint32_t lean[2] = {0, 0};
-        LFG_HIP(ctx, hipMemcpy(lean, ctx->motion_ws + ctx->motion_ws_layout.ctrl + lfg::kCtrlLeanSettled * sizeof(uint32_t), 8, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(lean, cur.motion_ws + cur.motion_ws_layout.ctrl + lfg::kCtrlLeanSettled * sizeof(uint32_t), 8, hipMemcpyDeviceToHost));
         uint32_t flags[3] = {0, 0, 0};
-        LFG_HIP(ctx, hipMemcpy(flags, ctx->motion_ws + ctx->motion_ws_layout.orderFlags, 12, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(flags, cur.motion_ws + cur.motion_ws_layout.orderFlags, 12, hipMemcpyDeviceToHost));
         fprintf(stderr, "lfg: lean kernel: %d tiles listed, %u segments settled, %u left to the generic kernel (counted in -DLFG_LEAN_STATS builds); order flags: hand-over %u, hints %u, lean %u (sample blocks with a close match %u, with an exact one %u)\n",
-                ctx->motion_ws_layout.leanCount, lean[0], lean[1], flags[0], flags[1], flags[2] & 1u, (flags[2] >> 1) & 0x7FFu, (flags[2] >> 12) & 0x7FFu);
+                cur.motion_ws_layout.leanCount, lean[0], lean[1], flags[0], flags[1], lfg::verdict_lean(flags[2]) ? 1u : 0u, lfg::verdict_close(flags[2]), lfg::verdict_exact(flags[2]));
     }
     if (ctx->knobs.debugDyn) {       // the deepest private lists of the handed-over segments: block (4 x queue slot + wave), pixel, records
         uint32_t handed[2] = {0, 0};
-        LFG_HIP(ctx, hipMemcpy(handed, ctx->motion_ws + ctx->motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
-        const size_t blocks = (size_t)std::min<uint32_t>(handed[0], (uint32_t)ctx->motion_ws_layout.queueCap) * 4u, per = 16u * 56u;
+        LFG_HIP(ctx, hipMemcpy(handed, cur.motion_ws + cur.motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
+        const size_t blocks = (size_t)std::min<uint32_t>(handed[0], (uint32_t)cur.motion_ws_layout.queueCap) * 4u, per = 16u * 56u;
         std::vector<uint32_t> dc(blocks * per);
-        if (!dc.empty()) LFG_HIP(ctx, hipMemcpy(dc.data(), ctx->motion_ws + ctx->motion_ws_layout.dynCount, dc.size() * 4, hipMemcpyDeviceToHost));
+        if (!dc.empty()) LFG_HIP(ctx, hipMemcpy(dc.data(), cur.motion_ws + cur.motion_ws_layout.dynCount, dc.size() * 4, hipMemcpyDeviceToHost));
         size_t hist[40] = {0};
         int dumped = 0;
         const uint32_t deep = (uint32_t)ctx->knobs.debugDynDeep;
@@ -1009,11 +968,11 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
                 fprintf(stderr, "lfg: dyn list block %zu (part %zu of its segment) pixel %zu (row %zu, column %zu): %u records\n", i / per, (i / per) % 8u, i % per, (i % per) / 56u, (i % per) % 56u, dc[i]);
                 if (dumped++ < 6) {      // the records themselves: lower bound of the cost and the candidate's rank, in the order they were recorded
                     const size_t blk = i / per, row = (i % per) / 56u, col = (i % per) % 56u;
-                    const int K = ctx->motion_ws_layout.listDyn;
+                    const int K = cur.motion_ws_layout.listDyn;
                     for (int k = 0; k < std::min<int>((int)dc[i], K); ++k) {
                         uint32_t rec = 0; float thr = 0.f;
-                        (void)hipMemcpy(&rec, ctx->motion_ws + ctx->motion_ws_layout.dynList + (((blk * 16u + row) * (size_t)K + (size_t)k) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
-                        (void)hipMemcpy(&thr, ctx->motion_ws + ctx->motion_ws_layout.dynUmin + ((blk * 16u + row) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
+                        (void)hipMemcpy(&rec, cur.motion_ws + cur.motion_ws_layout.dynList + (((blk * 16u + row) * (size_t)K + (size_t)k) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
+                        (void)hipMemcpy(&thr, cur.motion_ws + cur.motion_ws_layout.dynUmin + ((blk * 16u + row) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
                         const uint32_t bits = (rec >> 11) << 10; float c; memcpy(&c, &bits, 4);
                         fprintf(stderr, "      record %2d: cost >= %.3f rank %4u (dx %+d, dy %+d)%s\n", k, c, rec & 0x7FFu, (int)((rec & 0x7FFu) % 33u) - 16, (int)((rec & 0x7FFu) / 33u) - 16, k == 0 ? "" : "");
                         if (k + 1 == std::min<int>((int)dc[i], K)) fprintf(stderr, "      final threshold %.3f\n", thr);
@@ -1022,9 +981,9 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
             }
         }
         {   // which segments under the flagged tiles were handed over
-            const uint32_t ptx = (ctx->motion_ws_w + 55u) / 56u, pty = (ctx->motion_ws_h + 63u) / 64u;
+            const uint32_t ptx = (cur.motion_ws_w + 55u) / 56u, pty = (cur.motion_ws_h + 63u) / 64u;
             std::vector<uint32_t> sm((size_t)ptx * pty * 4u);
-            LFG_HIP(ctx, hipMemcpy(sm.data(), ctx->motion_ws + ctx->motion_ws_layout.segMap, sm.size() * 4, hipMemcpyDeviceToHost));
+            LFG_HIP(ctx, hipMemcpy(sm.data(), cur.motion_ws + cur.motion_ws_layout.segMap, sm.size() * 4, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < flags.size(); ++i) if (flags[i]) {
                 const uint32_t fx = (uint32_t)(i % tx), fy = (uint32_t)(i / tx);
                 for (uint32_t px = fx * 64u / 56u; px <= std::min(ptx - 1u, (fx * 64u + 63u) / 56u); ++px)
@@ -1054,22 +1013,22 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
     if (out_tiles) *out_tiles = tx * ty;
     if (out_fallback_tiles) *out_fallback_tiles = fb;
     if (out_mean_recorded) {
-        const size_t px = (size_t)ctx->motion_ws_w * ctx->motion_ws_h;
+        const size_t px = (size_t)cur.motion_ws_w * cur.motion_ws_h;
         std::vector<uint32_t> cnt(px);
-        LFG_HIP(ctx, hipMemcpy(cnt.data(), ctx->motion_ws + ctx->motion_ws_layout.count, px * 4, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(cnt.data(), cur.motion_ws + cur.motion_ws_layout.count, px * 4, hipMemcpyDeviceToHost));
         // (tiles whose candidates were shared between several workgroups keep their counts elsewhere: left out)
-        const lfg::PrefilterPlanHost plan = lfg::prefilter_plan(ctx->motion_ws_w, ctx->motion_ws_h, ctx->motion_slots,
-                                                                ctx->motion_ws_layout.lastLean ? ctx->motion_ws_layout.rimSplit2 : ctx->motion_ws_layout.rimSplit);
+        const lfg::PrefilterPlanHost plan = lfg::prefilter_plan(cur.motion_ws_w, cur.motion_ws_h, ctx->motion_slots,
+                                                                cur.motion_ws_layout.lastLean ? cur.motion_ws_layout.rimSplit2 : cur.motion_ws_layout.rimSplit);
         // (a segment that settled all of its pixels in the prefilter wrote no counts: its pixels hold at most two records,
         //  counted as none here)
         std::vector<uint32_t> segDone((size_t)plan.tiles * 4u);
-        LFG_HIP(ctx, hipMemcpy(segDone.data(), ctx->motion_ws + ctx->motion_ws_layout.segDone, segDone.size() * 4, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(segDone.data(), cur.motion_ws + cur.motion_ws_layout.segDone, segDone.size() * 4, hipMemcpyDeviceToHost));
         double sum = 0; size_t n = 0;
-        for (uint32_t y = 0; y < ctx->motion_ws_h; ++y)
-            for (uint32_t x = 0; x < ctx->motion_ws_w; ++x) {
+        for (uint32_t y = 0; y < cur.motion_ws_h; ++y)
+            for (uint32_t x = 0; x < cur.motion_ws_w; ++x) {
                 const size_t ptile = (size_t)(y / 64u) * (size_t)plan.tilesX + x / 56u;
                 if (!flags[(size_t)(y / 64u) * tx + x / 64u] && plan.tileMap[ptile] == 0xFFFFFFFFu) {
-                    sum += segDone[ptile * 4u + (y % 64u) / 16u] ? 0.0 : (double)cnt[(size_t)y * ctx->motion_ws_w + x]; ++n;
+                    sum += segDone[ptile * 4u + (y % 64u) / 16u] ? 0.0 : (double)cnt[(size_t)y * cur.motion_ws_w + x]; ++n;
                 }
             }
         *out_mean_recorded = n ? sum / (double)n : 0.0;
@@ -1094,7 +1053,7 @@ LFG_EXPORT int lfg_interpolate(lfg_context *ctx, const lfg_frame *prev, const lf
     int rc = interp_tables(ctx, (int)curr->width, (int)curr->height, &tb);
     if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
-    hipError_t e = lfg::launch_interpolate(ctx->stream, *prev, *curr, *mv, *out, factor, ctx->semantics != 0, tb);
+    hipError_t e = lfg::launch_interpolate(ctx->cur().stream, *prev, *curr, *mv, *out, factor, ctx->semantics != 0, tb);
     if (e != hipSuccess) return fail_hip(ctx, e, "interpolate kernel launch");
     return LFG_OK;
 }
@@ -1102,7 +1061,7 @@ LFG_EXPORT int lfg_interpolate(lfg_context *ctx, const lfg_frame *prev, const lf
 LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                       lfg_frame *out, float factor) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: NULL argument");
-    lfg_frame &mv = ctx->mv_tmp;
+    lfg_frame &mv = ctx->cur().mv_tmp;
     if (!mv.data || mv.width != curr->width || mv.height != curr->height) {   // frame_manager.cpp:226-230
         lfg_frame_destroy(ctx, &mv);
         int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
@@ -1153,7 +1112,7 @@ LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, co
     int rc = interp_tables(ctx, (int)curr->width, (int)curr->height, &tb);
     if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
-    hipError_t e = lfg::launch_interpolate_multi(ctx->stream, *prev, *curr, *mv, outs, factors, (int)count, ctx->semantics != 0, tb);
+    hipError_t e = lfg::launch_interpolate_multi(ctx->cur().stream, *prev, *curr, *mv, outs, factors, (int)count, ctx->semantics != 0, tb);
     if (e != hipSuccess) return fail_hip(ctx, e, "interpolate kernel launch");
     return LFG_OK;
 }
@@ -1161,7 +1120,7 @@ LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, co
 LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                             lfg_frame *const *outs, const float *factors, uint32_t count) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames_multi: NULL argument");
-    lfg_frame &mv = ctx->mv_tmp;
+    lfg_frame &mv = ctx->cur().mv_tmp;
     if (!mv.data || mv.width != curr->width || mv.height != curr->height) {   // frame_manager.cpp:226-230
         lfg_frame_destroy(ctx, &mv);
         int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
@@ -1209,13 +1168,13 @@ LFG_EXPORT int lfg_interpolate_scale(lfg_context *ctx, const lfg_frame *prev, co
         // one kernel: the generated frame is interpolated row by row inside the 2x scale kernel and never stored at
         // input resolution; accounted to the scale stage
         StageTimer timer(ctx, LFG_STAGE_SCALE);
-        hipError_t e = lfg::launch_interpolate_scale_2x(ctx->stream, *prev, *curr, *mv, *out, *tx, *ty, factor, ctx->semantics != 0);
+        hipError_t e = lfg::launch_interpolate_scale_2x(ctx->cur().stream, *prev, *curr, *mv, *out, *tx, *ty, factor, ctx->semantics != 0);
         if (e != hipSuccess) return fail_hip(ctx, e, "fused interpolate + scale kernel launch");
         ctx->scale_last_kernel = 2;
         return LFG_OK;
     }
     // any other size ratio: the two stages, through a context-owned frame at input resolution
-    lfg_frame &mid = ctx->mid_tmp;
+    lfg_frame &mid = ctx->cur().mid_tmp;
     if (!mid.data || mid.width != curr->width || mid.height != curr->height) {
         lfg_frame_destroy(ctx, &mid);
         rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_RGBA8_UNORM, &mid);
@@ -1229,7 +1188,7 @@ LFG_EXPORT int lfg_interpolate_scale(lfg_context *ctx, const lfg_frame *prev, co
 LFG_EXPORT int lfg_mv_export_rgba32f(lfg_context *ctx, const lfg_frame *mv, void *device_rgba32f) {
     if (!ctx || !frame_ok(mv, LFG_FORMAT_MV_S8X2) || !device_rgba32f || (uintptr_t)device_rgba32f % 16u)
         return fail(ctx, LFG_ERR_INVALID, "lfg_mv_export_rgba32f: bad argument");
-    hipError_t e = lfg::launch_mv_export(ctx->stream, *mv, (float *)device_rgba32f);
+    hipError_t e = lfg::launch_mv_export(ctx->cur().stream, *mv, (float *)device_rgba32f);
     if (e != hipSuccess) return fail_hip(ctx, e, "mv export kernel launch");
     return LFG_OK;
 }
@@ -1240,11 +1199,11 @@ LFG_EXPORT int lfg_selftest_sqrt(lfg_context *ctx, uint32_t lo_bits, uint32_t hi
     if (!ctx || !out_mismatches || lo_bits > hi_bits) return fail(ctx, LFG_ERR_INVALID, "lfg_selftest_sqrt: bad argument");
     unsigned long long *d = nullptr;
     LFG_HIP(ctx, hipMalloc((void **)&d, sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess) e = lfg::launch_sqrt_selftest(ctx->stream, lo_bits, hi_bits, d);
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->cur().stream);
+    if (e == hipSuccess) e = lfg::launch_sqrt_selftest(ctx->cur().stream, lo_bits, hi_bits, d);
     unsigned long long h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, ctx->cur().stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->cur().stream);
     (void)hipFree(d);
     if (e != hipSuccess) return fail_hip(ctx, e, "sqrt selftest");
     *out_mismatches = (uint64_t)h;

@@ -152,16 +152,15 @@ namespace {
 // that precedes it).
 // (everyLane false: the selected lane only -- lfg_broadcast_frame_lane, whose caller has ordered that lane behind the frame's readers.)
 hipError_t behind_lanes(lfg_context *ctx, bool everyLane) {
+#ifdef LFG_DIAG_COMM_SELECTED_LANE_ONLY   // (diagnostic build: round 2's ordering, to see tests/test_gpu_comm.py's ordering test fail)
+    everyLane = false;
+#endif
     hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipEventRecord(ctx->comm_ready, ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->comm_stream, ctx->comm_ready, 0);
-#ifndef LFG_DIAG_COMM_SELECTED_LANE_ONLY   // (diagnostic build: round 2's ordering, to see tests/test_gpu_comm.py's ordering test fail)
-    for (size_t j = 0; everyLane && j < ctx->lanes.size() && e == hipSuccess; ++j) {
-        if ((int)j == ctx->lane || !ctx->lanes[j].stream) continue;       // (the selected lane's stream is ctx->stream, above)
-        e = hipEventRecord(ctx->comm_ready, ctx->lanes[j].stream);
+    const size_t lanes = everyLane ? ctx->lanes.size() : 1;         // (the selected lane first)
+    for (size_t k = 0; k < lanes && e == hipSuccess; ++k) {
+        e = hipEventRecord(ctx->comm_ready, ctx->from_selected(k).stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->comm_stream, ctx->comm_ready, 0);
     }
-#endif
     return e;
 }
 }  // namespace
@@ -197,7 +196,7 @@ LFG_EXPORT int lfg_comm_wait(lfg_context *ctx) {
     if (!ctx->comm) return fail(ctx, LFG_ERR_INVALID, "lfg_comm_wait: no communicator (lfg_comm_init)");
     if (ctx->comm_pending) {               // (never cleared: another lane may still have to wait for the same broadcast,
                                            //  and waiting for an event that has fired costs nothing on the device)
-        const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->comm_done, 0);
+        const hipError_t e = hipStreamWaitEvent(ctx->cur().stream, ctx->comm_done, 0);
         if (e != hipSuccess) return fail(ctx, LFG_ERR_DEVICE, std::string("lfg_comm_wait: ") + hipGetErrorString(e));
     }
     return LFG_OK;

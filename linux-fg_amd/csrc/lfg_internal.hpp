@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "linuxfg_hip.h"
+#include "lfg_motion_verdict.hpp"
 
 namespace lfg {
 
@@ -89,24 +90,6 @@ enum MotionCtrlWord : int {
     kCtrlLeanLeft = 7,
 };
 
-// Measurement knobs, read ONCE from the environment when a context is created (lfg_context_create) and never again: a call's
-// launch geometry cannot change between two lfg_motion calls because somebody called setenv.  All of them are for A/B runs of
-// tools/; none changes a result.
-struct MotionKnobs {
-    int leanForce = -1;       // LFG_LEAN_FORCE = 1: every call through the lean kernel whatever the verdict, 0: none, unset: by the verdict
-    int fallbackFull = 0;     // LFG_FALLBACK_FULL: the second pass always on its full grid
-    int dynParts = 0;         // LFG_DYN_PARTS_RT = 4 | 8: parts of a handed-over segment, whatever the lane count
-    int prefGroups = 0;       // LFG_PREF_GROUPS: workgroups of the persistent kernel
-    int resolveGroups = 0;    // LFG_RESOLVE_GROUPS: workgroups of the resolve kernel
-    int strips = 0;           // LFG_MOTION_STRIP = 1: the exposed strips through a kernel of their own (motion_strip.hip: exact, measured slower)
-    int stripPad = -1;        // LFG_STRIP_PAD: bytes of dynamic LDS a strip workgroup asks for on top of its own (-1: the launcher's choice)
-    int debug = 0;            // LFG_DEBUG: reporting calls print what they read
-    int debugDyn = 0;         // LFG_DEBUG_DYN: lfg_motion_last_stats prints the deepest private lists of the handed-over segments,
-    int debugDynDeep = 14;    // LFG_DEBUG_DYN_DEEP: ... deeper than this
-    int tierForce = -1;       // LFG_TIER_FORCE = 0 | 1: the persistent kernel's variant whatever the verdict (-1: by the verdict)
-    int commCus = 8;          // LFG_COMM_CUS = 0 | 8 | 16 | 24 | 32: CUs a communicator keeps free of the library's own kernels (lfg_comm.cpp)
-};
-
 struct MotionWorkspaceLayout { size_t colBand, rowBand /* [height], [width] words of the strip kernel (motion_strip.hip), inside the control area the hint kernel clears */; size_t verdict /* byte offset of the call's verdict word, order32[kCand + 2] of its own order table; orderFlags: of [kCand] */, orderFlags; size_t list, umin, count, tileFlags, segDone, segMap, queueCount, ctrl, order, plan, auxList, auxUmin, auxCount,
                                queue, dynList, dynUmin, dynCount, dynInit, openList, merge, mergeBytes, leanTiles, hardTiles, plan2, total; int queueCap, slots, rimSplit, listMain, listAux, listDyn, leanCount, leanLaunch /* with the partial tiles behind them */, rimSplit2, units, units2, units2Static /* the second plan's units without the lean kernel's tiles, which come last in its table */, tiles, lastLean /* the lane's last call went by the second plan */; };
 // Work units of the motion prefilter (motion_plan.hip: prefilter_plan).  A unit is a 56 x 64 tile, or one of nChunks
@@ -157,46 +140,9 @@ struct ProfileSlot {
 }  // namespace lfg
 
 // What a lane (lfg_lanes: one of several frames in flight on a GPU) owns apart from the context: its stream, the temporaries
-// and the motion workspace of its calls, and the event other lanes wait for.  The context's own fields ARE the selected
-// lane's; lfg_lane_select swaps them with the entry of this table.
+// and the motion workspace of its calls, the event other lanes wait for, and the verdicts its motion calls are launched by.
 struct lfg_lane_state {
     hipStream_t own_stream = nullptr, stream = nullptr;
-    lfg_frame mv_tmp{}, mid_tmp{};
-    uint8_t *motion_ws = nullptr;
-    size_t motion_ws_bytes = 0;
-    uint32_t motion_ws_w = 0, motion_ws_h = 0;
-    lfg::MotionWorkspaceLayout motion_ws_layout{};
-    int motion_units = 0;
-    hipEvent_t mark = nullptr;
-    bool marked = false;
-    uint32_t *lean_flag = nullptr;             // pinned: the order kernel's verdict on the lane's last call ("content for the lean kernel")
-    hipEvent_t lean_ev = nullptr;              // ... recorded behind its copy
-    bool lean_ev_pending = false;
-    int lean_predict = 0;                      // the verdict word the next call goes by (bit 0: lean kernel; bit 30: a tile went through the literal kernel; bit 31: most sample blocks have a match)
-    bool lean_seen = false;                    // ... and whether any call's word has arrived yet
-    uint32_t lean_request_guess = 0;           // what the call that carries the pending verdict request was launched on (motion_run)
-};
-
-struct lfg_context {
-    int device = 0;
-    int device_cus = 0;                        // its compute units
-    std::vector<lfg_lane_state> lanes;         // empty until lfg_lanes(); entry `lane` is stale while that lane is selected
-    int lane = 0;
-    hipEvent_t mark = nullptr;                 // the selected lane's (see lfg_lane_state)
-    bool marked = false;
-    uint32_t *lean_flag = nullptr;             // likewise
-    hipEvent_t lean_ev = nullptr;
-    bool lean_ev_pending = false;
-    int lean_predict = 0;
-    bool lean_seen = false;
-    uint32_t lean_request_guess = 0;
-    // lfg_motion_prediction_stats: calls whose verdict came back, and the guesses it contradicted (all lanes together)
-    uint64_t pred_verdicts = 0, pred_lean_wrong = 0, pred_grid_wrong = 0, pred_second_wrong = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    std::string error;
-    std::vector<lfg::AxisTable> tables;       // small cache, linear search
-    std::vector<lfg::UvTable> uv_tables;      // likewise (interpolate)
     lfg_frame mv_tmp{};                        // temporary of lfg_interpolate_frames
     lfg_frame mid_tmp{};                       // temporary of lfg_interpolate_scale where the fused kernel does not apply
     // prefiltered motion path: scratch for one frame size, grown on demand
@@ -205,6 +151,25 @@ struct lfg_context {
     uint32_t motion_ws_w = 0, motion_ws_h = 0;
     lfg::MotionWorkspaceLayout motion_ws_layout{};
     int motion_units = 0;                      // work units of the prefilter for the current workspace size
+    hipEvent_t mark = nullptr;                 // lfg_lane_mark
+    bool marked = false;
+    lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
+};
+
+struct lfg_context {
+    int device = 0;
+    int device_cus = 0;                        // its compute units
+    std::vector<lfg_lane_state> lanes;         // never empty: lfg_context_create makes lane 0, lfg_lanes the others
+    int lane = 0;                              // the selected one
+    lfg_lane_state &cur() { return lanes[(size_t)lane]; }
+    const lfg_lane_state &cur() const { return lanes[(size_t)lane]; }
+    // the k-th lane from the selected one on (k < lanes.size()): loops over every lane visit the selected one first
+    lfg_lane_state &from_selected(size_t k) { return lanes[((size_t)lane + k) % lanes.size()]; }
+    // lfg_motion_prediction_stats: calls whose verdict came back, and the guesses it contradicted (all lanes together)
+    uint64_t pred_verdicts = 0, pred_lean_wrong = 0, pred_grid_wrong = 0, pred_second_wrong = 0;
+    std::string error;
+    std::vector<lfg::AxisTable> tables;       // small cache, linear search
+    std::vector<lfg::UvTable> uv_tables;      // likewise (interpolate)
     int motion_slots = 0;                      // prefilter workgroups resident at once on this device (0 = not queried yet)
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kPNT, 3) void motion_lean_kernel(
     // [kCand + 2]: most of the call's sample blocks have a near-exact match (motion_order_kernel) -- otherwise this is not the
     // content the kernel is for, and every workgroup leaves before it has staged anything
     // (a tile in which anything is left goes onto the list the generic kernel draws from behind its own table: here, all of them)
-    if ((order32[kCand + 2] & 1u) == 0u && !whateverTheVerdict) {
+    if (!verdict_lean(order32[kCand + 2]) && !whateverTheVerdict) {
         if (tid == 0 && !partial) hardTiles[atomicAdd(hardCount, 1u)] = (uint32_t)tile;      // (a rim tile's segments have their units in the plan)
         return;
     }

@@ -317,10 +317,10 @@ __global__ __launch_bounds__(kNT, 4) void motion_tiled_8_16_kernel(
     int parts = 1, part = 0, slot = 0;
     if (tileFlags) {
         const uint32_t flagged = *flaggedTiles;
-        // (for the host, which sizes the lane's NEXT launch of this pass by it: bit 30 of the call's verdict word -- which this
-        //  launch, the call's last, also delivers: one store into the host's pinned word, not a copy command behind the call)
+        // (for the host, which sizes the lane's NEXT launch of this pass by it: kVerdictFlagged in the call's verdict word -- which
+        //  this launch, the call's last, also delivers: one store into the host's pinned word, not a copy command behind the call)
         if (verdictWord && blockIdx.x == 0 && threadIdx.x == 0) {
-            const uint32_t word = *verdictWord | (flagged != 0u ? 1u << 30 : 0u);
+            const uint32_t word = verdict_with_flagged(*verdictWord, flagged != 0u);
             if (flagged != 0u) *verdictWord = word;
             if (hostWord) __hip_atomic_store(hostWord, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(kNT, 4) void motion_tiled_8_16_loop_kernel(
     __shared__ uint32_t sLast;
     const uint32_t flagged = *flaggedTiles;
     if (verdictWord && blockIdx.x == 0 && threadIdx.x == 0) {          // (see the kernel above)
-        const uint32_t word = *verdictWord | (flagged != 0u ? 1u << 30 : 0u);
+        const uint32_t word = verdict_with_flagged(*verdictWord, flagged != 0u);
         if (flagged != 0u) *verdictWord = word;
         if (hostWord) __hip_atomic_store(hostWord, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }

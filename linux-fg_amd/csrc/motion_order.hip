@@ -210,11 +210,10 @@ __global__ __launch_bounds__(kHints) void motion_order_kernel(
         for (int w = 0; w < kWaves; ++w) closeAll += sWaveClose[w];
         uint32_t moderateAll = 0u;
         for (int w = 0; w < kWaves; ++w) moderateAll += sWaveModerate[w];
-        // (bit 0: the verdict; above it the two counts, for LFG_DEBUG; bit 29: half the sample blocks or more match moderately well -- the
-        //  variant of the persistent kernel for the lane's next call; bit 30 is the literal pass's; bit 31: most sample blocks have a match
-        //  -- the host sizes the persistent grid of the lane's next call by it)
-        order32[kCand + 2] = (((closeAll & 0xFFFFu) * 16u >= 15u * (uint32_t)kHints) ? 1u : 0u) | ((closeAll & 0xFFFFu) << 1) | (((closeAll >> 16) & 0x7FFu) << 12) |
-                             ((moderateAll * 2u >= (uint32_t)kHints ? 1u : 0u) << 29) | (mostMatch << 31);
+        // (the call's verdict word, lfg_motion_verdict.hpp: the lean verdict and the two counts; half the sample blocks or more match
+        //  moderately well -- the variant of the persistent kernel for the lane's next call; most sample blocks have a match -- the host
+        //  sizes the persistent grid of the lane's next call by it.  The literal pass adds its own bit.)
+        order32[kCand + 2] = verdict_encode(closeAll, closeAll >> 16, moderateAll, (uint32_t)kHints, mostMatch);
         order32[0] = entryOfScan[top];
         if (top != zero) order32[1] = entryOfScan[zero];
         sRunning = top != zero ? 2u : 1u;

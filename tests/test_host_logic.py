@@ -1,5 +1,5 @@
 """Host-side logic that needs no GPU: the synthetic frame source (C++ vs Python), the exact 1/255
-split used by the kernels, the golden fixtures against the oracle, and the sharding helpers."""
+split used by the kernels, the golden fixtures against the oracle, the motion launch policy, and the sharding helpers."""
 import os
 import subprocess
 
@@ -61,6 +61,18 @@ def test_cpp_synthetic_capture_equals_python(synth_check, w, h, stream):
     for k in (1, 2):
         want = synth.translate(want, (3, -2), seed + k)
         assert (frames[k] == want).all()
+
+
+def test_motion_launch_policy_equals_its_pre_refactor_form(tmp_path):
+    """tests/cpp/motion_policy_check.cpp: csrc/lfg_motion_verdict.hpp (verdict word, launch policy, scoring) compiled with g++
+    alone and held to motion_run's former expressions over every verdict bit, lane state, flag and knob value."""
+    out = tmp_path / "motion_policy_check"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "linux-fg_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "motion_policy_check.cpp"), "-o", str(out)])
+    r = subprocess.run([str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    assert r.stdout.startswith("ok "), r.stdout
+    assert int(r.stdout.split()[1]) > 1_000_000
 
 
 def test_stream_assignment_covers_every_stream_once():
