@@ -249,6 +249,32 @@ int  lfg_motion_workspace_size(lfg_context *ctx, uint32_t width, uint32_t height
  * after such a change re-plans (it waits for the lane's stream once).  Reporting only; either pointer may be NULL. */
 int  lfg_motion_plan(const lfg_context *ctx, int *out_rim_split, int *out_workgroups);
 
+/* Coarse-to-fine (pyramid) block matcher, opt-in, next to the full search.  No reference counterpart: the reference has one
+ * +-16 full search (shaders/motion.comp:27-47).  Writes the same LFG_FORMAT_MV_S8X2 vectors -- 8 x 8 block p + [-4,3]^2,
+ * curr texels outside the image skipped, prev outside the image read as 0, prev(q + v) ~ curr(q) -- so every consumer of
+ * lfg_motion's output takes them unchanged.  Integer arithmetic only:
+ *   - levels 1 .. L of both frames: W_k = ceil(W_{k-1} / 2) (likewise H), each channel of P_k(x,y) the rounded mean
+ *     (sum + 2) >> 2 of P_{k-1} at (2x + i, 2y + j), i, j in {0,1}, coordinates clamped to the level;
+ *   - cost C_k(p, v) = sum over the block's texels q inside level k of sum_c |curr_k(q)_c - prev_k(q + v)_c|;
+ *   - the minimum of the key (C, vx^2 + vy^2, vy, vx) wins (not affected by lfg_set_semantics);
+ *   - level L: v in [-coarse_radius, coarse_radius]^2; level k < L: c + [-refine_radius, refine_radius]^2 and (0,0), with
+ *     c = 2 * v_{k+1}(x / 2, y / 2); mv = v_0.
+ * 1 <= levels <= 4, 1 <= coarse_radius <= 32, 1 <= refine_radius <= 4 and coarse_radius * 2^levels + refine_radius *
+ * (2^levels - 1) <= 127 (the longest vector); otherwise LFG_ERR_UNSUPPORTED before anything is enqueued.  The range is
+ * that bound: (2, 16, 2) reaches +-70 px.  Each call costs the same on any content.  Frames as lfg_motion takes them (RGBA8
+ * 4-byte aligned, any size).  Enqueued on the selected lane; keeps, per lane, device memory of
+ * 10 * sum over k = 1 .. levels of W_k * H_k bytes (plus up to 256 bytes of alignment per array): about 26 MB at 4K with
+ * (2, 16, 2).  Timed under LFG_STAGE_MOTION. */
+int  lfg_motion_pyramid(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame *mv,
+                        int levels, int coarse_radius, int refine_radius);
+/* The motion estimator of lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   LFG_ESTIMATOR_FULL_SEARCH (default): lfg_motion(8, 16), the reference's;
+ *   LFG_ESTIMATOR_PYRAMID: lfg_motion_pyramid(2, 16, 2) into the lane's temporary, then the interpolate stage
+ *       (lfg_set_fused_motion_interpolate does not apply).  Long vectors want LFG_SEMANTICS_INTENDED: under the reference
+ *       semantics a vector of 2 px or more moves both samples out of the image. */
+typedef enum lfg_motion_estimator { LFG_ESTIMATOR_FULL_SEARCH = 0, LFG_ESTIMATOR_PYRAMID = 1 } lfg_motion_estimator;
+int  lfg_set_motion_estimator(lfg_context *ctx, int estimator);
+
 /* Which arithmetic lfg_motion and lfg_interpolate follow.  No reference counterpart: SURVEY.md 8(f) rank 4.
  *   LFG_SEMANTICS_REFERENCE (default, the parity contract): the shaders as written -- equal block-match costs
  *       resolve to the first candidate in scan order, so flat areas report (-16,-16) (shaders/motion.comp:27-28,49;

@@ -20,6 +20,7 @@ FORMAT_MV_S8X2 = 1
 STAGE_SCALE, STAGE_MOTION, STAGE_INTERPOLATE = 0, 1, 2
 MOTION_PREFILTERED, MOTION_EXACT_ONLY = 0, 1
 SEMANTICS_REFERENCE, SEMANTICS_INTENDED = 0, 1
+ESTIMATOR_FULL_SEARCH, ESTIMATOR_PYRAMID = 0, 1
 _BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2}
 COMM_ID_BYTES = 128
 MAX_LANES = 4
@@ -82,6 +83,8 @@ SIGNATURES = {
     "lfg_motion_prediction_stats": (_i, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
     "lfg_motion_workspace_size": (_i, [_vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint64)]),
     "lfg_motion_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "lfg_motion_pyramid": (_i, [_vp, _FP, _FP, _FP, _i, _i, _i]),
+    "lfg_set_motion_estimator": (_i, [_vp, _i]),
     "lfg_set_semantics": (_i, [_vp, _i]),
     "lfg_interpolate": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float]),
     "lfg_interpolate_frames": (_i, [_vp, _FP, _FP, _FP, ctypes.c_float]),
@@ -285,6 +288,16 @@ class Context:
     def set_motion_mode(self, mode: int):
         """0 = prefiltered (default), 1 = exact kernel only; results are identical."""
         self._check(self.lib.lfg_set_motion_mode(self.h, mode), "lfg_set_motion_mode")
+
+    def motion_pyramid(self, prev: Frame, curr: Frame, mv: Frame, levels: int = 2, coarse_radius: int = 16, refine_radius: int = 2):
+        """Coarse-to-fine block matcher (lfg_motion_pyramid): the same vector format as motion(), a range of
+        coarse_radius * 2^levels + refine_radius * (2^levels - 1) pixels at a cost independent of the content."""
+        self._check(self.lib.lfg_motion_pyramid(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                int(levels), int(coarse_radius), int(refine_radius)), "lfg_motion_pyramid")
+
+    def set_motion_estimator(self, estimator: int):
+        """ESTIMATOR_FULL_SEARCH (default) or ESTIMATOR_PYRAMID for interpolate_frames[_multi]."""
+        self._check(self.lib.lfg_set_motion_estimator(self.h, int(estimator)), "lfg_set_motion_estimator")
 
     def set_semantics(self, semantics: int):
         """0 = the shaders as written (parity contract), 1 = opt-in "intended" tie-break and motion-vector units."""

@@ -459,6 +459,7 @@ void lane_release(lfg_lane_state &l) {
     if (l.mv_tmp.data && l.mv_tmp.owned) (void)hipFree(l.mv_tmp.data);
     if (l.mid_tmp.data && l.mid_tmp.owned) (void)hipFree(l.mid_tmp.data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
+    if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
     if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
@@ -857,6 +858,43 @@ LFG_EXPORT int lfg_set_motion_mode(lfg_context *ctx, int mode) {
     return LFG_OK;
 }
 
+LFG_EXPORT int lfg_motion_pyramid(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame *mv,
+                                  int levels, int coarse_radius, int refine_radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(mv, LFG_FORMAT_MV_S8X2))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_pyramid: prev/curr must be RGBA8 and mv MV_S8X2, all non-empty");
+    if (!same_size(prev, curr) || !same_size(curr, mv))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_pyramid: prev, curr and mv differ in size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u || mv->pitch % 2u || (uintptr_t)mv->data % 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_pyramid: RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
+    if (levels < 1 || levels > lfg::kPyramidMaxLevels || coarse_radius < 1 || coarse_radius > 32 || refine_radius < 1 || refine_radius > 4)
+        return fail(ctx, LFG_ERR_UNSUPPORTED, "lfg_motion_pyramid: need 1 <= levels <= 4, 1 <= coarse_radius <= 32, 1 <= refine_radius <= 4");
+    if (coarse_radius * (1 << levels) + refine_radius * ((1 << levels) - 1) > 127)
+        return fail(ctx, LFG_ERR_UNSUPPORTED, "lfg_motion_pyramid: coarse_radius * 2^levels + refine_radius * (2^levels - 1) exceeds 127");
+    lfg_lane_state &cur = ctx->cur();
+    lfg::PyramidLayout layout;
+    const size_t bytes = lfg::pyramid_workspace_bytes(curr->width, curr->height, levels, &layout);
+    if (bytes > cur.pyramid_ws_bytes) {
+        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // the lane's earlier calls may still read the old one
+        if (cur.pyramid_ws) (void)hipFree(cur.pyramid_ws);
+        cur.pyramid_ws = nullptr; cur.pyramid_ws_bytes = 0;
+        LFG_HIP(ctx, hipMalloc((void **)&cur.pyramid_ws, bytes));
+        cur.pyramid_ws_bytes = bytes;
+    }
+    StageTimer timer(ctx, LFG_STAGE_MOTION);
+    hipError_t e = lfg::launch_motion_pyramid(cur.stream, *prev, *curr, *mv, levels, coarse_radius, refine_radius, cur.pyramid_ws, layout);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pyramid motion kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_set_motion_estimator(lfg_context *ctx, int estimator) {
+    if (!ctx || (estimator != LFG_ESTIMATOR_FULL_SEARCH && estimator != LFG_ESTIMATOR_PYRAMID))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_motion_estimator: unknown estimator");
+    ctx->estimator = estimator;
+    return LFG_OK;
+}
+
 LFG_EXPORT int lfg_motion_workspace_size(lfg_context *ctx, uint32_t width, uint32_t height, uint64_t *out_bytes) {
     if (!ctx) return LFG_ERR_INVALID;
     if (!out_bytes || width == 0 || height == 0 || width > 32768u || height > 32768u)
@@ -1067,6 +1105,11 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
         int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
         if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
     }
+    if (ctx->estimator == LFG_ESTIMATOR_PYRAMID) {          // (the fused motion kernels are the full search's: two stages here)
+        int rc = lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2);
+        if (rc != LFG_OK) return rc;
+        return lfg_interpolate(ctx, prev, curr, &mv, out, factor);
+    }
     if (ctx->fuse_motion_interpolate) {
         // The north-star order: the motion kernels write the generated frame from the vectors while they
         // hold them; the vector frame -- this call's temporary -- is not written at all.  `out` is checked as lfg_interpolate
@@ -1126,7 +1169,8 @@ LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *p
         int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
         if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
     }
-    int rc = lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);                      // frame_manager.cpp:332-333
+    int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
+                                                     : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);   // frame_manager.cpp:332-333
     if (rc != LFG_OK) return rc;
     return lfg_interpolate_multi(ctx, prev, curr, &mv, outs, factors, count);
 }

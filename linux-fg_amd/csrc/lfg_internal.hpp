@@ -132,6 +132,16 @@ struct PrefilterPlanHost {
     std::vector<uint32_t> leanPartial;   // ... and rim tiles of which it takes the segments that lie inside the image: tile | mask of segments << 24
 };
 
+// Scratch of lfg_motion_pyramid (motion_pyramid.hip): byte offsets of levels 1 .. levels of both frames (RGBA8, rows of w * 4
+// bytes) and of their vector fields (MV_S8X2, rows of w * 2 bytes); w / h[0] is the frame's own size.
+constexpr int kPyramidMaxLevels = 4;
+struct PyramidLayout {
+    int levels = 0;
+    uint32_t w[kPyramidMaxLevels + 1] = {}, h[kPyramidMaxLevels + 1] = {};
+    size_t prev[kPyramidMaxLevels + 1] = {}, curr[kPyramidMaxLevels + 1] = {}, mv[kPyramidMaxLevels + 1] = {};
+    size_t total = 0;
+};
+
 struct ProfileSlot {
     hipEvent_t begin = nullptr, end = nullptr;
     int stage = 0;
@@ -151,6 +161,9 @@ struct lfg_lane_state {
     uint32_t motion_ws_w = 0, motion_ws_h = 0;
     lfg::MotionWorkspaceLayout motion_ws_layout{};
     int motion_units = 0;                      // work units of the prefilter for the current workspace size
+    // lfg_motion_pyramid: both frames' pyramids and the vector fields of levels 1 .. L, grown on demand
+    uint8_t *pyramid_ws = nullptr;
+    size_t pyramid_ws_bytes = 0;
     hipEvent_t mark = nullptr;                 // lfg_lane_mark
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
@@ -174,6 +187,7 @@ struct lfg_context {
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only
     int semantics = 0;                         // 0: the shaders as written, 1: "intended" (lfg_set_semantics)
+    int estimator = 0;                         // lfg_interpolate_frames[_multi]: LFG_ESTIMATOR_FULL_SEARCH / _PYRAMID (lfg_set_motion_estimator)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -268,6 +282,11 @@ hipError_t launch_interpolate(hipStream_t s, const lfg_frame &prev, const lfg_fr
 hipError_t launch_interpolate_multi(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                     const lfg_frame *const *outs, const float *factors, int count, bool intended,
                                     const InterpTables &tb);
+// Coarse-to-fine motion (motion_pyramid.hip): pyramid_workspace_bytes lays out the scratch for frames of this size, and
+// launch_motion_pyramid enqueues the pyramids, the level-L search and the refinements into it.
+size_t pyramid_workspace_bytes(uint32_t width, uint32_t height, int levels, PyramidLayout *layout);
+hipError_t launch_motion_pyramid(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                 int levels, int coarseRadius, int refineRadius, uint8_t *workspace, const PyramidLayout &layout);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

@@ -31,6 +31,10 @@ static void PrintUsage() {
               << "                           rank's current frames are its own stream.  FILE carries the communicator id.\n"
               << "  --comm-nonce N           A number the launcher gives every rank of ONE run (default: LFG_COMM_NONCE, else 0; more than one rank needs a non-zero one): an\n"
               << "                           id file left behind by another run is then never joined\n"
+              << "  --motion full|pyramid    Motion estimator of the generated frames (default full: the reference's +-16 search;\n"
+              << "                           pyramid: coarse-to-fine, +-70 px at a cost independent of the content)\n"
+              << "  --semantics reference|intended  Arithmetic of motion and interpolation (default reference: the shaders as\n"
+              << "                           written; intended: vectors displace by pixels -- what vectors longer than 1 px need)\n"
               << "  --frames N               Number of input frames to process (default: 10)\n"
               << "  --device N               HIP device ordinal (default: 0)\n"
               << "  --dump-dir DIR           Write every presented frame to DIR as raw RGBA8\n"
@@ -55,6 +59,7 @@ int main(int argc, char* argv[]) {
     int frames = 10, device = 0;
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
+    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false;
@@ -83,6 +88,18 @@ int main(int argc, char* argv[]) {
         else if (strcmp(argv[i], "--rank") == 0 && i + 1 < argc) rank = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--comm-file") == 0 && i + 1 < argc) commFile = argv[++i];
         else if (strcmp(argv[i], "--comm-nonce") == 0 && i + 1 < argc) commNonce = strtoull(argv[++i], nullptr, 0);
+        else if (strcmp(argv[i], "--motion") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "full") == 0) estimator = LFG_ESTIMATOR_FULL_SEARCH;
+            else if (strcmp(m, "pyramid") == 0) estimator = LFG_ESTIMATOR_PYRAMID;
+            else { LOG_ERROR("Invalid --motion (full|pyramid)"); return 1; }
+        }
+        else if (strcmp(argv[i], "--semantics") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "reference") == 0) semantics = LFG_SEMANTICS_REFERENCE;
+            else if (strcmp(m, "intended") == 0) semantics = LFG_SEMANTICS_INTENDED;
+            else { LOG_ERROR("Invalid --semantics (reference|intended)"); return 1; }
+        }
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--device") == 0 && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--dump-dir") == 0 && i + 1 < argc) dumpDir = argv[++i];
@@ -115,6 +132,13 @@ int main(int argc, char* argv[]) {
     }
 
     if (!HipContext::Get().Initialize(device)) { LOG_ERROR("Failed to initialize HIP"); return 1; }
+    // (library settings, like --in-flight: ScalerConfig keeps the reference's fields)
+    if (lfg_set_semantics(HipContext::Get().GetDevice(), semantics) != LFG_OK ||
+        lfg_set_motion_estimator(HipContext::Get().GetDevice(), estimator) != LFG_OK) {
+        LOG_ERROR("Failed to set the motion options: ", lfg_last_error(HipContext::Get().GetDevice()));
+        HipContext::Get().Cleanup();
+        return 1;
+    }
     if (!FrameManager::Get().Initialize(config.outputWidth, config.outputHeight)) {
         LOG_ERROR("Failed to initialize frame manager");
         HipContext::Get().Cleanup();
