@@ -270,8 +270,10 @@ int  lfg_motion_pyramid(lfg_context *ctx, const lfg_frame *prev, const lfg_frame
 /* The motion estimator of lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
  *   LFG_ESTIMATOR_FULL_SEARCH (default): lfg_motion(8, 16), the reference's;
  *   LFG_ESTIMATOR_PYRAMID: lfg_motion_pyramid(2, 16, 2) into the lane's temporary, then the interpolate stage
- *       (lfg_set_fused_motion_interpolate does not apply).  Long vectors want LFG_SEMANTICS_INTENDED: under the reference
- *       semantics a vector of 2 px or more moves both samples out of the image. */
+ *       (lfg_set_fused_motion_interpolate does not apply).  Under the reference semantics a vector of 2 px or more moves both
+ *       of lfg_interpolate's samples out of the image; LFG_SEMANTICS_INTENDED keeps them inside, but with the shader's signs,
+ *       which are backwards for these vectors (see LFG_SEMANTICS_INTENDED).  Content that moves wants
+ *       lfg_set_interpolator(LFG_INTERPOLATOR_COMPENSATED). */
 typedef enum lfg_motion_estimator { LFG_ESTIMATOR_FULL_SEARCH = 0, LFG_ESTIMATOR_PYRAMID = 1 } lfg_motion_estimator;
 int  lfg_set_motion_estimator(lfg_context *ctx, int estimator);
 
@@ -281,7 +283,12 @@ int  lfg_set_motion_estimator(lfg_context *ctx, int estimator);
  *       F6), and the pixel-unit motion vector is added to normalised uv unscaled (shaders/interpolate.comp:17,34-35; F5).
  *   LFG_SEMANTICS_INTENDED (opt-in): equal costs resolve to the shortest vector (then scan order), so flat areas
  *       report (0,0); interpolate divides the vector by the image size before adding it to uv, so it displaces
- *       by pixels.  Everything else (costs, sampling, signs, rounding) is unchanged; the oracle has the same switch. */
+ *       by pixels.  Everything else (costs, sampling, signs, rounding) is unchanged; the oracle has the same switch.
+ *       The signs stay the shader's (interpolate.comp:34-35): prev is read at g - v t and curr at g + v (1 - t), while the
+ *       vectors (prev(q + v) ~ curr(q)) put the content at g + v t in prev and g - v (1 - t) in curr.  So for moving content
+ *       the two samples land 2 |v| apart and neither is the content at g: every generated frame of a pan is a double image.
+ *       This mode stays as it is (pinned by the tests); lfg_interpolate_compensated is the interpolation that moves content
+ *       to where it is at time t, and it wants this mode for its motion stage (flat areas then report (0,0)). */
 typedef enum lfg_semantics { LFG_SEMANTICS_REFERENCE = 0, LFG_SEMANTICS_INTENDED = 1 } lfg_semantics;
 int  lfg_set_semantics(lfg_context *ctx, int semantics);
 
@@ -321,6 +328,46 @@ int  lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled);
  * lfg_interpolate_multi with the context-owned motion-vector temporary. */
 int  lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                   lfg_frame *const *outs, const float *factors, uint32_t count);
+
+/* Motion-compensated interpolation, opt-in, next to the shader's path.  No reference counterpart (the reference samples at
+ * g -+ mv(g), shaders/interpolate.comp:34-35).  The vectors are projected forward to time t and both frames are fetched along
+ * the projected vectors; pixels that nothing lands on are occlusions.  Always in pixels and with the vectors' own signs: it
+ * does not depend on lfg_set_semantics.  All float arithmetic is fp32 without contraction.
+ *   Inputs: prev, curr RGBA8 and mv LFG_FORMAT_MV_S8X2 (as lfg_motion / lfg_motion_pyramid write it; any byte values), all
+ *   W x H; factor t finite in [0, 1], s = 1.0f - t; 0 <= match_sad <= 1020.
+ *   Match gate: q with v = mv(q) is matched when sum over c of |curr(q)_c - prev(q + v)_c| <= match_sad, prev outside the
+ *   image read as 0.  An unmatched pixel's content is not in prev: its vector does not project.
+ *   Projection, every matched q: dx = (int)floorf((float)v.x * s + 0.5f), dy likewise, d = q + (dx, dy); outside the image
+ *   dropped, otherwise atomicMin of the key ((65535 - (vx^2 + vy^2)) << 16) | ((vy + 128) << 8) | (vx + 128) into K(d), K
+ *   starting at 0xFFFFFFFF (a hole).  The longest vector wins, then the smallest vy, then the smallest vx (without depth the
+ *   larger motion is taken for the foreground); the order is total, so the result does not depend on scheduling.
+ *   Sampling at d with the vector u decoded from K(d): P = ((float)d.x + 0.5f) + (float)u.x * t, C = ((float)d.x + 0.5f) -
+ *   (float)u.x * s, y likewise, each fetched with the bilinear clamp-to-edge rule of lfg_interpolate (same floor, weights and
+ *   sum order) in pixel units: u' = P.x - 0.5f.  A sample is inside when 0 <= x <= W and 0 <= y <= H.  Output: mix(Pv, Cv, t)
+ *   when both are inside or neither is, else the inside one; stored as lfg_interpolate stores (clamp, x 255, half to even).
+ *   Holes (K(d) = 0xFFFFFFFF): walk from d in each of the four axis directions, k = 1 .. 16, stopping at the image edge, and
+ *   keep each direction's first non-hole pixel; u = the smallest (|v|^2, vy, vx) of the kept vectors (the background-most),
+ *   (0, 0) if none.  P and C as above, and c = (clamp((int)floorf(C.x), 0, W - 1), likewise y): c unmatched -> Cv alone
+ *   (content revealed in curr); c matched with mv(c) != u -> Pv alone (content covered in curr); else as a projected pixel.
+ *   Hence t = 1 gives curr exactly for any vectors and match_sad, and a uniform even vector at t = 0.5 gives prev shifted by
+ *   -v / 2 on the interior.
+ * Frames: 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4), 2-byte aligned mv; the outputs must not overlap each
+ * other or any input.  Any violation, and a NaN, infinite or out-of-range factor or match_sad, returns LFG_ERR_INVALID before
+ * anything is enqueued.  Keeps, per lane, device memory of 4 * W * H bytes (33 MB at 4K), grown on demand.  Enqueued on the
+ * selected lane (clear K, project, interpolate per factor); timed under LFG_STAGE_INTERPOLATE.  _multi: 1 <= count <=
+ * LFG_MAX_FACTORS, outs[i] for factors[i], each identical to the single call. */
+int  lfg_interpolate_compensated(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                 lfg_frame *out, float factor, int match_sad);
+int  lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                       lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad);
+/* The interpolation of lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   LFG_INTERPOLATOR_SHADER (default): lfg_interpolate[_multi], the reference's shader; every path as before;
+ *   LFG_INTERPOLATOR_COMPENSATED: the selected estimator (lfg_set_motion_estimator) into the lane's temporary, then
+ *       lfg_interpolate_compensated[_multi] with match_sad (lfg_set_fused_motion_interpolate does not apply).  Use it with
+ *       LFG_SEMANTICS_INTENDED for the motion stage: under the reference tie order flat areas report (-16,-16).
+ * 0 <= match_sad <= 1020 (the default is 48); otherwise, or for an unknown interpolator, LFG_ERR_INVALID and no change. */
+typedef enum lfg_interpolator { LFG_INTERPOLATOR_SHADER = 0, LFG_INTERPOLATOR_COMPENSATED = 1 } lfg_interpolator;
+int  lfg_set_interpolator(lfg_context *ctx, int interpolator, int match_sad);
 
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --

@@ -21,6 +21,8 @@ STAGE_SCALE, STAGE_MOTION, STAGE_INTERPOLATE = 0, 1, 2
 MOTION_PREFILTERED, MOTION_EXACT_ONLY = 0, 1
 SEMANTICS_REFERENCE, SEMANTICS_INTENDED = 0, 1
 ESTIMATOR_FULL_SEARCH, ESTIMATOR_PYRAMID = 0, 1
+INTERPOLATOR_SHADER, INTERPOLATOR_COMPENSATED = 0, 1
+DEFAULT_MATCH_SAD = 48
 _BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2}
 COMM_ID_BYTES = 128
 MAX_LANES = 4
@@ -91,6 +93,9 @@ SIGNATURES = {
     "lfg_interpolate_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
     "lfg_interpolate_frames_multi": (_i, [_vp, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
     "lfg_interpolate_scale": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float]),
+    "lfg_interpolate_compensated": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
+    "lfg_interpolate_compensated_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
+    "lfg_set_interpolator": (_i, [_vp, _i, _i]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
     "lfg_mv_export_rgba32f": (_i, [_vp, _FP, _vp]),
@@ -379,6 +384,23 @@ class Context:
         po, pf, n = self._multi_args(outs, factors)
         self._check(self.lib.lfg_interpolate_frames_multi(self.h, ctypes.byref(prev), ctypes.byref(curr), po, pf, n),
                     "lfg_interpolate_frames_multi")
+
+    def interpolate_compensated(self, prev: Frame, curr: Frame, mv: Frame, out: Frame, factor: float = 0.5,
+                                match_sad: int = DEFAULT_MATCH_SAD):
+        """Motion-compensated interpolation (lfg_interpolate_compensated): the vectors projected to time `factor`, both
+        frames fetched along them, holes filled from the background-most neighbour."""
+        self._check(self.lib.lfg_interpolate_compensated(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                         ctypes.byref(out), factor, int(match_sad)), "lfg_interpolate_compensated")
+
+    def interpolate_compensated_multi(self, prev: Frame, curr: Frame, mv: Frame, outs, factors, match_sad: int = DEFAULT_MATCH_SAD):
+        """lfg_interpolate_compensated_multi: one generated frame per factor, each equal to the single call."""
+        po, pf, n = self._multi_args(outs, factors)
+        self._check(self.lib.lfg_interpolate_compensated_multi(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                               po, pf, n, int(match_sad)), "lfg_interpolate_compensated_multi")
+
+    def set_interpolator(self, interpolator: int, match_sad: int = DEFAULT_MATCH_SAD):
+        """INTERPOLATOR_SHADER (default) or INTERPOLATOR_COMPENSATED for interpolate_frames[_multi]."""
+        self._check(self.lib.lfg_set_interpolator(self.h, int(interpolator), int(match_sad)), "lfg_set_interpolator")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -1,0 +1,132 @@
+// interpolate_mc.hip -- motion-compensated interpolation (lfg_interpolate_compensated, include/linuxfg_hip.h): the vectors are
+// projected forward to time t, then both frames are fetched along the projected vectors.  No reference counterpart; opt-in,
+// next to interpolate.hip (the shader's path).  tests/mc_model.c restates every step below on the CPU.
+//
+// Two launches per factor, after the key image K (W * H words, the lane's scratch) has been set to 0xFF bytes in stream order:
+//   mc_project_kernel      one thread per source pixel q: the match gate, then one atomicMin of the vector's key into K(q + d);
+//   mc_interpolate_kernel  one thread per output pixel: K, the hole walk where K is a hole, both bilinear fetches, the blend.
+// The second launch starts once every projection is visible, and it never writes K: a hole's walk reads words of its
+// neighbours that other workgroups also read.
+//
+// Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 8
+// (two fetches, mostly cached neighbours) + 4 (out) in the interpolation: 34 bytes, 280 MB at 4K.
+#include "lfg_device.hpp"
+#include "lfg_internal.hpp"
+#include "lfg_interp.hpp"
+
+namespace lfg {
+
+namespace {
+
+constexpr uint32_t kMcHole = 0xFFFFFFFFu;
+constexpr int kMcWalk = 16;                    // the hole walk's reach, per axis direction
+constexpr int kMcBlockX = 64, kMcBlockY = 4;   // a wave is 64 pixels of one row
+
+__device__ __forceinline__ uint32_t texel_u32(const uint8_t *__restrict__ img, size_t pitch, int x, int y) {
+    return *reinterpret_cast<const uint32_t *>(img + (size_t)y * pitch + (size_t)x * 4u);
+}
+
+struct Mv { int x, y; };
+
+__device__ __forceinline__ Mv mv_at(const uint8_t *__restrict__ mv, size_t pitch, int x, int y) {
+    const uint16_t w = *reinterpret_cast<const uint16_t *>(mv + (size_t)y * pitch + (size_t)x * 2u);
+    return Mv{(int)(int8_t)(w & 0xffu), (int)(int8_t)(w >> 8)};
+}
+
+// The match gate: sum over the channels of |curr(q) - prev(q + v)| <= matchSad, prev outside the image read as 0.
+__device__ __forceinline__ bool matched(const uint8_t *__restrict__ prev, size_t prevPitch, uint32_t currTexel,
+                                        int W, int H, int qx, int qy, Mv v, int matchSad) {
+    const int sx = qx + v.x, sy = qy + v.y;
+    const uint32_t p = (sx >= 0 && sx < W && sy >= 0 && sy < H) ? texel_u32(prev, prevPitch, sx, sy) : 0u;
+    return __builtin_amdgcn_sad_u8(currTexel, p, 0u) <= (uint32_t)matchSad;
+}
+
+// Longest vector first, then the smallest vy, then the smallest vx: the smallest key wins.
+__device__ __forceinline__ uint32_t mc_key(Mv v) {
+    return ((uint32_t)(65535 - (v.x * v.x + v.y * v.y)) << 16) | ((uint32_t)(v.y + 128) << 8) | (uint32_t)(v.x + 128);
+}
+
+__device__ __forceinline__ Mv mc_decode(uint32_t key) { return Mv{(int)(key & 0xffu) - 128, (int)((key >> 8) & 0xffu) - 128}; }
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_kernel(
+        const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, int W, int H, float t, int matchSad, uint32_t *__restrict__ keys) {
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const Mv v = mv_at(mv, mvPitch, x, y);
+    if (!matched(prev, prevPitch, texel_u32(curr, currPitch, x, y), W, H, x, y, v, matchSad)) return;
+    const float s = 1.0f - t;
+    const int dx = x + (int)__builtin_floorf((float)v.x * s + 0.5f), dy = y + (int)__builtin_floorf((float)v.y * s + 0.5f);
+    if (dx < 0 || dx >= W || dy < 0 || dy >= H) return;
+    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, mc_key(v));     // the result is unused: one global_atomic_umin
+}
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad,
+        uint8_t *__restrict__ out, size_t outPitch) {
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const float s = 1.0f - t;
+    uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
+    const bool hole = key == kMcHole;
+    if (hole) {
+        // The fill vector: of the first non-hole word in each axis direction within kMcWalk, the smallest (|v|^2, vy, vx),
+        // i.e. the smallest of (65535 - key_hi) << 16 | key_lo; (0, 0) when every direction runs out.
+        uint32_t best = kMcHole;
+        const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            for (int k = 1; k <= kMcWalk; ++k) {
+                const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
+                if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
+                const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
+                if (n == kMcHole) continue;
+                const uint32_t order = ((65535u - (n >> 16)) << 16) | (n & 0xffffu);
+                best = order < best ? order : best;
+                break;
+            }
+        }
+        key = best == kMcHole ? (128u << 8) | 128u : best;        // only the low 16 bits are decoded
+    }
+    const Mv u = mc_decode(key);
+    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+    const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
+    const float Cx = px - (float)u.x * s, Cy = py - (float)u.y * s;
+    const SampleTaps sp = pixel_taps(prev, W, H, prevPitch, Px, Py);
+    const SampleTaps sc = pixel_taps(curr, W, H, currPitch, Cx, Cy);
+    const SampleTexels tp = sample_load(sp), tc = sample_load(sc);        // both fetches in flight before either is used
+    // 0: blend as a projected pixel, 1: prev's sample alone (covered), 2: curr's alone (revealed)
+    int only = 0;
+    if (hole) {
+        const int cx = clampi((int)__builtin_floorf(Cx), 0, W - 1), cy = clampi((int)__builtin_floorf(Cy), 0, H - 1);
+        const Mv vc = mv_at(mv, mvPitch, cx, cy);
+        if (!matched(prev, (size_t)prevPitch, texel_u32(curr, (size_t)currPitch, cx, cy), W, H, cx, cy, vc, matchSad)) only = 2;
+        else if (vc.x != u.x || vc.y != u.y) only = 1;
+    }
+    if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
+    const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
+    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
+    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+}
+
+}  // namespace
+
+hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {
+    const int W = (int)curr.width, H = (int)curr.height;
+    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 4u, s);
+    if (e != hipSuccess) return e;
+    const dim3 block(kMcBlockX, kMcBlockY), grid((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
+    hipLaunchKernelGGL(mc_project_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
+                       (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, factor,
+                       matchSad, keys);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mc_interpolate_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
+                       (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
+                       (const uint32_t *)keys, W, H, factor, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
+    return hipGetLastError();
+}
+
+}  // namespace lfg

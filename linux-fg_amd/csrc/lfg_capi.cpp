@@ -460,6 +460,7 @@ void lane_release(lfg_lane_state &l) {
     if (l.mid_tmp.data && l.mid_tmp.owned) (void)hipFree(l.mid_tmp.data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
+    if (l.mc_keys) (void)hipFree(l.mc_keys);
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
     if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
@@ -1105,6 +1106,12 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
         int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
         if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
     }
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {      // two stages under either estimator (no fused kernel)
+        int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
+                                                         : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);
+        if (rc != LFG_OK) return rc;
+        return lfg_interpolate_compensated(ctx, prev, curr, &mv, out, factor, ctx->match_sad);
+    }
     if (ctx->estimator == LFG_ESTIMATOR_PYRAMID) {          // (the fused motion kernels are the full search's: two stages here)
         int rc = lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2);
         if (rc != LFG_OK) return rc;
@@ -1172,7 +1179,86 @@ LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *p
     int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
                                                      : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);   // frame_manager.cpp:332-333
     if (rc != LFG_OK) return rc;
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
+        return lfg_interpolate_compensated_multi(ctx, prev, curr, &mv, outs, factors, count, ctx->match_sad);
     return lfg_interpolate_multi(ctx, prev, curr, &mv, outs, factors, count);
+}
+
+// ---- motion-compensated interpolation (interpolate_mc.hip)
+
+namespace {
+
+// The bytes a frame's pixels span: from the first row's start to the last row's last pixel.
+bool frames_overlap(const lfg_frame *a, const lfg_frame *b) {
+    const uintptr_t a0 = (uintptr_t)a->data, b0 = (uintptr_t)b->data;
+    const uintptr_t a1 = a0 + (size_t)a->pitch * (a->height - 1u) + (size_t)a->width * bytes_per_pixel(a->format);
+    const uintptr_t b1 = b0 + (size_t)b->pitch * (b->height - 1u) + (size_t)b->width * bytes_per_pixel(b->format);
+    return a0 < b1 && b0 < a1;
+}
+
+int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                    lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    const std::string n(name);
+    if (!outs || !factors || count == 0 || count > LFG_MAX_FACTORS)
+        return fail(ctx, LFG_ERR_INVALID, n + ": count must be in [1, LFG_MAX_FACTORS] and outs/factors non-NULL");
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(mv, LFG_FORMAT_MV_S8X2))
+        return fail(ctx, LFG_ERR_INVALID, n + ": prev/curr must be RGBA8 and mv MV_S8X2, all non-empty");
+    if (!same_size(prev, curr) || !same_size(curr, mv))
+        return fail(ctx, LFG_ERR_INVALID, n + ": prev, curr and mv differ in size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u || mv->pitch % 2u || (uintptr_t)mv->data % 2u)
+        return fail(ctx, LFG_ERR_INVALID, n + ": RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
+    if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, n + ": match_sad must be in [0, 1020]");
+    for (uint32_t i = 0; i < count; ++i) {
+        const lfg_frame *o = outs[i];
+        if (!frame_ok(o, LFG_FORMAT_RGBA8_UNORM) || !same_size(curr, o) || o->pitch % 4u || (uintptr_t)o->data % 4u)
+            return fail(ctx, LFG_ERR_INVALID, n + ": bad output frame (NULL, empty, wrong format, size or alignment)");
+        if (!std::isfinite(factors[i]) || factors[i] < 0.0f || factors[i] > 1.0f)
+            return fail(ctx, LFG_ERR_INVALID, n + ": every factor must be a finite number in [0, 1]");
+        if (frames_overlap(o, prev) || frames_overlap(o, curr) || frames_overlap(o, mv))
+            return fail(ctx, LFG_ERR_INVALID, n + ": an output aliases an input");
+        for (uint32_t j = 0; j < i; ++j)
+            if (frames_overlap(outs[j], o)) return fail(ctx, LFG_ERR_INVALID, n + ": two outputs alias each other");
+    }
+    lfg_lane_state &cur = ctx->cur();
+    const size_t bytes = (size_t)curr->width * curr->height * 4u;
+    if (bytes > cur.mc_keys_bytes) {
+        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // the lane's earlier calls may still read the old one
+        if (cur.mc_keys) (void)hipFree(cur.mc_keys);
+        cur.mc_keys = nullptr; cur.mc_keys_bytes = 0;
+        LFG_HIP(ctx, hipMalloc((void **)&cur.mc_keys, bytes));
+        cur.mc_keys_bytes = bytes;
+    }
+    StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
+    for (uint32_t i = 0; i < count; ++i) {                       // one key image, reused in stream order
+        hipError_t e = lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
+        if (e != hipSuccess) return fail_hip(ctx, e, "compensated interpolate kernel launch");
+    }
+    return LFG_OK;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_interpolate_compensated(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                           lfg_frame *out, float factor, int match_sad) {
+    lfg_frame *const outs[1] = {out};
+    return compensated_run(ctx, prev, curr, mv, outs, &factor, 1, match_sad, "lfg_interpolate_compensated");
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                                 lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad) {
+    return compensated_run(ctx, prev, curr, mv, outs, factors, count, match_sad, "lfg_interpolate_compensated_multi");
+}
+
+LFG_EXPORT int lfg_set_interpolator(lfg_context *ctx, int interpolator, int match_sad) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (interpolator != LFG_INTERPOLATOR_SHADER && interpolator != LFG_INTERPOLATOR_COMPENSATED)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_interpolator: unknown interpolator");
+    if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, "lfg_set_interpolator: match_sad must be in [0, 1020]");
+    ctx->interpolator = interpolator;
+    ctx->match_sad = match_sad;
+    return LFG_OK;
 }
 
 LFG_EXPORT int lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled) {

@@ -164,6 +164,9 @@ struct lfg_lane_state {
     // lfg_motion_pyramid: both frames' pyramids and the vector fields of levels 1 .. L, grown on demand
     uint8_t *pyramid_ws = nullptr;
     size_t pyramid_ws_bytes = 0;
+    // lfg_interpolate_compensated: the key image K of one factor (W * H words), grown on demand
+    uint32_t *mc_keys = nullptr;
+    size_t mc_keys_bytes = 0;
     hipEvent_t mark = nullptr;                 // lfg_lane_mark
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
@@ -188,6 +191,8 @@ struct lfg_context {
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only
     int semantics = 0;                         // 0: the shaders as written, 1: "intended" (lfg_set_semantics)
     int estimator = 0;                         // lfg_interpolate_frames[_multi]: LFG_ESTIMATOR_FULL_SEARCH / _PYRAMID (lfg_set_motion_estimator)
+    int interpolator = 0;                      // lfg_interpolate_frames[_multi]: LFG_INTERPOLATOR_SHADER / _COMPENSATED (lfg_set_interpolator)
+    int match_sad = 48;                        // ... and the compensated interpolator's match gate
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -287,6 +292,9 @@ hipError_t launch_interpolate_multi(hipStream_t s, const lfg_frame &prev, const 
 size_t pyramid_workspace_bytes(uint32_t width, uint32_t height, int levels, PyramidLayout *layout);
 hipError_t launch_motion_pyramid(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                  int levels, int coarseRadius, int refineRadius, uint8_t *workspace, const PyramidLayout &layout);
+// Motion-compensated interpolation (interpolate_mc.hip): clears `keys` (W * H words), projects, interpolates; one factor.
+hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

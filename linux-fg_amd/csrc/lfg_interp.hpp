@@ -115,6 +115,35 @@ __device__ __forceinline__ V4 sample_finish(const SampleTaps &s, const SampleTex
     return r;
 }
 
+// ---- texture_bilinear's pixel-unit sibling, in the same two steps (interpolate_mc.hip): (px, py) is a position in pixels with
+// texel centres at i + 0.5, so u = px - 0.5 replaces s * W - 0.5; floor, weights, clamping and sum order are texture_bilinear's.
+// `inside` is 0 <= px <= W and 0 <= py <= H; unlike sample_finish, blend_taps never zeroes a sample.  Callers keep positions
+// within a few hundred pixels of the image, so the floors fit an int.
+__device__ __forceinline__ SampleTaps pixel_taps(const uint8_t *__restrict__ img, int W, int H, int pitch, float px, float py) {
+    SampleTaps s;
+    s.inside = px >= 0.0f && px <= (float)W && py >= 0.0f && py <= (float)H;
+    const float u = px - 0.5f, v = py - 0.5f;
+    const float fu = __builtin_floorf(u), fv = __builtin_floorf(v);
+    const float a = u - fu, b = v - fv;
+    const int i0 = (int)fu, j0 = (int)fv;
+    s.i0 = clampi(i0, 0, W - 1); s.i1 = clampi(i0 + 1, 0, W - 1);
+    s.r0 = img + (size_t)clampi(j0, 0, H - 1) * (size_t)pitch;
+    s.r1 = img + (size_t)clampi(j0 + 1, 0, H - 1) * (size_t)pitch;
+    s.w00 = (1.0f - a) * (1.0f - b); s.w10 = a * (1.0f - b);
+    s.w01 = (1.0f - a) * b; s.w11 = a * b;
+    return s;
+}
+
+__device__ __forceinline__ V4 blend_taps(const SampleTaps &s, const SampleTexels &t) {
+    const V4 t00 = unorm4(t.t00), t10 = unorm4(t.t10), t01 = unorm4(t.t01), t11 = unorm4(t.t11);
+    V4 r;
+    r.x = ((s.w00 * t00.x + s.w10 * t10.x) + s.w01 * t01.x) + s.w11 * t11.x;
+    r.y = ((s.w00 * t00.y + s.w10 * t10.y) + s.w01 * t01.y) + s.w11 * t11.y;
+    r.z = ((s.w00 * t00.z + s.w10 * t10.z) + s.w01 * t01.z) + s.w11 * t11.z;
+    r.w = ((s.w00 * t00.w + s.w10 * t10.w) + s.w01 * t01.w) + s.w11 * t11.w;
+    return r;
+}
+
 // One interpolated pixel as packed RGBA8: mix(S(prev, uv - mv t), S(curr, uv + mv (1 - t)), t), clamped, x 255,
 // round half to even (interpolate.comp:30-39).  mx, my: the motion vector in pixels (already divided by the image
 // size under the opt-in intended semantics).

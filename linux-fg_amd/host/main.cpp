@@ -35,6 +35,8 @@ static void PrintUsage() {
               << "                           pyramid: coarse-to-fine, +-70 px at a cost independent of the content)\n"
               << "  --semantics reference|intended  Arithmetic of motion and interpolation (default reference: the shaders as\n"
               << "                           written; intended: vectors displace by pixels -- what vectors longer than 1 px need)\n"
+              << "  --interpolator shader|compensated  Interpolation of the generated frames (default shader: the reference's;\n"
+              << "                           compensated: vectors projected to the frame's time, holes filled; wants --semantics intended)\n"
               << "  --frames N               Number of input frames to process (default: 10)\n"
               << "  --device N               HIP device ordinal (default: 0)\n"
               << "  --dump-dir DIR           Write every presented frame to DIR as raw RGBA8\n"
@@ -59,7 +61,7 @@ int main(int argc, char* argv[]) {
     int frames = 10, device = 0;
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
-    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE;
+    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false;
@@ -100,6 +102,12 @@ int main(int argc, char* argv[]) {
             else if (strcmp(m, "intended") == 0) semantics = LFG_SEMANTICS_INTENDED;
             else { LOG_ERROR("Invalid --semantics (reference|intended)"); return 1; }
         }
+        else if (strcmp(argv[i], "--interpolator") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "shader") == 0) interpolator = LFG_INTERPOLATOR_SHADER;
+            else if (strcmp(m, "compensated") == 0) interpolator = LFG_INTERPOLATOR_COMPENSATED;
+            else { LOG_ERROR("Invalid --interpolator (shader|compensated)"); return 1; }
+        }
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--device") == 0 && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--dump-dir") == 0 && i + 1 < argc) dumpDir = argv[++i];
@@ -134,7 +142,8 @@ int main(int argc, char* argv[]) {
     if (!HipContext::Get().Initialize(device)) { LOG_ERROR("Failed to initialize HIP"); return 1; }
     // (library settings, like --in-flight: ScalerConfig keeps the reference's fields)
     if (lfg_set_semantics(HipContext::Get().GetDevice(), semantics) != LFG_OK ||
-        lfg_set_motion_estimator(HipContext::Get().GetDevice(), estimator) != LFG_OK) {
+        lfg_set_motion_estimator(HipContext::Get().GetDevice(), estimator) != LFG_OK ||
+        lfg_set_interpolator(HipContext::Get().GetDevice(), interpolator, 48) != LFG_OK) {
         LOG_ERROR("Failed to set the motion options: ", lfg_last_error(HipContext::Get().GetDevice()));
         HipContext::Get().Cleanup();
         return 1;

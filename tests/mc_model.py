@@ -1,0 +1,101 @@
+"""CPU model of lfg_interpolate_compensated (include/linuxfg_hip.h): the match gate, the projection of the vectors to time t,
+the hole fill and the sampling, in the header's fp32 operation order.  The loops are C (tests/mc_model.c, built here with
+the system C compiler and -ffp-contract=off on first use).
+
+``interpolate_compensated(prev, curr, mv, t, match_sad)`` gives the whole frame; ``..., roi=(x, y, w, h)`` only the ROI's
+pixels (the projection still covers the whole frame: any source pixel may land in the ROI), so ROIs of a 4K or 8K frame are
+cheap.  ``keys(...)`` is the projected key image itself, and ``sample(..., K, ...)`` the sampling step from any key image."""
+from __future__ import annotations
+
+import ctypes
+import hashlib
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SRC = os.path.join(_HERE, "mc_model.c")
+_lib = None
+
+HOLE = 0xFFFFFFFF
+DEFAULT_MATCH_SAD = 48
+
+
+def _load():
+    global _lib
+    if _lib is None:
+        src = open(_SRC, "rb").read()
+        out = os.path.join(tempfile.gettempdir(), f"lfg_mc_model_{os.getuid()}_{hashlib.sha1(src).hexdigest()[:12]}.so")
+        if not os.path.exists(out):
+            tmp = out + f".{os.getpid()}"
+            subprocess.check_call([os.environ.get("CC", "cc"), "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", tmp, _SRC, "-lm"])
+            os.replace(tmp, out)
+        L = ctypes.CDLL(out)
+        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.mc_project.argtypes = [vp, vp, vp, i, i, f, i, vp]
+        L.mc_project.restype = None
+        L.mc_sample.argtypes = [vp, vp, vp, vp, i, i, f, i, i, i, i, i, vp]
+        L.mc_sample.restype = None
+        _lib = L
+    return _lib
+
+
+def _ptr(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _inputs(prev, curr, mv):
+    prev = np.ascontiguousarray(prev, np.uint8)
+    curr = np.ascontiguousarray(curr, np.uint8)
+    mv = np.ascontiguousarray(mv).astype(np.int8, copy=False)
+    assert prev.shape == curr.shape and prev.shape[2] == 4 and mv.shape == prev.shape[:2] + (2,)
+    return prev, curr, np.ascontiguousarray(mv)
+
+
+def key(vx: int, vy: int) -> int:
+    """A vector's projection key: the smallest key wins (longest vector, then smallest vy, then smallest vx)."""
+    return ((65535 - (vx * vx + vy * vy)) << 16) | ((vy + 128) << 8) | (vx + 128)
+
+
+def keys(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, t: float, match_sad: int = DEFAULT_MATCH_SAD) -> np.ndarray:
+    """(H, W) uint32: the projected key of every pixel, HOLE where nothing lands."""
+    prev, curr, mv = _inputs(prev, curr, mv)
+    H, W = prev.shape[:2]
+    K = np.empty((H, W), np.uint32)
+    _load().mc_project(_ptr(prev), _ptr(curr), _ptr(mv), W, H, float(t), int(match_sad), _ptr(K))
+    return K
+
+
+def interpolate_compensated(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, t: float,
+                            match_sad: int = DEFAULT_MATCH_SAD, roi=None) -> np.ndarray:
+    """(H, W, 4) uint8 of the whole frame, or (h, w, 4) of roi = (x, y, w, h)."""
+    return sample(prev, curr, mv, keys(prev, curr, mv, t, match_sad), t, match_sad, roi)
+
+
+def sample(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, K: np.ndarray, t: float,
+           match_sad: int = DEFAULT_MATCH_SAD, roi=None) -> np.ndarray:
+    """The sampling step alone, from a key image K (H, W) uint32 given by the caller: lets a test place keys and holes."""
+    prev, curr, mv = _inputs(prev, curr, mv)
+    H, W = prev.shape[:2]
+    K = np.ascontiguousarray(K, np.uint32)
+    assert K.shape == (H, W)
+    x, y, w, h = roi if roi is not None else (0, 0, W, H)
+    out = np.empty((h, w, 4), np.uint8)
+    _load().mc_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(t), int(match_sad), x, y, x + w, y + h, _ptr(out))
+    return out
+
+
+def moving_square(w: int = 96, h: int = 64, size: int = 16, at=(30, 24), shift=(12, 0), seed: int = 7):
+    """A textured size x size square that moves by `shift` over a static textured background: (prev, curr, square's
+    top-left in prev).  The textures are uncorrelated noise, so the block matcher finds both motions."""
+    rng = np.random.default_rng(seed)
+    bg = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    sq = rng.integers(0, 256, (size, size, 4), dtype=np.uint8)
+    x, y = at
+    prev = bg.copy()
+    prev[y:y + size, x:x + size] = sq
+    curr = bg.copy()
+    curr[y + shift[1]:y + shift[1] + size, x + shift[0]:x + shift[0] + size] = sq
+    return prev, curr, (x, y)

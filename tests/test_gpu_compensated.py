@@ -1,0 +1,370 @@
+"""lfg_interpolate_compensated on the GPU against the CPU model (tests/mc_model.py), byte for byte; what it gets right that
+the shader's modes do not; the interpolator switch of lfg_interpolate_frames[_multi]; argument checks; lanes; and the host's
+--interpolator option."""
+import ctypes
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from linux_fg_amd import capi, synth
+from tests import mc_model as mc
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
+
+SIZES = [(1, 1), (7, 5), (33, 17), (64, 64), (257, 131)]
+FACTORS = [0.0, 0.25, 0.5, 0.75, 1.0]
+MATCH = [0, 48, 1020]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import __graft_entry__ as entry
+    if not os.path.exists(capi.LIB_PATH):
+        entry.build()
+    with capi.Context(0) as c:
+        yield c
+
+
+def gpu_vectors(ctx, prev, curr, estimator):
+    h, w = prev.shape[:2]
+    p, c = ctx.frame_from(prev), ctx.frame_from(curr)
+    m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
+    ctx.set_semantics(capi.SEMANTICS_INTENDED)
+    try:
+        if estimator == "full":
+            ctx.motion(p, c, m)
+        else:
+            ctx.motion_pyramid(p, c, m, 2, 16, 2)
+        return ctx.download(m)
+    finally:
+        ctx.set_semantics(capi.SEMANTICS_REFERENCE)
+        for f in (p, c, m):
+            ctx.destroy_frame(f)
+
+
+def case(ctx, field, w, h, seed):
+    """(prev, curr, mv int8) for one kind of vector field."""
+    rng = np.random.default_rng(seed)
+    if field in ("motion", "pyramid"):
+        prev = synth.make_prev(w, h, synth.BASE_SEED + seed)
+        curr = synth.translate(prev, (5, -3) if field == "motion" else (-30, 18), synth.BASE_SEED + seed)
+        return prev, curr, gpu_vectors(ctx, prev, curr, "full" if field == "motion" else "pyramid")
+    prev = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    mv = np.zeros((h, w, 2), np.int8)
+    if field == "uniform":
+        mv[...] = rng.integers(-20, 21, 2)
+        curr = synth.translate(prev, tuple(-int(v) for v in mv[0, 0]), synth.BASE_SEED + seed)
+    elif field == "piecewise":            # four quadrants with their own vectors: collisions along the seams
+        vs = rng.integers(-12, 13, (4, 2))
+        mv[: h // 2, : w // 2], mv[: h // 2, w // 2:], mv[h // 2:, : w // 2], mv[h // 2:, w // 2:] = vs
+        curr = np.clip(prev.astype(np.int16) + rng.integers(-6, 7, prev.shape), 0, 255).astype(np.uint8)
+    else:                                 # dense random over the full byte range: holes and conflicts everywhere
+        mv = rng.integers(-128, 128, (h, w, 2)).astype(np.int8)
+        curr = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    return prev, curr, mv
+
+
+def run(ctx, prev, curr, mv, t, match_sad):
+    h, w = prev.shape[:2]
+    p, c, m = ctx.frame_from(prev), ctx.frame_from(curr), ctx.frame_from(mv, capi.FORMAT_MV_S8X2)
+    o = ctx.create_frame(w, h)
+    try:
+        ctx.interpolate_compensated(p, c, m, o, t, match_sad)
+        return ctx.download(o)
+    finally:
+        for f in (p, c, m, o):
+            ctx.destroy_frame(f)
+
+
+def first_bad(got, want):
+    bad = np.argwhere((got != want).any(-1))
+    return f"{len(bad)} pixels differ, first {bad[:3].tolist()}"
+
+
+@pytest.mark.parametrize("field", ["uniform", "piecewise", "random", "motion", "pyramid"])
+def test_every_pixel_equals_the_model(ctx, field):
+    for i, (w, h) in enumerate(SIZES):
+        prev, curr, mv = case(ctx, field, w, h, 13 * i + 5)
+        for t in FACTORS:
+            for ms in MATCH:
+                got = run(ctx, prev, curr, mv, t, ms)
+                want = mc.interpolate_compensated(prev, curr, mv, t, ms)
+                assert (got == want).all(), f"{w}x{h} {field} t={t} match_sad={ms}: {first_bad(got, want)}"
+
+
+@pytest.mark.parametrize("w,h", [(640, 360), (1920, 1080)])
+def test_full_frames(ctx, w, h):
+    for field in ("piecewise", "random", "motion", "pyramid"):
+        prev, curr, mv = case(ctx, field, w, h, 3)
+        for t, ms in ((0.25, 48), (0.5, 1020), (0.75, 0)):
+            got = run(ctx, prev, curr, mv, t, ms)
+            want = mc.interpolate_compensated(prev, curr, mv, t, ms)
+            assert (got == want).all(), f"{w}x{h} {field} t={t}: {first_bad(got, want)}"
+
+
+@pytest.mark.parametrize("w,h", [(3840, 2160), (7680, 4320)])
+def test_rois_of_4k_and_8k(ctx, w, h):
+    rng = np.random.default_rng(w)
+    rois = [(0, 0, 64, 64), (w - 64, h - 64, 64, 64)] + [(int(rng.integers(0, w - 64)), int(rng.integers(0, h - 64)), 64, 64)
+                                                         for _ in range(6)]
+    for field, t, ms in (("random", 0.5, 1020), ("motion", 0.25, 48)):
+        prev, curr, mv = case(ctx, field, w, h, 9)
+        got = run(ctx, prev, curr, mv, t, ms)
+        for x, y, rw, rh in rois:
+            want = mc.interpolate_compensated(prev, curr, mv, t, ms, roi=(x, y, rw, rh))
+            assert (got[y:y + rh, x:x + rw] == want).all(), (w, h, field, x, y)
+
+
+def pitched(ctx, host, pad_px, fmt=capi.FORMAT_RGBA8):
+    """`host` in the left part of a wider frame, described with the wider row pitch (lfg_frame_wrap); the padding poisoned."""
+    h, w, ch = host.shape
+    wide = np.full((h, w + pad_px, ch), 0x5A, host.dtype)
+    wide[:, :w] = host
+    big = ctx.frame_from(wide, fmt)
+    return big, capi.Context.wrap(big.data, w, h, fmt, pitch=(w + pad_px) * ch)
+
+
+def test_padded_pitch(ctx):
+    w, h = 257, 131
+    prev, curr, mv = case(ctx, "random", w, h, 17)
+    bp, p = pitched(ctx, prev, 3)
+    bc, c = pitched(ctx, curr, 5)
+    bm, m = pitched(ctx, mv, 7, capi.FORMAT_MV_S8X2)
+    bo, o = pitched(ctx, np.zeros((h, w, 4), np.uint8), 9)
+    try:
+        for t, ms in ((0.5, 1020), (0.25, 0)):
+            ctx.interpolate_compensated(p, c, m, o, t, ms)
+            raw = ctx.download(bo)
+            assert (raw[:, w:] == 0x5A).all()                     # the padding is not written
+            want = mc.interpolate_compensated(prev, curr, mv, t, ms)
+            assert (raw[:, :w] == want).all(), first_bad(raw[:, :w], want)
+    finally:
+        for f in (bp, bc, bm, bo):
+            ctx.destroy_frame(f)
+
+
+def test_multi_equals_single_calls(ctx):
+    w, h = 640, 360
+    prev, curr, mv = case(ctx, "piecewise", w, h, 23)
+    factors = [0.25, 0.5, 0.75, 1.0, 0.0]
+    p, c, m = ctx.frame_from(prev), ctx.frame_from(curr), ctx.frame_from(mv, capi.FORMAT_MV_S8X2)
+    outs = [ctx.create_frame(w, h) for _ in factors]
+    try:
+        ctx.interpolate_compensated_multi(p, c, m, outs, factors, 48)
+        multi = [ctx.download(o) for o in outs]
+        for t, got in zip(factors, multi):
+            ctx.interpolate_compensated(p, c, m, outs[0], t, 48)
+            assert (got == ctx.download(outs[0])).all(), t
+    finally:
+        for f in [p, c, m] + outs:
+            ctx.destroy_frame(f)
+
+
+# ---- what the shader's modes do not do: content at time t where it is
+
+def test_4k_pan_full_search(ctx):
+    w, h = 3840, 2160
+    prev = synth.make_prev(w, h)
+    curr = synth.translate(prev, (6, -4))
+    mv = gpu_vectors(ctx, prev, curr, "full")
+    got = run(ctx, prev, curr, mv, 0.5, 48)
+    want = synth.translate(prev, (3, -2))
+    assert (got[24:-24, 24:-24] == want[24:-24, 24:-24]).all(), first_bad(got[24:-24, 24:-24], want[24:-24, 24:-24])
+
+
+def test_4k_pan_pyramid(ctx):
+    w, h = 3840, 2160
+    prev = synth.make_prev(w, h)
+    curr = synth.translate(prev, (40, -24))
+    mv = gpu_vectors(ctx, prev, curr, "pyramid")
+    got = run(ctx, prev, curr, mv, 0.5, 48)
+    want = synth.translate(prev, (20, -12))
+    assert (got[100:-100, 100:-100] == want[100:-100, 100:-100]).all(), first_bad(got[100:-100, 100:-100], want[100:-100, 100:-100])
+
+
+def test_moving_square(ctx):
+    prev, curr, (x, y) = mc.moving_square()
+    mv = gpu_vectors(ctx, prev, curr, "full")
+    bg = np.random.default_rng(7).integers(0, 256, prev.shape, dtype=np.uint8)     # moving_square's own background
+    for t in (0.25, 0.5, 0.75):
+        s = int(12 * t)
+        truth = bg.copy()
+        truth[y:y + 16, x + s:x + s + 16] = prev[y:y + 16, x:x + 16]
+        got = run(ctx, prev, curr, mv, t, 48)
+        assert (got == mc.interpolate_compensated(prev, curr, mv, t, 48)).all()
+        ok = (got == truth).all(-1)
+        assert ok[y + 4:y + 12, x + s + 4:x + s + 12].all(), t
+        swept = np.zeros_like(ok)
+        swept[y - 4:y + 20, x - 4:x + 12 + 20] = True
+        assert ok[~swept].all(), t
+
+
+# ---- the interpolator switch
+
+@pytest.mark.parametrize("estimator", [capi.ESTIMATOR_FULL_SEARCH, capi.ESTIMATOR_PYRAMID])
+def test_interpolator_switch(ctx, estimator):
+    w, h = 640, 360
+    prev = synth.make_prev(w, h)
+    curr = synth.translate(prev, (9, -5))
+    factors = [0.25, 0.5, 0.75]
+    p, c = ctx.frame_from(prev), ctx.frame_from(curr)
+    m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
+    outs = [ctx.create_frame(w, h) for _ in factors]
+    ref = ctx.create_frame(w, h)
+    try:
+        ctx.set_semantics(capi.SEMANTICS_INTENDED)
+        ctx.set_motion_estimator(estimator)
+        if estimator == capi.ESTIMATOR_PYRAMID:
+            ctx.motion_pyramid(p, c, m, 2, 16, 2)
+        else:
+            ctx.motion(p, c, m)
+        for ms in (48, 300):
+            want = {}
+            for t in factors:
+                ctx.interpolate_compensated(p, c, m, ref, t, ms)
+                want[t] = ctx.download(ref)
+            ctx.set_interpolator(capi.INTERPOLATOR_COMPENSATED, ms)
+            for fused in (False, True):
+                ctx.set_fused_motion_interpolate(fused)
+                ctx.interpolate_frames(p, c, outs[0], 0.5)
+                assert (ctx.download(outs[0]) == want[0.5]).all(), (ms, fused)
+                ctx.interpolate_frames_multi(p, c, outs, factors)
+                for t, o in zip(factors, outs):
+                    assert (ctx.download(o) == want[t]).all(), (ms, fused, t)
+            ctx.set_fused_motion_interpolate(False)
+        # back on the shader: lfg_motion (or the pyramid) followed by lfg_interpolate
+        ctx.set_interpolator(capi.INTERPOLATOR_SHADER)
+        ctx.interpolate_frames(p, c, outs[0], 0.5)
+        ctx.interpolate(p, c, m, ref, 0.5)
+        assert (ctx.download(outs[0]) == ctx.download(ref)).all()
+    finally:
+        ctx.set_interpolator(capi.INTERPOLATOR_SHADER)
+        ctx.set_motion_estimator(capi.ESTIMATOR_FULL_SEARCH)
+        ctx.set_semantics(capi.SEMANTICS_REFERENCE)
+        ctx.set_fused_motion_interpolate(False)
+        for f in [p, c, m, ref] + outs:
+            ctx.destroy_frame(f)
+
+
+def test_invalid_arguments_launch_nothing(ctx):
+    lib = ctx.lib
+    w, h = 40, 24
+    prev, curr, mv = case(ctx, "random", w, h, 1)
+    p, c, m = ctx.frame_from(prev), ctx.frame_from(curr), ctx.frame_from(mv, capi.FORMAT_MV_S8X2)
+    o, o2 = ctx.create_frame(w, h), ctx.create_frame(w, h)
+    pattern = np.full((h, w, 4), 0x5A, np.uint8)
+    ctx.upload(o, pattern)
+    ctx.upload(o2, pattern)
+    small = ctx.create_frame(w - 1, h)
+    small_mv = ctx.create_frame(w, h - 1, capi.FORMAT_MV_S8X2)
+    wide = ctx.create_frame(w + 1, h)
+    odd = capi.Context.wrap(wide.data, w, h, capi.FORMAT_RGBA8, pitch=w * 4 + 2)    # a pitch that is not a multiple of 4
+    big = ctx.create_frame(w, h)
+    mv_in_big = capi.Context.wrap(big.data, w, h, capi.FORMAT_MV_S8X2, pitch=w * 2)  # vectors in the first half of `big`
+    empty = capi.Frame()
+    B = ctypes.byref
+
+    def single(a, b, v, out, t=0.5, ms=48):
+        return lib.lfg_interpolate_compensated(ctx.h, a and B(a), b and B(b), v and B(v), out and B(out), t, ms)
+
+    bad = [
+        single(None, c, m, o), single(p, c, None, o), single(p, c, m, None), single(empty, c, m, o),
+        single(p, c, p, o),                      # mv of the wrong format
+        single(p, m, m, o),                      # curr of the wrong format
+        single(p, c, m, small), single(p, c, small_mv, o),
+        single(odd, c, m, o), single(p, odd, m, o),
+        single(p, c, m, p), single(p, c, m, c), single(p, c, mv_in_big, big),       # the output overlaps an input
+        single(p, c, m, o, float("nan")), single(p, c, m, o, float("inf")), single(p, c, m, o, -0.01), single(p, c, m, o, 1.01),
+        single(p, c, m, o, 0.5, -1), single(p, c, m, o, 0.5, 1021),
+    ]
+
+    def multi(outs, factors, count=None, ms=48):
+        po = (capi._FP * len(outs))(*[ctypes.pointer(f) for f in outs])
+        pf = (ctypes.c_float * len(factors))(*factors)
+        return lib.lfg_interpolate_compensated_multi(ctx.h, B(p), B(c), B(m), po, pf, len(outs) if count is None else count, ms)
+
+    bad += [
+        multi([o, o], [0.25, 0.5]),              # two outputs alias each other
+        multi([o], [0.5], count=0), multi([o] * 17, [0.5] * 17),
+        multi([o, o2], [0.5, float("nan")]), multi([o, o2], [0.5, 0.5], ms=2000),
+        multi([o, c], [0.5, 0.5]),
+    ]
+    assert all(rc == -1 for rc in bad), bad                          # LFG_ERR_INVALID
+    assert lib.lfg_set_interpolator(ctx.h, 2, 48) == -1
+    assert lib.lfg_set_interpolator(ctx.h, 1, 1021) == -1
+    assert lib.lfg_set_interpolator(ctx.h, 1, -1) == -1
+    assert lib.lfg_last_error(ctx.h).decode()
+    ctx.sync()
+    assert (ctx.download(o) == pattern).all() and (ctx.download(o2) == pattern).all()
+    # the shader path is still the default: lfg_interpolate_frames after the failed settings equals motion + interpolate
+    ref = ctx.create_frame(w, h)
+    ctx.interpolate_frames(p, c, o, 0.5)
+    ctx.motion(p, c, m)
+    ctx.interpolate(p, c, m, ref, 0.5)
+    assert (ctx.download(o) == ctx.download(ref)).all()
+    for f in (p, c, m, o, o2, small, small_mv, wide, big, ref):
+        ctx.destroy_frame(f)
+
+
+def test_three_lanes_equal_one_lane(ctx):
+    sizes = [(200, 120), (96, 64), (200, 120), (130, 90), (96, 64), (300, 170)]
+    cases = [case(ctx, "random" if i % 2 else "piecewise", w, h, 60 + i) for i, (w, h) in enumerate(sizes)]
+    alone = [run(ctx, a, b, v, 0.5, 1020) for a, b, v in cases]
+    ctx.lanes(3)
+    try:
+        frames = []
+        for i, (a, b, v) in enumerate(cases):
+            ctx.lane_select(i % 3)
+            h, w = a.shape[:2]
+            p, c, m = ctx.frame_from(a), ctx.frame_from(b), ctx.frame_from(v, capi.FORMAT_MV_S8X2)
+            o = ctx.create_frame(w, h)
+            ctx.interpolate_compensated(p, c, m, o, 0.5, 1020)
+            frames.append((p, c, m, o))
+        ctx.sync()
+        for fs, want in zip(frames, alone):
+            assert (ctx.download(fs[3]) == want).all()
+            for f in fs:
+                ctx.destroy_frame(f)
+    finally:
+        ctx.lane_select(0)
+        ctx.lanes(1)
+
+
+def test_host_compensated_stream_matches_capi(tmp_path):
+    if not os.path.exists(HOST):
+        import __graft_entry__ as entry
+        entry.build()
+    w, h, n = 1920, 1080, 3
+    frames = [synth.make_prev(w, h)]
+    for k in range(1, n):
+        frames.append(synth.translate(frames[-1], (12, -6), synth.BASE_SEED + k))
+    src = tmp_path / "in.rgba"
+    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
+    out = tmp_path / "out.rgba"
+    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
+                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended",
+                        "--interpolator", "compensated"],
+                       capture_output=True, text=True, timeout=300, check=True)
+    info = json.loads(p.stdout.strip().splitlines()[-1])
+    assert info["presented"] == 2 * n - 1
+    got = np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+    with capi.Context(0) as c:
+        c.set_semantics(capi.SEMANTICS_INTENDED)
+        ins = [c.frame_from(f) for f in frames]
+        ups = [c.create_frame(w, h) for _ in frames]
+        for i, u in zip(ins, ups):
+            c.scale(i, u)
+        m = c.create_frame(w, h, capi.FORMAT_MV_S8X2)
+        o = c.create_frame(w, h)
+        want = [c.download(ups[0])]
+        for k in range(1, n):
+            c.motion(ups[k - 1], ups[k], m)
+            c.interpolate_compensated(ups[k - 1], ups[k], m, o, 0.5, 48)
+            want += [c.download(o), c.download(ups[k])]
+    for k, (g, e) in enumerate(zip(got, want)):
+        assert (g == e).all(), k
