@@ -369,6 +369,35 @@ int  lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, 
 typedef enum lfg_interpolator { LFG_INTERPOLATOR_SHADER = 0, LFG_INTERPOLATOR_COMPENSATED = 1 } lfg_interpolator;
 int  lfg_set_interpolator(lfg_context *ctx, int interpolator, int match_sad);
 
+/* Per-pixel vector refinement, opt-in, between motion estimation and interpolation.  No reference counterpart.  Both
+ * estimators give each pixel the vector of the 8 x 8 block around it, so near a moving edge a band of up to ~4 px takes the
+ * other side's vector; this picks, for each pixel, the nearby vector that fits a small window around that pixel best.
+ * Integer arithmetic only; it does not depend on lfg_set_semantics.
+ *   Inputs: prev, curr RGBA8 and mv_in, mv_out LFG_FORMAT_MV_S8X2, all W x H; mv_in may hold any byte values;
+ *   0 <= radius <= 2.
+ *   Candidates of pixel q: mv_in(q + o) for o = (0, 0) and o = (a s, b s), a, b in {-1, 0, 1}, (a, b) != (0, 0), s in {4, 8}:
+ *   17 positions.  A position outside the image gives no candidate; mv_in(q) always is one.
+ *   Cost of candidate v at q: the sum over texels r of the (2 radius + 1)^2 window centred on q, and over the four channels,
+ *   of |curr(r)_c - prev(r + v)_c|; texels r outside the image are skipped, prev outside the image reads as 0 (the
+ *   conventions of lfg_motion_pyramid's cost and of lfg_interpolate_compensated's match gate).
+ *   mv_out(q) = the candidate with the smallest key (cost, vx^2 + vy^2, vy, vx), lfg_motion_pyramid's tie order.  The order
+ *   is total, so neither the order of evaluation nor any tiling changes a result.
+ * Hence: where all 17 candidates are equal (a uniform field, such as any pan) mv_out = mv_in, and every output vector is one
+ * of its pixel's candidates.
+ * Frames: 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4), 2-byte aligned mv; mv_out must not overlap any input
+ * (every output depends on its neighbours' inputs: the call cannot run in place).  Any violation, and a radius outside
+ * [0, 2], returns LFG_ERR_INVALID before anything is enqueued.  One launch on the selected lane; keeps no device memory;
+ * timed under LFG_STAGE_MOTION. */
+int  lfg_motion_refine(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv_in,
+                       lfg_frame *mv_out, int radius);
+/* Refinement in lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   radius = -1 (default): off; every path as before;
+ *   radius = 0 .. 2: the selected estimator (lfg_set_motion_estimator) into the lane's temporary, lfg_motion_refine with this
+ *       radius into a second per-lane temporary (W x H MV_S8X2, made on demand, freed by lfg_context_destroy), then the
+ *       selected interpolator (lfg_set_interpolator) on the refined vectors; lfg_set_fused_motion_interpolate does not apply.
+ * Any other radius: LFG_ERR_INVALID and no change. */
+int  lfg_set_vector_refinement(lfg_context *ctx, int radius);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

@@ -96,6 +96,8 @@ SIGNATURES = {
     "lfg_interpolate_compensated": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
     "lfg_interpolate_compensated_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
     "lfg_set_interpolator": (_i, [_vp, _i, _i]),
+    "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
+    "lfg_set_vector_refinement": (_i, [_vp, _i]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
     "lfg_mv_export_rgba32f": (_i, [_vp, _FP, _vp]),
@@ -401,6 +403,17 @@ class Context:
     def set_interpolator(self, interpolator: int, match_sad: int = DEFAULT_MATCH_SAD):
         """INTERPOLATOR_SHADER (default) or INTERPOLATOR_COMPENSATED for interpolate_frames[_multi]."""
         self._check(self.lib.lfg_set_interpolator(self.h, int(interpolator), int(match_sad)), "lfg_set_interpolator")
+
+    def motion_refine(self, prev: Frame, curr: Frame, mv_in: Frame, mv_out: Frame, radius: int = 1):
+        """Per-pixel vector refinement (lfg_motion_refine): each pixel takes, of the vectors of mv_in at it and 4 or 8 px
+        around it, the one that fits its (2 radius + 1)^2 window best."""
+        self._check(self.lib.lfg_motion_refine(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv_in),
+                                               ctypes.byref(mv_out), int(radius)), "lfg_motion_refine")
+
+    def set_vector_refinement(self, radius: int):
+        """-1 (default: off) or 0..2: lfg_motion_refine with that radius between the estimator and the interpolator of
+        interpolate_frames[_multi]."""
+        self._check(self.lib.lfg_set_vector_refinement(self.h, int(radius)), "lfg_set_vector_refinement")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -457,6 +457,7 @@ void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
     if (l.mv_tmp.data && l.mv_tmp.owned) (void)hipFree(l.mv_tmp.data);
+    if (l.mv_refined.data && l.mv_refined.owned) (void)hipFree(l.mv_refined.data);
     if (l.mid_tmp.data && l.mid_tmp.owned) (void)hipFree(l.mid_tmp.data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
@@ -1097,6 +1098,23 @@ LFG_EXPORT int lfg_interpolate(lfg_context *ctx, const lfg_frame *prev, const lf
     return LFG_OK;
 }
 
+namespace {
+
+// lfg_set_vector_refinement: lfg_motion_refine of the estimator's vectors `mv` into the lane's second temporary, made for
+// this frame size on demand; *refined is that temporary.
+int refine_stage(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_frame **refined) {
+    lfg_frame &r = ctx->cur().mv_refined;
+    if (!r.data || r.width != curr->width || r.height != curr->height) {
+        lfg_frame_destroy(ctx, &r);
+        int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &r);
+        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create refined motion vectors frame");
+    }
+    *refined = &r;
+    return lfg_motion_refine(ctx, prev, curr, mv, &r, ctx->refine_radius);
+}
+
+}  // namespace
+
 LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                       lfg_frame *out, float factor) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: NULL argument");
@@ -1105,6 +1123,17 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
         lfg_frame_destroy(ctx, &mv);
         int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
         if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
+    }
+    if (ctx->refine_radius >= 0) {                  // estimator, refinement, interpolator: three stages (no fused kernel)
+        int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
+                                                         : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);
+        if (rc != LFG_OK) return rc;
+        const lfg_frame *refined = nullptr;
+        rc = refine_stage(ctx, prev, curr, &mv, &refined);
+        if (rc != LFG_OK) return rc;
+        return ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED
+                   ? lfg_interpolate_compensated(ctx, prev, curr, refined, out, factor, ctx->match_sad)
+                   : lfg_interpolate(ctx, prev, curr, refined, out, factor);
     }
     if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {      // two stages under either estimator (no fused kernel)
         int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
@@ -1179,9 +1208,14 @@ LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *p
     int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
                                                      : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);   // frame_manager.cpp:332-333
     if (rc != LFG_OK) return rc;
+    const lfg_frame *vectors = &mv;
+    if (ctx->refine_radius >= 0) {
+        rc = refine_stage(ctx, prev, curr, &mv, &vectors);
+        if (rc != LFG_OK) return rc;
+    }
     if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
-        return lfg_interpolate_compensated_multi(ctx, prev, curr, &mv, outs, factors, count, ctx->match_sad);
-    return lfg_interpolate_multi(ctx, prev, curr, &mv, outs, factors, count);
+        return lfg_interpolate_compensated_multi(ctx, prev, curr, vectors, outs, factors, count, ctx->match_sad);
+    return lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count);
 }
 
 // ---- motion-compensated interpolation (interpolate_mc.hip)
@@ -1258,6 +1292,36 @@ LFG_EXPORT int lfg_set_interpolator(lfg_context *ctx, int interpolator, int matc
     if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, "lfg_set_interpolator: match_sad must be in [0, 1020]");
     ctx->interpolator = interpolator;
     ctx->match_sad = match_sad;
+    return LFG_OK;
+}
+
+// ---- per-pixel vector refinement (motion_refine.hip)
+
+LFG_EXPORT int lfg_motion_refine(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv_in,
+                                 lfg_frame *mv_out, int radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) ||
+        !frame_ok(mv_in, LFG_FORMAT_MV_S8X2) || !frame_ok(mv_out, LFG_FORMAT_MV_S8X2))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_refine: prev/curr must be RGBA8 and mv_in/mv_out MV_S8X2, all non-empty");
+    if (!same_size(prev, curr) || !same_size(curr, mv_in) || !same_size(curr, mv_out))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_refine: prev, curr, mv_in and mv_out differ in size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u ||
+        (mv_in->pitch | mv_out->pitch) % 2u || ((uintptr_t)mv_in->data | (uintptr_t)mv_out->data) % 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_refine: RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
+    if (frames_overlap(mv_out, prev) || frames_overlap(mv_out, curr) || frames_overlap(mv_out, mv_in))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_refine: mv_out overlaps an input (it cannot run in place)");
+    if (radius < 0 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_refine: radius must be in [0, 2]");
+    StageTimer timer(ctx, LFG_STAGE_MOTION);
+    hipError_t e = lfg::launch_motion_refine(ctx->cur().stream, *prev, *curr, *mv_in, *mv_out, radius);
+    if (e != hipSuccess) return fail_hip(ctx, e, "motion refine kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_set_vector_refinement(lfg_context *ctx, int radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (radius < -1 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_set_vector_refinement: radius must be -1 (off) or in [0, 2]");
+    ctx->refine_radius = radius;
     return LFG_OK;
 }
 

@@ -154,6 +154,7 @@ struct ProfileSlot {
 struct lfg_lane_state {
     hipStream_t own_stream = nullptr, stream = nullptr;
     lfg_frame mv_tmp{};                        // temporary of lfg_interpolate_frames
+    lfg_frame mv_refined{};                    // ... and its refined vectors (lfg_set_vector_refinement), made on demand
     lfg_frame mid_tmp{};                       // temporary of lfg_interpolate_scale where the fused kernel does not apply
     // prefiltered motion path: scratch for one frame size, grown on demand
     uint8_t *motion_ws = nullptr;
@@ -193,6 +194,7 @@ struct lfg_context {
     int estimator = 0;                         // lfg_interpolate_frames[_multi]: LFG_ESTIMATOR_FULL_SEARCH / _PYRAMID (lfg_set_motion_estimator)
     int interpolator = 0;                      // lfg_interpolate_frames[_multi]: LFG_INTERPOLATOR_SHADER / _COMPENSATED (lfg_set_interpolator)
     int match_sad = 48;                        // ... and the compensated interpolator's match gate
+    int refine_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_refine's radius, -1 = off (lfg_set_vector_refinement)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -295,6 +297,9 @@ hipError_t launch_motion_pyramid(hipStream_t s, const lfg_frame &prev, const lfg
 // Motion-compensated interpolation (interpolate_mc.hip): clears `keys` (W * H words), projects, interpolates; one factor.
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                           const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
+// Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
+hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
+                                const lfg_frame &mvOut, int radius);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

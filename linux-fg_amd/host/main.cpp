@@ -37,6 +37,8 @@ static void PrintUsage() {
               << "                           written; intended: vectors displace by pixels -- what vectors longer than 1 px need)\n"
               << "  --interpolator shader|compensated  Interpolation of the generated frames (default shader: the reference's;\n"
               << "                           compensated: vectors projected to the frame's time, holes filled; wants --semantics intended)\n"
+              << "  --refine-vectors R       Per-pixel vector refinement between motion and interpolation (default -1: off;\n"
+              << "                           0..2: each pixel takes the nearby vector that fits its (2R+1)^2 window best)\n"
               << "  --frames N               Number of input frames to process (default: 10)\n"
               << "  --device N               HIP device ordinal (default: 0)\n"
               << "  --dump-dir DIR           Write every presented frame to DIR as raw RGBA8\n"
@@ -61,7 +63,7 @@ int main(int argc, char* argv[]) {
     int frames = 10, device = 0;
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
-    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER;
+    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false;
@@ -108,6 +110,12 @@ int main(int argc, char* argv[]) {
             else if (strcmp(m, "compensated") == 0) interpolator = LFG_INTERPOLATOR_COMPENSATED;
             else { LOG_ERROR("Invalid --interpolator (shader|compensated)"); return 1; }
         }
+        else if (strcmp(argv[i], "--refine-vectors") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long r = strtol(argv[++i], &end, 10);
+            if (!end || *end != '\0' || r < -1 || r > 2) { LOG_ERROR("Invalid --refine-vectors (-1, 0, 1 or 2)"); return 1; }
+            refineRadius = (int)r;
+        }
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--device") == 0 && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--dump-dir") == 0 && i + 1 < argc) dumpDir = argv[++i];
@@ -143,7 +151,8 @@ int main(int argc, char* argv[]) {
     // (library settings, like --in-flight: ScalerConfig keeps the reference's fields)
     if (lfg_set_semantics(HipContext::Get().GetDevice(), semantics) != LFG_OK ||
         lfg_set_motion_estimator(HipContext::Get().GetDevice(), estimator) != LFG_OK ||
-        lfg_set_interpolator(HipContext::Get().GetDevice(), interpolator, 48) != LFG_OK) {
+        lfg_set_interpolator(HipContext::Get().GetDevice(), interpolator, 48) != LFG_OK ||
+        lfg_set_vector_refinement(HipContext::Get().GetDevice(), refineRadius) != LFG_OK) {
         LOG_ERROR("Failed to set the motion options: ", lfg_last_error(HipContext::Get().GetDevice()));
         HipContext::Get().Cleanup();
         return 1;
