@@ -5,7 +5,14 @@
  * Frames are tight: prev / curr / out RGBA8 rows of W * 4 bytes, mv int8 (x, y) pairs in rows of W * 2 bytes.
  *
  * mc_project: the key image K (W * H words) of one factor.  mc_sample: output pixels [x0, x1) x [y0, y1) from K, written to
- * out in rows of (x1 - x0) pixels. */
+ * out in rows of (x1 - x0) pixels.
+ *
+ * Mutants, for the test of the tests alone (tests/test_mc_model.py: a set of factors must tell each of them from the model);
+ * with no such macro defined this file is the model:
+ *   MC_MUTANT_C_FROM_P      the curr sample position as C = P - u instead of C = (x + 0.5) - u * s;
+ *   MC_MUTANT_CEIL_PROJECT  the projection as v - ceil(v * t - 0.5) instead of floor(v * s + 0.5);
+ *   MC_MUTANT_HALF_LAST     the curr sample position as C = (x - u * s) + 0.5: the half pixel added last.
+ * All are exact rewrites in real arithmetic and at every factor where the fp32 products are exact. */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -52,7 +59,12 @@ void mc_project(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, int 
         for (int qx = 0; qx < W; ++qx) {
             if (!matched(prev, curr, mv, W, H, qx, qy, match_sad)) continue;
             const int vx = mv[((size_t)qy * W + qx) * 2], vy = mv[((size_t)qy * W + qx) * 2 + 1];
+#ifdef MC_MUTANT_CEIL_PROJECT
+            const int dx = vx - (int)ceilf((float)vx * t - 0.5f), dy = vy - (int)ceilf((float)vy * t - 0.5f);
+            (void)s;
+#else
             const int dx = (int)floorf((float)vx * s + 0.5f), dy = (int)floorf((float)vy * s + 0.5f);
+#endif
             const int x = qx + dx, y = qy + dy;
             if (x < 0 || x >= W || y < 0 || y >= H) continue;
             const uint32_t key = ((uint32_t)(65535 - (vx * vx + vy * vy)) << 16) | ((uint32_t)(vy + 128) << 8) | (uint32_t)(vx + 128);
@@ -119,7 +131,14 @@ void mc_sample(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, const
             if (hole) fill_vector(K, W, H, x, y, &ux, &uy);
             else decode(key, &ux, &uy);
             const float Px = ((float)x + 0.5f) + (float)ux * t, Py = ((float)y + 0.5f) + (float)uy * t;
+#if defined(MC_MUTANT_C_FROM_P)
+            const float Cx = Px - (float)ux, Cy = Py - (float)uy;
+            (void)s;
+#elif defined(MC_MUTANT_HALF_LAST)
+            const float Cx = ((float)x - (float)ux * s) + 0.5f, Cy = ((float)y - (float)uy * s) + 0.5f;
+#else
             const float Cx = ((float)x + 0.5f) - (float)ux * s, Cy = ((float)y + 0.5f) - (float)uy * s;
+#endif
             const vec4 Pv = bilinear_px(prev, W, H, Px, Py), Cv = bilinear_px(curr, W, H, Cx, Cy);
             if (hole) {
                 const int cx = clampi((int)floorf(Cx), 0, W - 1), cy = clampi((int)floorf(Cy), 0, H - 1);

@@ -17,20 +17,25 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "mc_model.c")
-_lib = None
+_libs = {}
 
 HOLE = 0xFFFFFFFF
 DEFAULT_MATCH_SAD = 48
+MUTANTS = ("C_FROM_P", "CEIL_PROJECT", "HALF_LAST")     # mc_model.c: rewrites that a test's factors must tell from the model
 
 
-def _load():
-    global _lib
-    if _lib is None:
+def _load(mutant=None):
+    """The model, or with mutant = one of MUTANTS the model built with -DMC_MUTANT_<mutant>, under a cache name of its own."""
+    if mutant not in _libs:
+        assert mutant is None or mutant in MUTANTS, mutant
         src = open(_SRC, "rb").read()
-        out = os.path.join(tempfile.gettempdir(), f"lfg_mc_model_{os.getuid()}_{hashlib.sha1(src).hexdigest()[:12]}.so")
+        tag = hashlib.sha1(src).hexdigest()[:12] + (f"_{mutant.lower()}" if mutant else "")
+        out = os.path.join(tempfile.gettempdir(), f"lfg_mc_model_{os.getuid()}_{tag}.so")
         if not os.path.exists(out):
             tmp = out + f".{os.getpid()}"
-            subprocess.check_call([os.environ.get("CC", "cc"), "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", tmp, _SRC, "-lm"])
+            define = [f"-DMC_MUTANT_{mutant}"] if mutant else []
+            subprocess.check_call([os.environ.get("CC", "cc"), "-O2", "-ffp-contract=off", "-shared", "-fPIC"] + define +
+                                  ["-o", tmp, _SRC, "-lm"])
             os.replace(tmp, out)
         L = ctypes.CDLL(out)
         vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
@@ -38,8 +43,8 @@ def _load():
         L.mc_project.restype = None
         L.mc_sample.argtypes = [vp, vp, vp, vp, i, i, f, i, i, i, i, i, vp]
         L.mc_sample.restype = None
-        _lib = L
-    return _lib
+        _libs[mutant] = L
+    return _libs[mutant]
 
 
 def _ptr(a: np.ndarray):
@@ -59,23 +64,24 @@ def key(vx: int, vy: int) -> int:
     return ((65535 - (vx * vx + vy * vy)) << 16) | ((vy + 128) << 8) | (vx + 128)
 
 
-def keys(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, t: float, match_sad: int = DEFAULT_MATCH_SAD) -> np.ndarray:
+def keys(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, t: float, match_sad: int = DEFAULT_MATCH_SAD,
+         mutant=None) -> np.ndarray:
     """(H, W) uint32: the projected key of every pixel, HOLE where nothing lands."""
     prev, curr, mv = _inputs(prev, curr, mv)
     H, W = prev.shape[:2]
     K = np.empty((H, W), np.uint32)
-    _load().mc_project(_ptr(prev), _ptr(curr), _ptr(mv), W, H, float(t), int(match_sad), _ptr(K))
+    _load(mutant).mc_project(_ptr(prev), _ptr(curr), _ptr(mv), W, H, float(t), int(match_sad), _ptr(K))
     return K
 
 
 def interpolate_compensated(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, t: float,
-                            match_sad: int = DEFAULT_MATCH_SAD, roi=None) -> np.ndarray:
+                            match_sad: int = DEFAULT_MATCH_SAD, roi=None, mutant=None) -> np.ndarray:
     """(H, W, 4) uint8 of the whole frame, or (h, w, 4) of roi = (x, y, w, h)."""
-    return sample(prev, curr, mv, keys(prev, curr, mv, t, match_sad), t, match_sad, roi)
+    return sample(prev, curr, mv, keys(prev, curr, mv, t, match_sad, mutant), t, match_sad, roi, mutant)
 
 
 def sample(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, K: np.ndarray, t: float,
-           match_sad: int = DEFAULT_MATCH_SAD, roi=None) -> np.ndarray:
+           match_sad: int = DEFAULT_MATCH_SAD, roi=None, mutant=None) -> np.ndarray:
     """The sampling step alone, from a key image K (H, W) uint32 given by the caller: lets a test place keys and holes."""
     prev, curr, mv = _inputs(prev, curr, mv)
     H, W = prev.shape[:2]
@@ -83,7 +89,7 @@ def sample(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, K: np.ndarray, t:
     assert K.shape == (H, W)
     x, y, w, h = roi if roi is not None else (0, 0, W, H)
     out = np.empty((h, w, 4), np.uint8)
-    _load().mc_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(t), int(match_sad), x, y, x + w, y + h, _ptr(out))
+    _load(mutant).mc_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(t), int(match_sad), x, y, x + w, y + h, _ptr(out))
     return out
 
 

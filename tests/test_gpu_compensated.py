@@ -1,6 +1,6 @@
 """lfg_interpolate_compensated on the GPU against the CPU model (tests/mc_model.py), byte for byte; what it gets right that
-the shader's modes do not; the interpolator switch of lfg_interpolate_frames[_multi]; argument checks; lanes; and the host's
---interpolator option."""
+the shader's modes do not; the interpolator switch of lfg_interpolate_frames[_multi]; argument checks; lanes; the host's
+--interpolator option; and the hand-made cases of test_mc_model.py that need no hand-placed key image."""
 import ctypes
 import json
 import os
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from linux_fg_amd import capi, synth
+from tests import cases
 from tests import mc_model as mc
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
 
 SIZES = [(1, 1), (7, 5), (33, 17), (64, 64), (257, 131)]
-FACTORS = [0.0, 0.25, 0.5, 0.75, 1.0]
+# Dyadic factors make every product of the position arithmetic exact in fp32; the inexact ones are those that tell the model's
+# mutants from the model (test_mc_model.py), and the last two approach t = 1 and t = 0 without reaching them.
+FACTORS = cases.DYADIC_FACTORS + cases.INEXACT_FACTORS + cases.LIMIT_FACTORS
 MATCH = [0, 48, 1020]
 
 
@@ -48,25 +51,12 @@ def gpu_vectors(ctx, prev, curr, estimator):
 
 
 def case(ctx, field, w, h, seed):
-    """(prev, curr, mv int8) for one kind of vector field."""
-    rng = np.random.default_rng(seed)
+    """(prev, curr, mv int8) for one kind of vector field: an estimator's on the GPU, or one of cases.field."""
     if field in ("motion", "pyramid"):
         prev = synth.make_prev(w, h, synth.BASE_SEED + seed)
         curr = synth.translate(prev, (5, -3) if field == "motion" else (-30, 18), synth.BASE_SEED + seed)
         return prev, curr, gpu_vectors(ctx, prev, curr, "full" if field == "motion" else "pyramid")
-    prev = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
-    mv = np.zeros((h, w, 2), np.int8)
-    if field == "uniform":
-        mv[...] = rng.integers(-20, 21, 2)
-        curr = synth.translate(prev, tuple(-int(v) for v in mv[0, 0]), synth.BASE_SEED + seed)
-    elif field == "piecewise":            # four quadrants with their own vectors: collisions along the seams
-        vs = rng.integers(-12, 13, (4, 2))
-        mv[: h // 2, : w // 2], mv[: h // 2, w // 2:], mv[h // 2:, : w // 2], mv[h // 2:, w // 2:] = vs
-        curr = np.clip(prev.astype(np.int16) + rng.integers(-6, 7, prev.shape), 0, 255).astype(np.uint8)
-    else:                                 # dense random over the full byte range: holes and conflicts everywhere
-        mv = rng.integers(-128, 128, (h, w, 2)).astype(np.int8)
-        curr = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
-    return prev, curr, mv
+    return cases.field(field, w, h, seed)
 
 
 def run(ctx, prev, curr, mv, t, match_sad):
@@ -101,7 +91,8 @@ def test_every_pixel_equals_the_model(ctx, field):
 def test_full_frames(ctx, w, h):
     for field in ("piecewise", "random", "motion", "pyramid"):
         prev, curr, mv = case(ctx, field, w, h, 3)
-        for t, ms in ((0.25, 48), (0.5, 1020), (0.75, 0)):
+        inexact = list(zip(cases.INEXACT_FACTORS + cases.LIMIT_FACTORS, (1020, 48, 0, 1020, 48, 1020)))
+        for t, ms in [(0.25, 48), (0.5, 1020), (0.75, 0)] + inexact:
             got = run(ctx, prev, curr, mv, t, ms)
             want = mc.interpolate_compensated(prev, curr, mv, t, ms)
             assert (got == want).all(), f"{w}x{h} {field} t={t}: {first_bad(got, want)}"
@@ -112,7 +103,8 @@ def test_rois_of_4k_and_8k(ctx, w, h):
     rng = np.random.default_rng(w)
     rois = [(0, 0, 64, 64), (w - 64, h - 64, 64, 64)] + [(int(rng.integers(0, w - 64)), int(rng.integers(0, h - 64)), 64, 64)
                                                          for _ in range(6)]
-    for field, t, ms in (("random", 0.5, 1020), ("motion", 0.25, 48)):
+    inexact = [("random", t, 1020) for t in cases.INEXACT_FACTORS + cases.LIMIT_FACTORS] if w == 3840 else []
+    for field, t, ms in [("random", 0.5, 1020), ("motion", 0.25, 48)] + inexact:
         prev, curr, mv = case(ctx, field, w, h, 9)
         got = run(ctx, prev, curr, mv, t, ms)
         for x, y, rw, rh in rois:
@@ -137,7 +129,8 @@ def test_padded_pitch(ctx):
     bm, m = pitched(ctx, mv, 7, capi.FORMAT_MV_S8X2)
     bo, o = pitched(ctx, np.zeros((h, w, 4), np.uint8), 9)
     try:
-        for t, ms in ((0.5, 1020), (0.25, 0)):
+        inexact = list(zip(cases.INEXACT_FACTORS + cases.LIMIT_FACTORS, (1020, 0, 48, 1020, 1020, 0)))
+        for t, ms in [(0.5, 1020), (0.25, 0)] + inexact:
             ctx.interpolate_compensated(p, c, m, o, t, ms)
             raw = ctx.download(bo)
             assert (raw[:, w:] == 0x5A).all()                     # the padding is not written
@@ -151,7 +144,7 @@ def test_padded_pitch(ctx):
 def test_multi_equals_single_calls(ctx):
     w, h = 640, 360
     prev, curr, mv = case(ctx, "piecewise", w, h, 23)
-    factors = [0.25, 0.5, 0.75, 1.0, 0.0]
+    factors = [0.25, 0.5, 0.75, 1.0, 0.0] + cases.INEXACT_FACTORS + cases.LIMIT_FACTORS
     p, c, m = ctx.frame_from(prev), ctx.frame_from(curr), ctx.frame_from(mv, capi.FORMAT_MV_S8X2)
     outs = [ctx.create_frame(w, h) for _ in factors]
     try:
@@ -160,9 +153,66 @@ def test_multi_equals_single_calls(ctx):
         for t, got in zip(factors, multi):
             ctx.interpolate_compensated(p, c, m, outs[0], t, 48)
             assert (got == ctx.download(outs[0])).all(), t
+            if t in cases.INEXACT_FACTORS + cases.LIMIT_FACTORS:
+                assert (got == mc.interpolate_compensated(prev, curr, mv, t, 48)).all(), t
     finally:
         for f in [p, c, m] + outs:
             ctx.destroy_frame(f)
+
+
+# ---- the hand-made cases of test_mc_model.py (tests/cases.py), through the GPU call
+
+def test_hand_made_cases(ctx):
+    """Each input at every factor equals the model, and at t = 0.5 the literal value that the CPU test states.  The cases on
+    flat black frames generate black whatever is projected, so the two that are about the projection alone also run on
+    textured frames with match_sad 1020, where the model's key image is the same (asserted here) and shows in the bytes."""
+    def check(prev, curr, mv, ms, name):
+        outs = {}
+        for t in FACTORS:
+            outs[t] = run(ctx, prev, curr, mv, t, ms)
+            want = mc.interpolate_compensated(prev, curr, mv, t, ms)
+            assert (outs[t] == want).all(), f"{name} t={t} match_sad={ms}: {first_bad(outs[t], want)}"
+        assert (outs[1.0] == curr).all(), name                         # the header: t = 1 gives curr
+        return outs[0.5]
+
+    prev, curr, mv, winners = cases.mc_collision()
+    K = mc.keys(prev, curr, mv, 0.5, 0)
+    assert all(K[y, x] == mc.key(*v) for (x, y), v in winners.items())
+    assert (check(prev, curr, mv, 0, "collision") == 0).all()
+    prev, curr, mv, _ = cases.mc_collision(textured_frames=True)
+    assert (mc.keys(prev, curr, mv, 0.5, 1020) == K).all()
+    got = check(prev, curr, mv, 1020, "collision, textured")
+    for (x, y), v in winners.items():                                # the winner's vector, not a loser's, samples the pixel
+        K1 = np.full((8, 8), mc.key(*v), np.uint32)
+        assert (got[y, x] == mc.sample(prev, curr, mv, K1, 0.5, 1020)[y, x]).all(), (x, y)
+
+    prev, curr, mv = cases.mc_unmatched_source()
+    for ms in (199, 200):
+        check(prev, curr, mv, ms, "unmatched source")
+
+    prev, curr, mv = cases.mc_projection_outside()
+    assert (check(prev, curr, mv, 0, "projection outside") == 0).all()
+    prev, curr, mv = cases.mc_projection_outside(textured_frames=True)
+    assert (mc.keys(prev, curr, mv, 0.5, 1020) == mc.keys(*cases.mc_projection_outside(), 0.5, 0)).all()
+    check(prev, curr, mv, 1020, "projection outside, textured")
+
+    prev, curr, mv, obj = cases.mc_revealed_and_covered()
+    got = check(prev, curr, mv, 0, "revealed and covered")
+    assert (got[2, 5] == obj).all()                                   # half way
+    assert (got[2, 4] == curr[2, 4]).all() and (got[2, 6] == prev[2, 6]).all()
+    want = np.zeros_like(prev)
+    want[2, 5] = obj
+    assert (got == want).all()
+
+    prev, curr, mv = cases.mc_row_projected_to_the_top()
+    got = check(prev, curr, mv, 1020, "row projected to the top")
+    assert (got[1] == curr[3]).all()
+
+    for w, h, seed in ((1, 1, 1), (7, 5, 2), (50, 40, 3)):           # t = 1 gives curr for any vectors and match_sad
+        prev, curr = cases.textured(w, h, seed), cases.textured(w, h, seed + 100)
+        mv = np.random.default_rng(seed).integers(-128, 128, (h, w, 2)).astype(np.int8)
+        for ms in (0, 48, 1020):
+            assert (run(ctx, prev, curr, mv, 1.0, ms) == curr).all(), (w, h, ms)
 
 
 # ---- what the shader's modes do not do: content at time t where it is

@@ -1,5 +1,6 @@
 """lfg_motion_pyramid on the GPU against the CPU model (tests/pyramid_model.py), byte for byte; its argument checks; the
-estimator switch of lfg_interpolate_frames[_multi]; lanes; and the host's --motion / --semantics options."""
+estimator switch of lfg_interpolate_frames[_multi]; lanes; the host's --motion / --semantics options; and the tie case of
+test_pyramid_model.py."""
 import ctypes
 import json
 import os
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 from linux_fg_amd import capi, synth
+from tests import cases
 from tests import pyramid_model as pm
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +74,19 @@ def test_every_pixel_equals_the_model(ctx, params, kind):
         want = pm.motion_pyramid(prev, curr, *params)
         bad = np.argwhere((got != want).any(-1))
         assert bad.size == 0, f"{w}x{h} {params} {kind}: {len(bad)} pixels differ, first {bad[:3].tolist()}"
+
+
+@pytest.mark.parametrize("axis", [0, 1])
+def test_tie_between_equal_length_vectors(ctx, axis):
+    """test_pyramid_model.py's tie (tests/cases.py): v and -v match exactly; the smaller vy or, vy equal, the smaller vx wins.
+    With more levels the tie is decided on reduced images first: those run against the model as well."""
+    prev, curr, params, want = cases.pyramid_tie(axis)
+    got = run_pyramid(ctx, prev, curr, params)
+    assert (got == pm.motion_pyramid(prev, curr, *params)).all()
+    inner = got[12:-12, 12:-12].reshape(-1, 2)
+    assert (inner == np.array(want, np.int8)).all(), np.unique(inner, axis=0)
+    for other in PARAMS:
+        assert (run_pyramid(ctx, prev, curr, other) == pm.motion_pyramid(prev, curr, *other)).all(), other
 
 
 @pytest.mark.parametrize("params", [(2, 16, 2), (4, 7, 1)])

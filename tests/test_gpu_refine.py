@@ -1,6 +1,6 @@
 """lfg_motion_refine on the GPU against the CPU model (tests/refine_model.py), byte for byte; argument checks; lanes; the
-refinement switch of lfg_interpolate_frames[_multi]; the host's --refine-vectors; and what it is for: the halo of wrong
-vectors around moving edges."""
+refinement switch of lfg_interpolate_frames[_multi]; the host's --refine-vectors; the hand-made cases of
+test_refine_model.py; and what it is for: the halo of wrong vectors around moving edges."""
 import ctypes
 import json
 import os
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from linux_fg_amd import capi, synth
+from tests import cases
 from tests import mc_model as mc
 from tests import pyramid_model as pm
 from tests import refine_model as rm
@@ -98,6 +99,43 @@ def test_every_vector_equals_the_model(ctx, field):
             assert (got == want).all(), f"{w}x{h} {field} radius={radius}: {first_bad(got, want)}"
             if field == "uniform":
                 assert (got == mv).all()
+
+
+# ---- the hand-made cases of test_refine_model.py (tests/cases.py), through the GPU call: the model, and the literal value
+# that the CPU test states
+
+def vec(a, x, y):
+    return tuple(int(c) for c in a[y, x])
+
+
+@pytest.mark.parametrize("radius", RADII)
+def test_hand_made_cases(ctx, radius):
+    def check(prev, curr, mv, name):
+        got = run(ctx, prev, curr, mv, radius)
+        want = rm.refine(prev, curr, mv, radius)
+        assert (got == want).all(), f"{name} radius={radius}: {first_bad(got, want)}"
+        return got
+
+    for vectors, want in cases.REFINE_TIES:                       # all-zero frames: every cost ties
+        got = check(*cases.refine_tie_case(vectors), f"tie {vectors}")
+        assert vec(got, 8, 8) == want, vectors
+    got = check(*cases.refine_candidates_outside(), "candidates outside")     # 4 x 1: the neighbours lie outside
+    assert vec(got, 0, 0) == (2, 0) and vec(got, 1, 0) == (0, 0) and vec(got, 3, 0) == (0, 0)
+    got = check(*cases.refine_prev_outside_zero(), "prev outside reads 0")
+    for x, y in ((6, 6), (2, 6), (10, 6), (6, 2), (2, 2), (6, 10)):
+        assert vec(got, x, y) == (100, 0), (x, y)
+    assert vec(got, 0, 0) == (0, 0)
+    if radius >= 1:
+        for vertical in (True, False):
+            prev, curr, mv, truth = cases.refine_straight_edge(radius, vertical)
+            got = check(prev, curr, mv, f"straight edge vertical={vertical}")
+            assert (got == truth).all(), first_bad(got, truth)
+    if radius == 1:
+        got = check(*cases.refine_cost_before_length(), "cost before length")
+        assert vec(got, 12, 8) == (6, 2) and vec(got, 8, 8) == (6, 2) and vec(got, 16, 8) == (6, 2) and vec(got, 0, 0) == (0, 0)
+    prev, curr = cases.textured(1, 1, 50), cases.textured(1, 1, 51)
+    for v in ((0, 0), (-128, 127), (3, -7)):                      # a 1 x 1 frame keeps its vector
+        assert vec(check(prev, curr, np.array([[v]], np.int8), "1 x 1"), 0, 0) == v
 
 
 @pytest.mark.parametrize("w,h", [(3840, 2160), (7680, 4320)])

@@ -1,9 +1,12 @@
 """Known answers for the CPU model of lfg_interpolate_compensated (tests/mc_model.py): t = 1, an even pan, one hand-worked
-8 x 8 case per rule of the header's definition, and the moving square that the shader's intended mode gets wrong."""
+8 x 8 case per rule of the header's definition, and the moving square that the shader's intended mode gets wrong.  And the
+power of two sets that the GPU tests rely on (tests/cases.py): the inexact factors against the model's mutants, and the scene of
+the dispatch matrix against the settings."""
 import numpy as np
 import pytest
 
 from linux_fg_amd import synth
+from tests import cases
 from tests import mc_model as mc
 
 HOLE, key = mc.HOLE, mc.key
@@ -23,8 +26,7 @@ def mix(p, c, t):
     return unorm(p) * (np.float32(1.0) - t) + unorm(c) * t
 
 
-def textured(w, h, seed):
-    return np.random.default_rng(seed).integers(0, 256, (h, w, 4), dtype=np.uint8)
+textured = cases.textured
 
 
 def test_unorm_round_trip_is_exact():
@@ -65,29 +67,21 @@ def test_pan_with_estimated_vectors():
 
 # ---- hand-worked 8 x 8 cases.  At t = 0.5 a vector v projects by floor(v * 0.5 + 0.5), i.e. v / 2 for even v.
 
-def zeros():
-    """Flat black frames and zero vectors: every pixel matches, even at match_sad 0."""
-    return np.zeros((8, 8, 4), np.uint8), np.zeros((8, 8, 4), np.uint8), np.zeros((8, 8, 2), np.int8)
-
+# The inputs that need no hand-placed key image are built in tests/cases.py: test_gpu_compensated.py runs them on the GPU.
 
 def test_collision_longest_then_vy_then_vx():
-    prev, curr, mv = zeros()
-    mv[4, 5] = (-2, 0)          # -> (4, 4), |v|^2 = 4
-    mv[4, 6] = (-4, 0)          # -> (4, 4), |v|^2 = 16: wins (and over (4,4)'s own (0,0))
-    mv[2, 4] = (0, 2)           # -> (4, 3)
-    mv[4, 4] = (0, -2)          # -> (4, 3): the same |v|^2, the smaller vy wins
-    mv[6, 2] = (2, 0)           # -> (3, 6)
-    mv[6, 4] = (-2, 0)          # -> (3, 6): the same |v|^2 and vy, the smaller vx wins
+    prev, curr, mv, winners = cases.mc_collision()
+    assert winners == {(4, 4): (-4, 0), (4, 3): (0, -2), (3, 6): (-2, 0)}
     K = mc.keys(prev, curr, mv, 0.5, 0)
     assert K[4, 4] == key(-4, 0)
     assert K[3, 4] == key(0, -2)
     assert K[6, 3] == key(-2, 0)
+    prev, curr, mv, _ = cases.mc_collision(textured_frames=True)       # the same keys where every pixel matches by the gate
+    assert (mc.keys(prev, curr, mv, 0.5, 1020) == K).all()
 
 
 def test_unmatched_source_does_not_project():
-    prev, curr, mv = zeros()
-    curr[3, 3] = (200, 0, 0, 0)                          # against prev(5, 3) = 0: SAD 200
-    mv[3, 3] = (2, 0)                                    # -> (4, 3)
+    prev, curr, mv = cases.mc_unmatched_source()         # curr(3, 3) against prev(5, 3): SAD 200; (2, 0) -> (4, 3)
     K = mc.keys(prev, curr, mv, 0.5, 199)
     assert K[3, 4] == key(0, 0) and K[3, 3] == HOLE
     K = mc.keys(prev, curr, mv, 0.5, 200)
@@ -95,9 +89,7 @@ def test_unmatched_source_does_not_project():
 
 
 def test_projection_outside_the_image_is_dropped():
-    prev, curr, mv = zeros()
-    mv[0, 0] = (0, -2)                                   # -> (0, -1)
-    mv[7, 7] = (4, 0)                                    # -> (9, 7)
+    prev, curr, mv = cases.mc_projection_outside()       # (0, 0) -> (0, -1), (7, 7) -> (9, 7)
     K = mc.keys(prev, curr, mv, 0.5, 0)
     assert K[0, 0] == HOLE and K[7, 7] == HOLE
     assert (K == HOLE).sum() == 2 and (K[K != HOLE] == key(0, 0)).all()
@@ -140,11 +132,7 @@ def test_hole_with_nothing_within_16_gets_zero():
 
 
 def test_revealed_content_comes_from_curr_and_covered_from_prev():
-    prev, curr, mv = zeros()
-    obj = (200, 100, 50, 255)
-    prev[2, 4] = obj                                     # an object moves from (4, 2) to (6, 2): v(6, 2) = (-2, 0)
-    curr[2, 6] = obj
-    mv[2, 6] = (-2, 0)
+    prev, curr, mv, obj = cases.mc_revealed_and_covered()    # an object moves from (4, 2) to (6, 2): v(6, 2) = (-2, 0)
     K = mc.keys(prev, curr, mv, 0.5, 0)
     # (4, 2) is unmatched (curr 0 against prev obj) and (6, 2) moved away: two holes; the object lands on (5, 2)
     assert K[2, 5] == key(-2, 0) and K[2, 4] == HOLE and K[2, 6] == HOLE
@@ -169,17 +157,17 @@ def test_revealed_content_comes_from_curr_and_covered_from_prev():
 def test_one_sample_inside_and_one_outside():
     prev, curr, mv = textured_case((0, 0), 8, 8)
     K = np.full((8, 8), key(0, 0), np.uint32)
-    cases = {
+    wants = {
         (4, 0): prev[1, 3],                              # P = 1.5 + 2 = 3.5 inside, C = 1.5 - 2 < 0 outside: prev alone
         (-4, 0): curr[1, 3],                             # P = -0.5 outside, C = 3.5 inside: curr alone
         (4, -4): unorm_pack(mix(prev[0, 3], curr[3, 0], 0.5)),   # both outside: the blend of the clamped samples
     }
-    for u, want in cases.items():
+    for u, want in wants.items():
         K2 = K.copy()
         K2[1, 1] = key(*u)
         assert (mc.sample(prev, curr, mv, K2, 0.5, 1020)[1, 1] == want).all(), u
     # and through the projection: row 3 moves up by 4 and lands on row 1, whose prev sample (y = -0.5) is outside
-    mv[3, :] = (0, -4)
+    prev, curr, mv = cases.mc_row_projected_to_the_top()
     assert (mc.keys(prev, curr, mv, 0.5, 1020)[1] == key(0, -4)).all()
     assert (mc.interpolate_compensated(prev, curr, mv, 0.5, 1020)[1] == curr[3]).all()
 
@@ -211,3 +199,44 @@ def test_roi_equals_the_whole_frame():
     whole = mc.interpolate_compensated(prev, curr, mv, 0.3, 400)
     for x, y, w, h in ((0, 0, 70, 50), (5, 7, 20, 11), (60, 40, 10, 10)):
         assert (mc.interpolate_compensated(prev, curr, mv, 0.3, 400, roi=(x, y, w, h)) == whole[y:y + h, x:x + w]).all()
+
+
+# ---- the power of what the GPU tests rely on
+
+@pytest.mark.parametrize("mutant", mc.MUTANTS)
+def test_inexact_factors_tell_the_mutants_from_the_model(mutant):
+    """Three rewrites of the position arithmetic that are exact in real numbers (tests/mc_model.c): the curr position as
+    P - u, the projection as v - ceil(v t - 0.5), the curr position with its half pixel added last.  On the dense random
+    field of test_gpu_compensated.py at 257 x 131 each gives the model's bytes at every dyadic factor -- the products are exact
+    there, which is why the GPU tests were blind to such a rewrite while they ran those alone -- and different bytes at
+    inexact factors that the GPU tests now run (cases.INEXACT_FACTORS).  Pixels that differ at match_sad 1020:
+        t             0.3    0.7    0.9    5/6
+        C_FROM_P      172    390    546    714
+        CEIL_PROJECT  2340   2472   6172   9049
+        HALF_LAST     0      0      3      6
+    The third is why 0.9 and 5/6 are in the set and why the frame is this large: it shows on a few pixels only.  Each mutant
+    must show at two factors or more, so the set survives the loss of one."""
+    prev, curr, mv = cases.field("random", 257, 131, 57)
+    for t in cases.DYADIC_FACTORS:
+        assert (mc.interpolate_compensated(prev, curr, mv, t, 1020, mutant=mutant)
+                == mc.interpolate_compensated(prev, curr, mv, t, 1020)).all(), t
+    differ = {t: int((mc.interpolate_compensated(prev, curr, mv, t, 1020, mutant=mutant)
+                      != mc.interpolate_compensated(prev, curr, mv, t, 1020)).any(-1).sum()) for t in cases.INEXACT_FACTORS}
+    print(mutant, differ)
+    assert sum(n > 0 for n in differ.values()) >= 2, differ
+
+
+def test_matrix_scene_tells_the_settings_apart():
+    """The scene and the factors of the dispatch matrix (test_gpu_dispatch.py): any two settings that the header defines
+    differently give different frames in the CPU chain, so a mixed-up branch cannot hide.  The only coincidences are the ones
+    the header demands: pyramid + compensated depends on neither semantics (28 distinct frames of 32)."""
+    prev, curr = cases.matrix_scene()
+    ch = cases.Chain(prev, curr)
+    factors = [cases.MATRIX_FACTOR] + cases.MATRIX_FACTORS
+    frames = {s: ch.frames(s, factors) for s in cases.SETTINGS}
+    for k, t in enumerate(factors):
+        for i, a in enumerate(cases.SETTINGS):
+            for b in cases.SETTINGS[i + 1:]:
+                same = (frames[a][k] == frames[b][k]).all()
+                assert same == cases.same_by_definition(a, b), (t, a, b)
+        assert len({frames[s][k].tobytes() for s in cases.SETTINGS}) == 28, t

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from linux_fg_amd import synth
+from tests import cases
 from tests import pyramid_model as pm
 
 
@@ -44,17 +45,9 @@ def test_flat_frames_give_zero():
 def test_tie_between_equal_length_vectors(axis):
     """curr repeats every 4 px along one axis and prev is curr moved by 2 along it: v and -v match exactly.  Of the two the
     smaller vy (vertical) or, vy equal, the smaller vx (horizontal) wins."""
-    rng = np.random.default_rng(5)
-    H, W = 48, 64
-    if axis == 0:
-        row = rng.integers(0, 256, (H, 4, 4), dtype=np.uint8)
-        curr = np.tile(row, (1, W // 4, 1))
-    else:
-        col = rng.integers(0, 256, (4, W, 4), dtype=np.uint8)
-        curr = np.tile(col, (H // 4, 1, 1))
-    prev = np.roll(curr, 2, axis=1 - axis)
-    mv = pm.motion_pyramid(prev, curr, 1, 4, 2)
-    want = (-2, 0) if axis == 0 else (0, -2)
+    prev, curr, params, want = cases.pyramid_tie(axis)
+    assert params == (1, 4, 2) and want == ((-2, 0) if axis == 0 else (0, -2))
+    mv = pm.motion_pyramid(prev, curr, *params)
     inner = mv[12:-12, 12:-12].reshape(-1, 2)
     assert (inner == np.array(want, np.int8)).all(), np.unique(inner, axis=0)
 

@@ -4,24 +4,14 @@ import numpy as np
 import pytest
 
 from linux_fg_amd import synth
+from tests import cases
 from tests import refine_model as rm
 
 RADII = [0, 1, 2]
 
 
-def textured(w, h, seed):
-    return np.random.default_rng(seed).integers(0, 256, (h, w, 4), dtype=np.uint8)
-
-
-def warp(prev, field):
-    """curr(q) = prev(q + v(q)), 0 where q + v(q) leaves the image (the cost's own convention for prev outside)."""
-    h, w = prev.shape[:2]
-    ys, xs = np.mgrid[0:h, 0:w]
-    sx, sy = xs + field[..., 0].astype(int), ys + field[..., 1].astype(int)
-    inside = (sx >= 0) & (sx < w) & (sy >= 0) & (sy < h)
-    curr = np.zeros_like(prev)
-    curr[inside] = prev[sy[inside], sx[inside]]
-    return curr
+# The hand-made inputs are built in tests/cases.py: test_gpu_refine.py runs them on the GPU.
+textured, warp = cases.textured, cases.warp
 
 
 def test_offsets_are_the_17_positions():
@@ -81,50 +71,22 @@ def test_roi_equals_whole_frame():
 def test_straight_edge_between_two_motions(radius, vertical):
     """Two regions with their own vectors, split by a straight line; the input field has the block matcher's error, a 3 px
     band past the edge holding the other side's vector.  Every pixel comes out with its own region's vector."""
-    w, h, e = 48, 40, 21
-    va, vb = np.array([3, -2], np.int8), np.array([-5, 1], np.int8)
-    ys, xs = np.mgrid[0:h, 0:w]
-    pos = xs if vertical else ys
-    truth = np.where((pos < e)[..., None], va, vb).astype(np.int8)
-    mv = np.where((pos < e + 3)[..., None], va, vb).astype(np.int8)
-    prev = textured(w, h, 20 + radius)
-    curr = warp(prev, truth)
+    prev, curr, mv, truth = cases.refine_straight_edge(radius, vertical)
     got = rm.refine(prev, curr, mv, radius)
     bad = np.argwhere((got != truth).any(-1))
     assert len(bad) == 0, bad[:5].tolist()
     assert (mv != truth).any()                     # the input was wrong in the band
 
 
-def tie_case(vectors):
-    """17 x 17 zero frames (every cost 0); pixel (8, 8)'s candidates set to `vectors` in offset order, the rest (7, 7)."""
-    mv = np.zeros((17, 17, 2), np.int8)
-    mv[...] = (7, 7)
-    for (dx, dy), v in zip(rm.OFFSETS, vectors):
-        mv[8 + dy, 8 + dx] = v
-    z = np.zeros((17, 17, 4), np.uint8)
-    return z, z, mv
-
-
 @pytest.mark.parametrize("radius", RADII)
 def test_ties_go_to_shorter_then_smaller_vy_then_smaller_vx(radius):
-    cases = [
-        ([(5, 5), (3, 0), (-3, 0), (0, 3), (0, -3)], (0, -3)),            # |v|^2 = 9 each: smallest vy
-        ([(5, 5), (3, 0), (-3, 0), (0, 3)], (-3, 0)),                     # (3,0) / (-3,0): same vy, smallest vx
-        ([(5, 5), (0, -3), (1, 2), (-2, -1)], (-2, -1)),                  # |v|^2 = 5 beats 9; (-2,-1) has the smaller vy
-        ([(5, 5), (4, 4), (0, 0)], (0, 0)),
-        ([(-9, 0), (9, 0)], (-9, 0)),
-    ]
-    for vectors, want in cases:
-        prev, curr, mv = tie_case(vectors)
+    for vectors, want in cases.REFINE_TIES:
+        prev, curr, mv = cases.refine_tie_case(vectors)
         assert tuple(int(c) for c in rm.refine(prev, curr, mv, radius)[8, 8]) == want, vectors
 
 
 def test_cost_comes_before_length():
-    w, h = 24, 16
-    prev = textured(w, h, 30)
-    curr = warp(prev, np.broadcast_to(np.array([6, 2], np.int8), (h, w, 2)))
-    mv = np.zeros((h, w, 2), np.int8)
-    mv[8, 16] = (6, 2)                             # a candidate of (12, 8) (offset (4, 0)) and of (8, 8) (offset (8, 0))
+    prev, curr, mv = cases.refine_cost_before_length()   # (6, 2) at (16, 8): a candidate of (12, 8) and of (8, 8)
     got = rm.refine(prev, curr, mv, 1)
     assert tuple(got[8, 12]) == (6, 2) and tuple(got[8, 8]) == (6, 2)
     assert tuple(got[8, 16]) == (6, 2)
@@ -135,9 +97,7 @@ def test_cost_comes_before_length():
 def test_candidates_outside_the_image_are_skipped(radius):
     """A 4 x 1 frame: pixel 0's only candidate is its own (x = 4 and x = 8 are outside), even though (0, 0) would fit
     better; an outside position read as (0, 0) would win here."""
-    prev = textured(4, 1, 40)
-    curr = prev.copy()                             # (0, 0) costs 0
-    mv = np.array([[(2, 0), (0, 0), (0, 0), (0, 0)]], np.int8)
+    prev, curr, mv = cases.refine_candidates_outside()
     got = rm.refine(prev, curr, mv, radius)
     assert tuple(got[0, 0]) == (2, 0)
     assert tuple(got[0, 1]) == (0, 0) and tuple(got[0, 3]) == (0, 0)   # pixel 0 is none of theirs either (offsets 4 and 8)
@@ -147,11 +107,7 @@ def test_candidates_outside_the_image_are_skipped(radius):
 def test_prev_outside_the_image_reads_as_zero(radius):
     """curr is 0 and prev 255: a vector that moves the whole window out of the image costs 0 and beats (0, 0), which costs
     255 per channel.  With prev clamped to the edge both would cost the same and (0, 0) would win on length."""
-    w, h = 12, 12
-    prev = np.full((h, w, 4), 255, np.uint8)
-    curr = np.zeros((h, w, 4), np.uint8)
-    mv = np.zeros((h, w, 2), np.int8)
-    mv[6, 6] = (100, 0)
+    prev, curr, mv = cases.refine_prev_outside_zero()
     got = rm.refine(prev, curr, mv, radius)
     for x, y in ((6, 6), (2, 6), (10, 6), (6, 2), (2, 2), (6, 10)):
         assert tuple(got[y, x]) == (100, 0), (x, y)
