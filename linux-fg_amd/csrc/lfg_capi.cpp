@@ -135,6 +135,28 @@ hipError_t sync_lanes(lfg_context *ctx) {
     return e;
 }
 
+// A frame the selected lane owns (mv_tmp, mv_refined, mid_tmp), at this size: kept while the size stays, made again when it
+// changes.  The test comes first because lfg_frame_destroy waits for every lane.  (frame_manager.cpp:226-230)
+int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, uint32_t format) {
+    if (f.data && f.width == width && f.height == height) return LFG_OK;
+    lfg_frame_destroy(ctx, &f);
+    return lfg_frame_create(ctx, width, height, format, &f);
+}
+
+// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys).  `what` names the allocation in the error.
+template <typename T>
+int lane_buffer_grow(lfg_context *ctx, T *&buf, size_t &have, size_t need, const char *what) {
+    if (need <= have) return LFG_OK;
+    lfg_lane_state &cur = ctx->cur();
+    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // the lane's earlier calls may still read the old one
+    if (buf) (void)hipFree(buf);
+    buf = nullptr; have = 0;
+    const hipError_t e = hipMalloc((void **)&buf, need);
+    if (e != hipSuccess) return fail_hip(ctx, e, what);
+    have = need;
+    return LFG_OK;
+}
+
 // uv table of one axis length (lfg_internal.hpp: UvTable); a handful of sizes per context, kept until it goes.
 // Bounded like the axis tables: trim_uv_tables runs at the top of the interpolate entry points, BEFORE any pointer is taken,
 // so that the two lookups of a call (width, height) can never free each other's table.
@@ -456,9 +478,8 @@ namespace {
 void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
-    if (l.mv_tmp.data && l.mv_tmp.owned) (void)hipFree(l.mv_tmp.data);
-    if (l.mv_refined.data && l.mv_refined.owned) (void)hipFree(l.mv_refined.data);
-    if (l.mid_tmp.data && l.mid_tmp.owned) (void)hipFree(l.mid_tmp.data);
+    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mid_tmp})      // (lane_frame)
+        if (f->data && f->owned) (void)hipFree(f->data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
     if (l.mc_keys) (void)hipFree(l.mc_keys);
@@ -877,13 +898,8 @@ LFG_EXPORT int lfg_motion_pyramid(lfg_context *ctx, const lfg_frame *prev, const
     lfg_lane_state &cur = ctx->cur();
     lfg::PyramidLayout layout;
     const size_t bytes = lfg::pyramid_workspace_bytes(curr->width, curr->height, levels, &layout);
-    if (bytes > cur.pyramid_ws_bytes) {
-        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // the lane's earlier calls may still read the old one
-        if (cur.pyramid_ws) (void)hipFree(cur.pyramid_ws);
-        cur.pyramid_ws = nullptr; cur.pyramid_ws_bytes = 0;
-        LFG_HIP(ctx, hipMalloc((void **)&cur.pyramid_ws, bytes));
-        cur.pyramid_ws_bytes = bytes;
-    }
+    int rc = lane_buffer_grow(ctx, cur.pyramid_ws, cur.pyramid_ws_bytes, bytes, "hipMalloc((void **)&cur.pyramid_ws, bytes)");
+    if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_MOTION);
     hipError_t e = lfg::launch_motion_pyramid(cur.stream, *prev, *curr, *mv, levels, coarse_radius, refine_radius, cur.pyramid_ws, layout);
     if (e != hipSuccess) return fail_hip(ctx, e, "pyramid motion kernel launch");
@@ -1100,17 +1116,26 @@ LFG_EXPORT int lfg_interpolate(lfg_context *ctx, const lfg_frame *prev, const lf
 
 namespace {
 
-// lfg_set_vector_refinement: lfg_motion_refine of the estimator's vectors `mv` into the lane's second temporary, made for
-// this frame size on demand; *refined is that temporary.
-int refine_stage(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_frame **refined) {
-    lfg_frame &r = ctx->cur().mv_refined;
-    if (!r.data || r.width != curr->width || r.height != curr->height) {
-        lfg_frame_destroy(ctx, &r);
-        int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &r);
-        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create refined motion vectors frame");
-    }
-    *refined = &r;
-    return lfg_motion_refine(ctx, prev, curr, mv, &r, ctx->refine_radius);
+// The full search as lfg_interpolate_frames[_multi] run it (frame_manager.cpp:332-333).
+constexpr int kFramesBlockSize = 8;
+constexpr float kFramesSearchRadius = 16.0f;
+
+// The vectors the generated frames are made from, on the selected lane: the selected estimator's in mv_tmp, and with
+// lfg_set_vector_refinement their refinement in mv_refined.  The estimator is enqueued before mv_refined is made: making
+// a frame can wait for every lane.
+int frame_vectors(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame **vectors) {
+    lfg_lane_state &cur = ctx->cur();
+    int rc = lane_frame(ctx, cur.mv_tmp, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
+    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
+    rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &cur.mv_tmp, 2, 16, 2)
+                                                 : lfg_motion(ctx, prev, curr, &cur.mv_tmp, kFramesBlockSize, kFramesSearchRadius);
+    if (rc != LFG_OK) return rc;
+    *vectors = &cur.mv_tmp;
+    if (ctx->refine_radius < 0) return LFG_OK;
+    rc = lane_frame(ctx, cur.mv_refined, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
+    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create refined motion vectors frame");
+    *vectors = &cur.mv_refined;
+    return lfg_motion_refine(ctx, prev, curr, &cur.mv_tmp, &cur.mv_refined, ctx->refine_radius);
 }
 
 }  // namespace
@@ -1118,38 +1143,15 @@ int refine_stage(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
 LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                       lfg_frame *out, float factor) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: NULL argument");
-    lfg_frame &mv = ctx->cur().mv_tmp;
-    if (!mv.data || mv.width != curr->width || mv.height != curr->height) {   // frame_manager.cpp:226-230
-        lfg_frame_destroy(ctx, &mv);
-        int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
-        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
-    }
-    if (ctx->refine_radius >= 0) {                  // estimator, refinement, interpolator: three stages (no fused kernel)
-        int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
-                                                         : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);
-        if (rc != LFG_OK) return rc;
-        const lfg_frame *refined = nullptr;
-        rc = refine_stage(ctx, prev, curr, &mv, &refined);
-        if (rc != LFG_OK) return rc;
-        return ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED
-                   ? lfg_interpolate_compensated(ctx, prev, curr, refined, out, factor, ctx->match_sad)
-                   : lfg_interpolate(ctx, prev, curr, refined, out, factor);
-    }
-    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {      // two stages under either estimator (no fused kernel)
-        int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
-                                                         : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);
-        if (rc != LFG_OK) return rc;
-        return lfg_interpolate_compensated(ctx, prev, curr, &mv, out, factor, ctx->match_sad);
-    }
-    if (ctx->estimator == LFG_ESTIMATOR_PYRAMID) {          // (the fused motion kernels are the full search's: two stages here)
-        int rc = lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2);
-        if (rc != LFG_OK) return rc;
-        return lfg_interpolate(ctx, prev, curr, &mv, out, factor);
-    }
-    if (ctx->fuse_motion_interpolate) {
+    // The fused motion kernels are the full search's and write the shader's interpolation: every other setting takes the stages.
+    if (ctx->fuse_motion_interpolate && ctx->estimator == LFG_ESTIMATOR_FULL_SEARCH && ctx->refine_radius < 0 &&
+        ctx->interpolator == LFG_INTERPOLATOR_SHADER) {
         // The north-star order: the motion kernels write the generated frame from the vectors while they
         // hold them; the vector frame -- this call's temporary -- is not written at all.  `out` is checked as lfg_interpolate
-        // checks it; whatever the fused path does not cover (see motion_run) takes the two stages below.
+        // checks it; whatever the fused path does not cover (see motion_run) goes on to lfg_interpolate.
+        lfg_frame &mv = ctx->cur().mv_tmp;
+        int rc = lane_frame(ctx, mv, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
+        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
         if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM) || !same_size(curr, out) || out->pitch % 4u)
             return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: bad output frame (NULL, empty, wrong format, size or pitch)");
         if (out->data == prev->data || out->data == curr->data)
@@ -1157,13 +1159,16 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
         lfg::FusedOut fo;
         fo.data = (uint8_t *)out->data; fo.pitch = (int)out->pitch; fo.t = factor; fo.intended = ctx->semantics != 0 ? 1 : 0; fo.storeMv = 0;
         bool done = false;
-        int rc = motion_run(ctx, prev, curr, &mv, 8, 16.0f, &fo, &done);
+        rc = motion_run(ctx, prev, curr, &mv, kFramesBlockSize, kFramesSearchRadius, &fo, &done);
         if (rc != LFG_OK || done) return rc;
         return lfg_interpolate(ctx, prev, curr, &mv, out, factor);     // (the generic kernel ran: it wrote the vectors)
     }
-    int rc = lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);                      // frame_manager.cpp:332-333
+    const lfg_frame *vectors = nullptr;
+    int rc = frame_vectors(ctx, prev, curr, &vectors);
     if (rc != LFG_OK) return rc;
-    return lfg_interpolate(ctx, prev, curr, &mv, out, factor);
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
+        return lfg_interpolate_compensated(ctx, prev, curr, vectors, out, factor, ctx->match_sad);
+    return lfg_interpolate(ctx, prev, curr, vectors, out, factor);
 }
 
 LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
@@ -1199,20 +1204,9 @@ LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, co
 LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                             lfg_frame *const *outs, const float *factors, uint32_t count) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames_multi: NULL argument");
-    lfg_frame &mv = ctx->cur().mv_tmp;
-    if (!mv.data || mv.width != curr->width || mv.height != curr->height) {   // frame_manager.cpp:226-230
-        lfg_frame_destroy(ctx, &mv);
-        int rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_MV_S8X2, &mv);
-        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
-    }
-    int rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &mv, 2, 16, 2)
-                                                     : lfg_motion(ctx, prev, curr, &mv, 8, 16.0f);   // frame_manager.cpp:332-333
+    const lfg_frame *vectors = nullptr;
+    int rc = frame_vectors(ctx, prev, curr, &vectors);
     if (rc != LFG_OK) return rc;
-    const lfg_frame *vectors = &mv;
-    if (ctx->refine_radius >= 0) {
-        rc = refine_stage(ctx, prev, curr, &mv, &vectors);
-        if (rc != LFG_OK) return rc;
-    }
     if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
         return lfg_interpolate_compensated_multi(ctx, prev, curr, vectors, outs, factors, count, ctx->match_sad);
     return lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count);
@@ -1257,13 +1251,8 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     }
     lfg_lane_state &cur = ctx->cur();
     const size_t bytes = (size_t)curr->width * curr->height * 4u;
-    if (bytes > cur.mc_keys_bytes) {
-        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // the lane's earlier calls may still read the old one
-        if (cur.mc_keys) (void)hipFree(cur.mc_keys);
-        cur.mc_keys = nullptr; cur.mc_keys_bytes = 0;
-        LFG_HIP(ctx, hipMalloc((void **)&cur.mc_keys, bytes));
-        cur.mc_keys_bytes = bytes;
-    }
+    int rc = lane_buffer_grow(ctx, cur.mc_keys, cur.mc_keys_bytes, bytes, "hipMalloc((void **)&cur.mc_keys, bytes)");
+    if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
     for (uint32_t i = 0; i < count; ++i) {                       // one key image, reused in stream order
         hipError_t e = lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
@@ -1369,11 +1358,8 @@ LFG_EXPORT int lfg_interpolate_scale(lfg_context *ctx, const lfg_frame *prev, co
     }
     // any other size ratio: the two stages, through a context-owned frame at input resolution
     lfg_frame &mid = ctx->cur().mid_tmp;
-    if (!mid.data || mid.width != curr->width || mid.height != curr->height) {
-        lfg_frame_destroy(ctx, &mid);
-        rc = lfg_frame_create(ctx, curr->width, curr->height, LFG_FORMAT_RGBA8_UNORM, &mid);
-        if (rc != LFG_OK) return rc;
-    }
+    rc = lane_frame(ctx, mid, curr->width, curr->height, LFG_FORMAT_RGBA8_UNORM);
+    if (rc != LFG_OK) return rc;
     rc = lfg_interpolate(ctx, prev, curr, mv, &mid, factor);
     if (rc != LFG_OK) return rc;
     return lfg_scale(ctx, &mid, out);

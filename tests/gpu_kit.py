@@ -1,0 +1,91 @@
+"""What the GPU test files share.  `ctx` is a pytest fixture: a test file imports it by name, which makes it that module's own
+(one context per file, as when each file defined it), and a linter will call that import unused."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from linux_fg_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import __graft_entry__ as entry
+    if not os.path.exists(capi.LIB_PATH):
+        entry.build()
+    with capi.Context(0) as c:
+        yield c
+
+
+def gpu_vectors(ctx, prev, curr, estimator):
+    """The vectors of "full" (lfg_motion) or "pyramid" (lfg_motion_pyramid at 2, 16, 2) under the intended semantics."""
+    h, w = prev.shape[:2]
+    p, c = ctx.frame_from(prev), ctx.frame_from(curr)
+    m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
+    ctx.set_semantics(capi.SEMANTICS_INTENDED)
+    try:
+        if estimator == "full":
+            ctx.motion(p, c, m)
+        else:
+            ctx.motion_pyramid(p, c, m, 2, 16, 2)
+        return ctx.download(m)
+    finally:
+        ctx.set_semantics(capi.SEMANTICS_REFERENCE)
+        for f in (p, c, m):
+            ctx.destroy_frame(f)
+
+
+def pitched(ctx, host, pad_px, fmt=capi.FORMAT_RGBA8):
+    """`host` in the left part of a wider frame, described with the wider row pitch (lfg_frame_wrap), as a caller handing
+    over a sub-rectangle would; the padding poisoned with 0x5A bytes.  Returns (the wider frame, the view)."""
+    h, w, ch = host.shape
+    wide = np.full((h, w + pad_px, ch), 0x5A, host.dtype)
+    wide[:, :w] = host
+    big = ctx.frame_from(wide, fmt)
+    return big, capi.Context.wrap(big.data, w, h, fmt, pitch=(w + pad_px) * ch)
+
+
+def first_bad(got, want):
+    bad = np.argwhere((got != want).any(-1))
+    return f"{len(bad)} pixels differ, first {bad[:3].tolist()}"
+
+
+def host_stream(tmp_path, frames, *options):
+    """`frames` through lfg_host as a raw file, under the intended semantics and `options`: the 2 n - 1 frames it presents."""
+    if not os.path.exists(HOST):
+        import __graft_entry__ as entry
+        entry.build()
+    n, (h, w) = len(frames), frames[0].shape[:2]
+    src = tmp_path / "in.rgba"
+    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
+    out = tmp_path / "out.rgba"
+    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
+                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended", *options],
+                       capture_output=True, text=True, timeout=300, check=True)
+    info = json.loads(p.stdout.strip().splitlines()[-1])
+    assert info["presented"] == 2 * n - 1
+    return np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+
+
+def three_lanes(ctx, inputs, enqueue, alone):
+    """Input i on lane i % 3, everything enqueued before the one sync.  enqueue(i, *inputs[i]) uploads what the call reads,
+    makes the call and returns its frames, the output last: each output must be alone[i], what the call gave on one lane."""
+    ctx.lanes(3)
+    try:
+        frames = []
+        for i, arrays in enumerate(inputs):
+            ctx.lane_select(i % 3)
+            frames.append(enqueue(i, *arrays))
+        ctx.sync()
+        for fs, want in zip(frames, alone):
+            assert (ctx.download(fs[-1]) == want).all()
+            for f in fs:
+                ctx.destroy_frame(f)
+    finally:
+        ctx.lane_select(0)
+        ctx.lanes(1)

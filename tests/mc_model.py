@@ -8,16 +8,14 @@ cheap.  ``keys(...)`` is the projected key image itself, and ``sample(..., K, ..
 from __future__ import annotations
 
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "mc_model.c")
-_libs = {}
+from tests.c_model import frames_and_vectors as _inputs, load, ptr as _ptr
+
+_VP, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+_SIGNATURES = {"mc_project": [_VP, _VP, _VP, _I, _I, _F, _I, _VP],
+               "mc_sample": [_VP, _VP, _VP, _VP, _I, _I, _F, _I, _I, _I, _I, _I, _VP]}
 
 HOLE = 0xFFFFFFFF
 DEFAULT_MATCH_SAD = 48
@@ -26,37 +24,8 @@ MUTANTS = ("C_FROM_P", "CEIL_PROJECT", "HALF_LAST")     # mc_model.c: rewrites t
 
 def _load(mutant=None):
     """The model, or with mutant = one of MUTANTS the model built with -DMC_MUTANT_<mutant>, under a cache name of its own."""
-    if mutant not in _libs:
-        assert mutant is None or mutant in MUTANTS, mutant
-        src = open(_SRC, "rb").read()
-        tag = hashlib.sha1(src).hexdigest()[:12] + (f"_{mutant.lower()}" if mutant else "")
-        out = os.path.join(tempfile.gettempdir(), f"lfg_mc_model_{os.getuid()}_{tag}.so")
-        if not os.path.exists(out):
-            tmp = out + f".{os.getpid()}"
-            define = [f"-DMC_MUTANT_{mutant}"] if mutant else []
-            subprocess.check_call([os.environ.get("CC", "cc"), "-O2", "-ffp-contract=off", "-shared", "-fPIC"] + define +
-                                  ["-o", tmp, _SRC, "-lm"])
-            os.replace(tmp, out)
-        L = ctypes.CDLL(out)
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.mc_project.argtypes = [vp, vp, vp, i, i, f, i, vp]
-        L.mc_project.restype = None
-        L.mc_sample.argtypes = [vp, vp, vp, vp, i, i, f, i, i, i, i, i, vp]
-        L.mc_sample.restype = None
-        _libs[mutant] = L
-    return _libs[mutant]
-
-
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _inputs(prev, curr, mv):
-    prev = np.ascontiguousarray(prev, np.uint8)
-    curr = np.ascontiguousarray(curr, np.uint8)
-    mv = np.ascontiguousarray(mv).astype(np.int8, copy=False)
-    assert prev.shape == curr.shape and prev.shape[2] == 4 and mv.shape == prev.shape[:2] + (2,)
-    return prev, curr, np.ascontiguousarray(mv)
+    assert mutant is None or mutant in MUTANTS, mutant
+    return load("mc_model", _SIGNATURES, ["-ffp-contract=off"] + ([f"-DMC_MUTANT_{mutant}"] if mutant else []), ["-lm"])
 
 
 def key(vx: int, vy: int) -> int:

@@ -8,39 +8,18 @@ of a 4K frame are cheap."""
 from __future__ import annotations
 
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "pyramid_model.c")
-_lib = None
+from tests.c_model import load, ptr as _ptr
+
+_VP, _I = ctypes.c_void_p, ctypes.c_int
+_SIGNATURES = {"pyramid_level": [_VP, _I, _I, _VP, _I, _I],
+               "pyramid_vectors": [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]}
 
 
 def _load():
-    global _lib
-    if _lib is None:
-        src = open(_SRC, "rb").read()
-        out = os.path.join(tempfile.gettempdir(), f"lfg_pyramid_model_{os.getuid()}_{hashlib.sha1(src).hexdigest()[:12]}.so")
-        if not os.path.exists(out):
-            tmp = out + f".{os.getpid()}"
-            subprocess.check_call([os.environ.get("CC", "cc"), "-O2", "-shared", "-fPIC", "-o", tmp, _SRC])
-            os.replace(tmp, out)
-        L = ctypes.CDLL(out)
-        vp, i = ctypes.c_void_p, ctypes.c_int
-        L.pyramid_level.argtypes = [vp, i, i, vp, i, i]
-        L.pyramid_level.restype = None
-        L.pyramid_vectors.argtypes = [vp, vp, i, i, i, i, i, i, vp, i, i, vp]
-        L.pyramid_vectors.restype = None
-        _lib = L
-    return _lib
-
-
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
+    return load("pyramid_model", _SIGNATURES)
 
 
 def level_sizes(w: int, h: int, levels: int):

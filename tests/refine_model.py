@@ -8,55 +8,27 @@ output depends only on mv within 8 px and the frames within radius + 128 px), so
 from __future__ import annotations
 
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from linux_fg_amd import synth
+from tests.c_model import frames_and_vectors, load, ptr as _ptr
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "refine_model.c")
-_lib = None
+_VP, _I = ctypes.c_void_p, ctypes.c_int
+_SIGNATURES = {"refine_roi": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _VP]}
 
 # candidate offsets: (0, 0), then s = 4, 8, then b, then a, skipping (a, b) = (0, 0)
 OFFSETS = [(0, 0)] + [(a * s, b * s) for s in (4, 8) for b in (-1, 0, 1) for a in (-1, 0, 1) if (a, b) != (0, 0)]
 
 
-def _load():
-    global _lib
-    if _lib is None:
-        src = open(_SRC, "rb").read()
-        out = os.path.join(tempfile.gettempdir(), f"lfg_refine_model_{os.getuid()}_{hashlib.sha1(src).hexdigest()[:12]}.so")
-        if not os.path.exists(out):
-            tmp = out + f".{os.getpid()}"
-            subprocess.check_call([os.environ.get("CC", "cc"), "-O2", "-shared", "-fPIC", "-o", tmp, _SRC])
-            os.replace(tmp, out)
-        L = ctypes.CDLL(out)
-        vp, i = ctypes.c_void_p, ctypes.c_int
-        L.refine_roi.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
-        L.refine_roi.restype = None
-        _lib = L
-    return _lib
-
-
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def refine(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, radius: int = 1, roi=None) -> np.ndarray:
     """(H, W, 2) int8 of the whole frame, or (h, w, 2) of roi = (x, y, w, h)."""
-    prev = np.ascontiguousarray(prev, np.uint8)
-    curr = np.ascontiguousarray(curr, np.uint8)
-    mv = np.ascontiguousarray(np.asarray(mv).astype(np.int8, copy=False))
-    assert prev.shape == curr.shape and prev.shape[2] == 4 and mv.shape == prev.shape[:2] + (2,)
+    prev, curr, mv = frames_and_vectors(prev, curr, mv)
     assert 0 <= radius <= 2
     H, W = prev.shape[:2]
     x, y, w, h = roi if roi is not None else (0, 0, W, H)
     out = np.empty((h, w, 2), np.int8)
-    _load().refine_roi(_ptr(prev), _ptr(curr), _ptr(mv), W, H, int(radius), x, y, x + w, y + h, _ptr(out))
+    load("refine_model", _SIGNATURES).refine_roi(_ptr(prev), _ptr(curr), _ptr(mv), W, H, int(radius), x, y, x + w, y + h, _ptr(out))
     return out
 
 

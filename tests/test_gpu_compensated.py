@@ -2,9 +2,6 @@
 the shader's modes do not; the interpolator switch of lfg_interpolate_frames[_multi]; argument checks; lanes; the host's
 --interpolator option; and the hand-made cases of test_mc_model.py that need no hand-placed key image."""
 import ctypes
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,42 +9,15 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import cases
 from tests import mc_model as mc
+from tests.gpu_kit import ctx, first_bad, gpu_vectors, host_stream, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
 
 SIZES = [(1, 1), (7, 5), (33, 17), (64, 64), (257, 131)]
 # Dyadic factors make every product of the position arithmetic exact in fp32; the inexact ones are those that tell the model's
 # mutants from the model (test_mc_model.py), and the last two approach t = 1 and t = 0 without reaching them.
 FACTORS = cases.DYADIC_FACTORS + cases.INEXACT_FACTORS + cases.LIMIT_FACTORS
 MATCH = [0, 48, 1020]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as entry
-    if not os.path.exists(capi.LIB_PATH):
-        entry.build()
-    with capi.Context(0) as c:
-        yield c
-
-
-def gpu_vectors(ctx, prev, curr, estimator):
-    h, w = prev.shape[:2]
-    p, c = ctx.frame_from(prev), ctx.frame_from(curr)
-    m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
-    ctx.set_semantics(capi.SEMANTICS_INTENDED)
-    try:
-        if estimator == "full":
-            ctx.motion(p, c, m)
-        else:
-            ctx.motion_pyramid(p, c, m, 2, 16, 2)
-        return ctx.download(m)
-    finally:
-        ctx.set_semantics(capi.SEMANTICS_REFERENCE)
-        for f in (p, c, m):
-            ctx.destroy_frame(f)
 
 
 def case(ctx, field, w, h, seed):
@@ -69,11 +39,6 @@ def run(ctx, prev, curr, mv, t, match_sad):
     finally:
         for f in (p, c, m, o):
             ctx.destroy_frame(f)
-
-
-def first_bad(got, want):
-    bad = np.argwhere((got != want).any(-1))
-    return f"{len(bad)} pixels differ, first {bad[:3].tolist()}"
 
 
 @pytest.mark.parametrize("field", ["uniform", "piecewise", "random", "motion", "pyramid"])
@@ -110,15 +75,6 @@ def test_rois_of_4k_and_8k(ctx, w, h):
         for x, y, rw, rh in rois:
             want = mc.interpolate_compensated(prev, curr, mv, t, ms, roi=(x, y, rw, rh))
             assert (got[y:y + rh, x:x + rw] == want).all(), (w, h, field, x, y)
-
-
-def pitched(ctx, host, pad_px, fmt=capi.FORMAT_RGBA8):
-    """`host` in the left part of a wider frame, described with the wider row pitch (lfg_frame_wrap); the padding poisoned."""
-    h, w, ch = host.shape
-    wide = np.full((h, w + pad_px, ch), 0x5A, host.dtype)
-    wide[:, :w] = host
-    big = ctx.frame_from(wide, fmt)
-    return big, capi.Context.wrap(big.data, w, h, fmt, pitch=(w + pad_px) * ch)
 
 
 def test_padded_pitch(ctx):
@@ -365,44 +321,23 @@ def test_three_lanes_equal_one_lane(ctx):
     sizes = [(200, 120), (96, 64), (200, 120), (130, 90), (96, 64), (300, 170)]
     cases = [case(ctx, "random" if i % 2 else "piecewise", w, h, 60 + i) for i, (w, h) in enumerate(sizes)]
     alone = [run(ctx, a, b, v, 0.5, 1020) for a, b, v in cases]
-    ctx.lanes(3)
-    try:
-        frames = []
-        for i, (a, b, v) in enumerate(cases):
-            ctx.lane_select(i % 3)
-            h, w = a.shape[:2]
-            p, c, m = ctx.frame_from(a), ctx.frame_from(b), ctx.frame_from(v, capi.FORMAT_MV_S8X2)
-            o = ctx.create_frame(w, h)
-            ctx.interpolate_compensated(p, c, m, o, 0.5, 1020)
-            frames.append((p, c, m, o))
-        ctx.sync()
-        for fs, want in zip(frames, alone):
-            assert (ctx.download(fs[3]) == want).all()
-            for f in fs:
-                ctx.destroy_frame(f)
-    finally:
-        ctx.lane_select(0)
-        ctx.lanes(1)
+
+    def enqueue(i, a, b, v):
+        h, w = a.shape[:2]
+        p, c, m = ctx.frame_from(a), ctx.frame_from(b), ctx.frame_from(v, capi.FORMAT_MV_S8X2)
+        o = ctx.create_frame(w, h)
+        ctx.interpolate_compensated(p, c, m, o, 0.5, 1020)
+        return p, c, m, o
+
+    three_lanes(ctx, cases, enqueue, alone)
 
 
 def test_host_compensated_stream_matches_capi(tmp_path):
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
     w, h, n = 1920, 1080, 3
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (12, -6), synth.BASE_SEED + k))
-    src = tmp_path / "in.rgba"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    out = tmp_path / "out.rgba"
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
-                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended",
-                        "--interpolator", "compensated"],
-                       capture_output=True, text=True, timeout=300, check=True)
-    info = json.loads(p.stdout.strip().splitlines()[-1])
-    assert info["presented"] == 2 * n - 1
-    got = np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+    got = host_stream(tmp_path, frames, "--interpolator", "compensated")
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

@@ -7,22 +7,13 @@ import pytest
 
 from linux_fg_amd import capi
 from tests import cases
+from tests.gpu_kit import ctx, first_bad
 
 pytestmark = pytest.mark.gpu
 
 ESTIMATOR = {"full": capi.ESTIMATOR_FULL_SEARCH, "pyramid": capi.ESTIMATOR_PYRAMID}
 INTERPOLATOR = {"shader": capi.INTERPOLATOR_SHADER, "compensated": capi.INTERPOLATOR_COMPENSATED}
 DEFAULT = ("full", -1, "shader", capi.SEMANTICS_REFERENCE)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import os
-    import __graft_entry__ as entry
-    if not os.path.exists(capi.LIB_PATH):
-        entry.build()
-    with capi.Context(0) as c:
-        yield c
 
 
 def apply(ctx, setting, fused=False, match_sad=capi.DEFAULT_MATCH_SAD):
@@ -39,11 +30,6 @@ def restore(ctx):
     ctx.lane_select(0)
     ctx.lanes(1)
     apply(ctx, DEFAULT)
-
-
-def first_bad(got, want):
-    bad = np.argwhere((got != want).any(-1))
-    return f"{len(bad)} pixels differ, first {bad[:3].tolist()}"
 
 
 _chains = {}

@@ -10,18 +10,11 @@ import pytest
 
 from linux_fg_amd import synth
 from oracle import scale_f64 as f64
+from tests.gpu_kit import ctx, pitched as _pitched
 
 pytestmark = pytest.mark.gpu
 
 RNG = np.random.default_rng(2024)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from linux_fg_amd import capi
-    c = capi.Context(0)
-    yield c
-    c.close()
 
 
 def rand_frame(w, h):
@@ -1268,20 +1261,6 @@ def test_golden_fixtures_on_device(ctx):
 
 # ------------------------------------------------------------------------------ pitched frames
 
-def _pitched(ctx, host, pad_px, fmt=None):
-    """Upload `host` into the left part of a wider device allocation and describe it with a row pitch
-    larger than width * bpp (lfg_frame_wrap), as a caller handing over a sub-rectangle would."""
-    from linux_fg_amd import capi
-    fmt = capi.FORMAT_RGBA8 if fmt is None else fmt
-    h, w, ch = host.shape
-    wide = np.zeros((h, w + pad_px, ch), host.dtype)
-    wide[:, :w] = host
-    wide[:, w:] = 0x5A if host.dtype == np.uint8 else 3          # poison the padding
-    big = ctx.frame_from(wide, fmt)
-    view = capi.Context.wrap(big.data, w, h, fmt, pitch=(w + pad_px) * ch)
-    return big, view
-
-
 def _read_pitched(ctx, big, w):
     return ctx.download(big)[:, :w]
 
@@ -1311,7 +1290,7 @@ def test_all_stages_with_row_pitch_larger_than_width(ctx, oracle, pad):
     assert (On == oracle.interpolate(Pn, Cn, mv, 0.5)).all()
     for b in (bP, bC, bO):                                   # nothing was written into the padding
         assert (ctx.download(b)[:, W:] == 0x5A).all()
-    assert (ctx.download(bM)[:, W:] == 3).all()
+    assert (ctx.download(bM)[:, W:] == 0x5A).all()
     for b in (bp, bc, bP, bC, bO, bM):
         ctx.destroy_frame(b)
 

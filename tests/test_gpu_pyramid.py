@@ -2,9 +2,6 @@
 estimator switch of lfg_interpolate_frames[_multi]; lanes; the host's --motion / --semantics options; and the tie case of
 test_pyramid_model.py."""
 import ctypes
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,22 +9,12 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import cases
 from tests import pyramid_model as pm
+from tests.gpu_kit import ctx, host_stream, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
 
 PARAMS = [(1, 32, 1), (2, 16, 2), (3, 12, 3), (4, 7, 1), (2, 8, 4)]
 SIZES = [(1, 1), (7, 5), (33, 17), (64, 64), (257, 131)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as entry
-    if not os.path.exists(capi.LIB_PATH):
-        entry.build()
-    with capi.Context(0) as c:
-        yield c
 
 
 def content(kind, w, h, seed):
@@ -54,15 +41,6 @@ def run_pyramid(ctx, prev, curr, params):
     for f in (p, c, m):
         ctx.destroy_frame(f)
     return out
-
-
-def pitched(ctx, host, pad_px, fmt=capi.FORMAT_RGBA8):
-    """`host` in the left part of a wider frame, described with the wider row pitch (lfg_frame_wrap); the padding poisoned."""
-    h, w, ch = host.shape
-    wide = np.full((h, w + pad_px, ch), 0x5A, host.dtype)
-    wide[:, :w] = host
-    big = ctx.frame_from(wide, fmt)
-    return big, capi.Context.wrap(big.data, w, h, fmt, pitch=(w + pad_px) * ch)
 
 
 @pytest.mark.parametrize("params", PARAMS)
@@ -205,43 +183,23 @@ def test_three_lanes_equal_one_lane(ctx):
     sizes = [(200, 120), (96, 64), (200, 120), (130, 90), (96, 64), (130, 90)]
     pairs = [content("translated" if i % 2 else "uncorrelated", w, h, 40 + i) for i, (w, h) in enumerate(sizes)]
     alone = [run_pyramid(ctx, a, b, (2, 16, 2)) for a, b in pairs]
-    ctx.lanes(3)
-    try:
-        frames = []
-        for i, (a, b) in enumerate(pairs):
-            ctx.lane_select(i % 3)
-            h, w = a.shape[:2]
-            p, c = ctx.frame_from(a), ctx.frame_from(b)
-            m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
-            ctx.motion_pyramid(p, c, m, 2, 16, 2)
-            frames.append((p, c, m))
-        ctx.sync()
-        for (p, c, m), want in zip(frames, alone):
-            assert (ctx.download(m) == want).all()
-            for f in (p, c, m):
-                ctx.destroy_frame(f)
-    finally:
-        ctx.lane_select(0)
-        ctx.lanes(1)
+
+    def enqueue(i, a, b):
+        h, w = a.shape[:2]
+        p, c = ctx.frame_from(a), ctx.frame_from(b)
+        m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
+        ctx.motion_pyramid(p, c, m, 2, 16, 2)
+        return p, c, m
+
+    three_lanes(ctx, pairs, enqueue, alone)
 
 
 def test_host_pyramid_stream_matches_capi(tmp_path):
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
     w, h, n = 1920, 1080, 3
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (20, 0), synth.BASE_SEED + k))
-    src = tmp_path / "in.rgba"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    out = tmp_path / "out.rgba"
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
-                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended", "--motion", "pyramid"],
-                       capture_output=True, text=True, timeout=300, check=True)
-    info = json.loads(p.stdout.strip().splitlines()[-1])
-    assert info["presented"] == 2 * n - 1
-    got = np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+    got = host_stream(tmp_path, frames, "--motion", "pyramid")
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

@@ -2,9 +2,6 @@
 refinement switch of lfg_interpolate_frames[_multi]; the host's --refine-vectors; the hand-made cases of
 test_refine_model.py; and what it is for: the halo of wrong vectors around moving edges."""
 import ctypes
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,40 +11,13 @@ from tests import cases
 from tests import mc_model as mc
 from tests import pyramid_model as pm
 from tests import refine_model as rm
+from tests.gpu_kit import ctx, first_bad, gpu_vectors, host_stream, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
 
 SIZES = [(1, 1), (7, 5), (33, 17), (64, 64), (257, 131), (1920, 1080)]
 RADII = [0, 1, 2]
 FIELDS = ["uniform", "piecewise", "random", "full", "pyramid"]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as entry
-    if not os.path.exists(capi.LIB_PATH):
-        entry.build()
-    with capi.Context(0) as c:
-        yield c
-
-
-def gpu_vectors(ctx, prev, curr, estimator):
-    h, w = prev.shape[:2]
-    p, c = ctx.frame_from(prev), ctx.frame_from(curr)
-    m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
-    ctx.set_semantics(capi.SEMANTICS_INTENDED)
-    try:
-        if estimator == "full":
-            ctx.motion(p, c, m)
-        else:
-            ctx.motion_pyramid(p, c, m, 2, 16, 2)
-        return ctx.download(m)
-    finally:
-        ctx.set_semantics(capi.SEMANTICS_REFERENCE)
-        for f in (p, c, m):
-            ctx.destroy_frame(f)
 
 
 def case(ctx, field, w, h, seed):
@@ -82,11 +52,6 @@ def run(ctx, prev, curr, mv, radius):
     finally:
         for f in (p, c, m, o):
             ctx.destroy_frame(f)
-
-
-def first_bad(got, want):
-    bad = np.argwhere((got != want).any(-1))
-    return f"{len(bad)} pixels differ, first {bad[:3].tolist()}"
 
 
 @pytest.mark.parametrize("field", FIELDS)
@@ -150,15 +115,6 @@ def test_rois_of_4k_and_8k(ctx, w, h):
             for x, y, rw, rh in rois:
                 want = rm.refine(prev, curr, mv, radius, roi=(x, y, rw, rh))
                 assert (got[y:y + rh, x:x + rw] == want).all(), (w, h, field, radius, x, y)
-
-
-def pitched(ctx, host, pad_px, fmt=capi.FORMAT_RGBA8):
-    """`host` in the left part of a wider frame, described with the wider row pitch; the padding poisoned."""
-    h, w, ch = host.shape
-    wide = np.full((h, w + pad_px, ch), 0x5A, host.dtype)
-    wide[:, :w] = host
-    big = ctx.frame_from(wide, fmt)
-    return big, capi.Context.wrap(big.data, w, h, fmt, pitch=(w + pad_px) * ch)
 
 
 def test_padded_pitch(ctx):
@@ -234,24 +190,15 @@ def test_three_lanes_equal_one_lane(ctx):
     sizes = [(200, 120), (96, 64), (200, 120), (130, 90), (96, 64), (300, 170)]
     cases = [case(ctx, "random" if i % 2 else "piecewise", w, h, 60 + i) for i, (w, h) in enumerate(sizes)]
     alone = [run(ctx, a, b, v, 1 + i % 2) for i, (a, b, v) in enumerate(cases)]
-    ctx.lanes(3)
-    try:
-        frames = []
-        for i, (a, b, v) in enumerate(cases):
-            ctx.lane_select(i % 3)
-            h, w = a.shape[:2]
-            p, c, m = ctx.frame_from(a), ctx.frame_from(b), ctx.frame_from(v, capi.FORMAT_MV_S8X2)
-            o = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
-            ctx.motion_refine(p, c, m, o, 1 + i % 2)
-            frames.append((p, c, m, o))
-        ctx.sync()
-        for fs, want in zip(frames, alone):
-            assert (ctx.download(fs[3]) == want).all()
-            for f in fs:
-                ctx.destroy_frame(f)
-    finally:
-        ctx.lane_select(0)
-        ctx.lanes(1)
+
+    def enqueue(i, a, b, v):
+        h, w = a.shape[:2]
+        p, c, m = ctx.frame_from(a), ctx.frame_from(b), ctx.frame_from(v, capi.FORMAT_MV_S8X2)
+        o = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
+        ctx.motion_refine(p, c, m, o, 1 + i % 2)
+        return p, c, m, o
+
+    three_lanes(ctx, cases, enqueue, alone)
 
 
 # ---- the refinement switch
@@ -322,23 +269,11 @@ def test_refinement_switch(ctx, estimator):
 
 
 def test_host_refined_stream_matches_capi(tmp_path):
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
     w, h, n = 1920, 1080, 3
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (12, -6), synth.BASE_SEED + k))
-    src = tmp_path / "in.rgba"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    out = tmp_path / "out.rgba"
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
-                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended",
-                        "--interpolator", "compensated", "--refine-vectors", "1"],
-                       capture_output=True, text=True, timeout=300, check=True)
-    info = json.loads(p.stdout.strip().splitlines()[-1])
-    assert info["presented"] == 2 * n - 1
-    got = np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+    got = host_stream(tmp_path, frames, "--interpolator", "compensated", "--refine-vectors", "1")
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

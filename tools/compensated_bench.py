@@ -6,17 +6,11 @@ warm-up; the vectors come from lfg_motion under the intended semantics, except f
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stage_bench import SIZES, arguments, emit, per_call_ms, write_json      # (puts the repository root on sys.path)
 from linux_fg_amd import capi, synth  # noqa: E402
 
-SIZES = {"1080p": (1920, 1080), "4k": (3840, 2160), "8k": (7680, 4320)}
 FACTORS = [0.25, 0.5, 0.75]
 
 
@@ -36,25 +30,11 @@ def contents(w, h):
 
 
 def per_call_us(ctx, fn, calls, warmup):
-    for _ in range(warmup):
-        fn()
-    ctx.sync()
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    for _ in range(calls):
-        fn()
-    ms = ctx.profile_get(capi.STAGE_INTERPOLATE)[0]
-    ctx.profile_enable(False)
-    return 1000.0 * ms / calls
+    return 1000.0 * per_call_ms(ctx, fn, calls, warmup, capi.STAGE_INTERPOLATE)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--sizes", default="1080p,4k,8k")
-    ap.add_argument("--json", default=None)
-    a = ap.parse_args()
+    a = arguments("1080p,4k,8k")
     rows = []
     with capi.Context(0) as ctx:
         ctx.set_semantics(capi.SEMANTICS_INTENDED)
@@ -74,13 +54,10 @@ def main():
                 r["shader_x3_us"] = per_call_us(ctx, lambda: ctx.interpolate_multi(p, c, m, outs, FACTORS), a.calls, a.warmup)
                 r["compensated_x3_us"] = per_call_us(ctx, lambda: ctx.interpolate_compensated_multi(p, c, m, outs, FACTORS, ms),
                                                      a.calls, a.warmup)
-                rows.append(r)
-                print(json.dumps(r), flush=True)
+                emit(rows, r)
                 for f in [p, c, m] + outs:
                     ctx.destroy_frame(f)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(rows, f, indent=1)
+    write_json(a.json, rows)
 
 
 if __name__ == "__main__":

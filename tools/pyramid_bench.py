@@ -5,18 +5,12 @@
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stage_bench import SIZES, arguments, emit, per_call_ms, write_json      # (puts the repository root on sys.path)
 from linux_fg_amd import capi, synth  # noqa: E402
-
-SIZES = {"1080p": (1920, 1080), "4k": (3840, 2160)}
-
 
 def contents(w, h):
     prev = synth.make_prev(w, h)
@@ -30,26 +24,12 @@ def contents(w, h):
     yield "static", prev, prev.copy()
 
 
-def per_call_ms(ctx, fn, calls, warmup):
-    for _ in range(warmup):
-        fn()
-    ctx.sync()
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    for _ in range(calls):
-        fn()
-    ms = [ctx.profile_get(s)[0] for s in (capi.STAGE_MOTION, capi.STAGE_INTERPOLATE)]
-    ctx.profile_enable(False)
-    return sum(ms) / calls
+def per_call(ctx, fn, calls, warmup):
+    return per_call_ms(ctx, fn, calls, warmup, capi.STAGE_MOTION, capi.STAGE_INTERPOLATE)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--sizes", default="1080p,4k")
-    ap.add_argument("--json", default=None)
-    a = ap.parse_args()
+    a = arguments("1080p,4k")
     rows = []
     with capi.Context(0) as ctx:
         ctx.set_semantics(capi.SEMANTICS_INTENDED)
@@ -60,23 +40,20 @@ def main():
                 m = ctx.create_frame(w, h, capi.FORMAT_MV_S8X2)
                 o = ctx.create_frame(w, h)
                 r = {"size": size, "content": name}
-                r["pyramid_ms"] = per_call_ms(ctx, lambda: ctx.motion_pyramid(p, c, m, 2, 16, 2), a.calls, a.warmup)
-                r["full_search_ms"] = per_call_ms(ctx, lambda: ctx.motion(p, c, m), a.calls, a.warmup)
+                r["pyramid_ms"] = per_call(ctx, lambda: ctx.motion_pyramid(p, c, m, 2, 16, 2), a.calls, a.warmup)
+                r["full_search_ms"] = per_call(ctx, lambda: ctx.motion(p, c, m), a.calls, a.warmup)
                 for est, key in ((capi.ESTIMATOR_PYRAMID, "frames_pyramid_ms"), (capi.ESTIMATOR_FULL_SEARCH, "frames_full_ms")):
                     ctx.set_motion_estimator(est)
-                    r[key] = per_call_ms(ctx, lambda: ctx.interpolate_frames(p, c, o, 0.5), a.calls, a.warmup)
+                    r[key] = per_call(ctx, lambda: ctx.interpolate_frames(p, c, o, 0.5), a.calls, a.warmup)
                 ctx.set_motion_estimator(capi.ESTIMATOR_FULL_SEARCH)
-                rows.append(r)
-                print(json.dumps(r), flush=True)
+                emit(rows, r)
                 for f in (p, c, m, o):
                     ctx.destroy_frame(f)
     for size in a.sizes.split(","):
         t = [r["pyramid_ms"] for r in rows if r["size"] == size]
         print(json.dumps({"size": size, "pyramid_min_ms": min(t), "pyramid_max_ms": max(t),
                           "pyramid_spread_pct": 100.0 * (max(t) - min(t)) / min(t)}))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(rows, f, indent=1)
+    write_json(a.json, rows)
 
 
 if __name__ == "__main__":
