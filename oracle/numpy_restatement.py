@@ -115,7 +115,9 @@ def motion(prev: np.ndarray, curr: np.ndarray, block_size: int = 8, search_radiu
     return best
 
 
-def interpolate(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, factor: float = 0.5) -> np.ndarray:
+def interpolate(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, factor: float = 0.5, semantics: int = 0) -> np.ndarray:
+    """semantics 1 (the opt-in "intended" variant, lfg_oracle_interpolate_ex): the vector is divided by the image size, in
+    fp32, before it is added to uv; nothing else changes."""
     H, W = curr.shape[:2]
     t = F(factor)
     px = np.arange(W, dtype=F)[None, :].repeat(H, 0)
@@ -123,6 +125,8 @@ def interpolate(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, factor: floa
     uvx = (px + F(0.5)) / F(W)
     uvy = (py + F(0.5)) / F(H)
     mx, my = mv[..., 0].astype(F), mv[..., 1].astype(F)
+    if semantics != 0:
+        mx, my = mx / F(W), my / F(H)
 
     def sample(img, scale):
         sx = uvx + mx * scale

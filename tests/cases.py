@@ -1,5 +1,6 @@
 """Inputs that the CPU tests of the models and the GPU tests share, so that the two cannot drift apart: the factors of the
-compensated interpolator, the scene and the CPU chain of the dispatch tests (tests/test_gpu_dispatch.py), and the hand-made
+compensated interpolator, the scene on which lfg_interpolate samples (tests/test_sampling_scene.py,
+tests/test_gpu_interpolate_scale.py), the scene and the CPU chain of the dispatch tests (tests/test_gpu_dispatch.py), and the hand-made
 cases of test_refine_model.py, test_mc_model.py and test_pyramid_model.py that are stated through the public inputs alone."""
 from __future__ import annotations
 
@@ -46,6 +47,32 @@ def field(kind, w, h, seed):
         mv = rng.integers(-128, 128, (h, w, 2)).astype(np.int8)
         curr = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
     return prev, curr, mv
+
+
+def sampling_scene(w, h, seed):
+    """(prev, curr, mv int8) on which lfg_interpolate samples, under both semantics: prev and curr are independent uniform
+    noise and the vectors are drawn per pixel, so that every row and column carries non-trivial ones -- about 55 % are (0, 0)
+    (both samples inside the image under either semantics), 35 % small, from [-3, 3]^2 (under the reference semantics a
+    sample of theirs leaves [0, 1] and reads as 0; under the intended semantics both move by a few pixels, mostly to
+    fractional positions), 10 % from the full byte range.  What the scene is held to: tests/test_sampling_scene.py."""
+    rng = np.random.default_rng(seed)
+    prev = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    curr = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    small = rng.integers(-3, 4, (h, w, 2)).astype(np.int8)
+    large = rng.integers(-128, 128, (h, w, 2)).astype(np.int8)
+    r = rng.random((h, w))
+    mv = np.zeros((h, w, 2), np.int8)
+    mv[r < 0.45] = small[r < 0.45]
+    mv[r < 0.10] = large[r < 0.10]
+    return prev, curr, mv
+
+
+SAMPLING_FACTORS = (0.5, 0.3)                       # a dyadic factor and one that is inexact in fp32
+
+
+def sampling_scene_of(w, h):
+    """The sampling scene the CPU test of its power and the GPU tests of lfg_interpolate_scale both take at w x h."""
+    return sampling_scene(w, h, 1000 * w + h)
 
 
 def warp(prev, field):

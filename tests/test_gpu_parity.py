@@ -10,7 +10,7 @@ import pytest
 
 from linux_fg_amd import synth
 from oracle import scale_f64 as f64
-from tests.gpu_kit import ctx, pitched as _pitched
+from tests.gpu_kit import assert_matches_f64, ctx, first_bad, pitched as _pitched, seam_rows as _seam_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -59,26 +59,6 @@ def assert_within_1lsb(got, want, max_mismatch=0.05):
     frac = float((d != 0).mean())
     assert frac <= max_mismatch, f"{frac:.4%} of bytes differ by 1 LSB"
     return frac
-
-
-def assert_matches_f64(got, V, eps=1e-3, what=""):
-    """The kernel's bytes against the float64 model's unrounded values V (oracle/scale_f64.py): within half an LSB plus
-    eps everywhere, and exactly rint(clip(V)) wherever V is further than eps from a rounding boundary.  The kernels'
-    fp32 arithmetic stays within ~1e-4 LSB of V, so this is ~500 times tighter than +-1 LSB; with the bound on the
-    shader (tests/test_scale_model.py) it gives +-1 LSB against the shader for every input.  Returns the near-ties."""
-    c = np.clip(V, 0.0, 255.0)
-    d = np.abs(got.astype(np.float64) - c)
-    at = tuple(int(i) for i in np.unravel_index(d.argmax(), d.shape))
-    assert d.max() <= 0.5 + eps, f"{what}: |got - V| = {d.max():.5f} at {at} (got {got[at]}, V {V[at]:.5f})"
-    near = f64.near_half(V, eps)
-    bad = ~near & (got != np.rint(c))
-    if bad.any():
-        at = tuple(int(i) for i in np.argwhere(bad)[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {got.size} bytes differ from rint(V) away from a tie, "
-                             f"first at {at} (got {got[at]}, V {V[at]:.5f})")
-    ties = int(near.sum())
-    print(f"f64 model {what}: {ties} near-ties in {got.size} bytes")
-    return ties
 
 
 # ------------------------------------------------------------------------------ scale
@@ -178,23 +158,6 @@ def test_scale_1080p_to_4k_every_pixel_repeated(ctx, oracle):
 #
 # Every pixel held to oracle/scale_f64.py with assert_matches_f64, and each case asserts which kernel ran
 # (lfg_scale_last_kernel: 0 generic, 1 exact 2x, 2 fused interpolate -> 2x), so a sweep cannot quietly test the other one.
-
-def _seam_rows(in_h):
-    """Input rows that straddle the 2x kernel's strip and XCD-band seams: an impulse at row first - 3 of a strip
-    reaches the last output rows of the strip above it and the first of its own."""
-    import ctypes
-    from linux_fg_amd import capi
-    lib = capi.load()
-    per, first, steps = ctypes.c_uint32(), ctypes.c_int32(), ctypes.c_int32()
-    assert lib.lfg_diag_scale_2x_strip(in_h, 0, 0, ctypes.byref(per), None, None) == 0
-    rows = set()
-    for x in range(8):
-        for i in range(per.value):
-            assert lib.lfg_diag_scale_2x_strip(in_h, x, i, None, ctypes.byref(first), ctypes.byref(steps)) == 0
-            if steps.value > 0:
-                rows.add(first.value - 3)
-    return sorted(r for r in rows if 0 <= r < in_h)
-
 
 def _scale_checked(ctx, src, ow, oh, kernel, what):
     got = run_scale(ctx, src, ow, oh)
@@ -1021,7 +984,7 @@ def test_interpolate_multi_intended_semantics_and_validation(intended, oracle):
         one = run_interpolate(intended, prev, curr, mv, t)            # the single-factor kernel, same semantics
         assert (g == one).all()
         want = oracle.interpolate(prev, curr, mv.astype(np.float32), t, semantics=oracle.INTENDED)
-        assert np.abs(g.astype(np.int16) - want.astype(np.int16)).max() <= 1
+        assert (g == want).all(), f"t = {t}: {first_bad(g, want)}"
     a, b = intended.create_frame(w, h), intended.create_frame(w, h)
     m = intended.create_frame(w, h, capi.FORMAT_MV_S8X2)
     small = intended.create_frame(w // 2, h)
@@ -1102,7 +1065,11 @@ def test_interpolate_scale_equals_the_two_stages(ctx, oracle, wh, out_wh):
 
 
 def test_interpolate_scale_1080p_to_4k(ctx, oracle):
-    """The benchmark's input-resolution variant at full size: fused kernel == the two stages, on the device's own motion vectors."""
+    """The benchmark's input-resolution variant at full size: fused kernel == the two stages, on the device's own motion vectors.
+    What the frame holds: on this (3, -2) pan under the reference semantics 7 of the 2,073,600 vectors are (0, 0) (the CPU
+    oracle's count); everywhere else a sample leaves [0, 1], and all but 44 pixels of the generated frame are black.  So this
+    holds the benchmark's own input to "black upscales to black" on every route, and little more.  Frames that sample are in
+    tests/test_gpu_interpolate_scale.py."""
     from linux_fg_amd import capi
     prev, curr = synth.make_pair(1920, 1080, stream=0, shift=(3, -2))
     p, c = ctx.frame_from(prev), ctx.frame_from(curr)
@@ -1541,9 +1508,7 @@ def test_intended_interpolate_matches_oracle(intended, oracle, t):
     mv = RNG.integers(-16, 17, size=(h, w, 2)).astype(np.int8)
     got = run_interpolate(intended, prev, curr, mv, t)
     want = oracle.interpolate(prev, curr, mv.astype(np.float32), t, semantics=oracle.INTENDED)
-    d = np.abs(got.astype(np.int16) - want.astype(np.int16))
-    assert d.max() <= 1, f"max diff {d.max()}"
-    assert (d != 0).mean() < 1e-3                                         # in practice identical
+    assert (got == want).all(), first_bad(got, want)                    # the same IEEE operations, no contraction
     lit = oracle.interpolate(prev, curr, mv.astype(np.float32), t)
     assert (want != lit).any()
 
@@ -1561,9 +1526,7 @@ def test_intended_interpolate_full_hd_every_pixel(intended, oracle):
     for t in (0.5, 0.25):
         got = run_interpolate(intended, prev, curr, mv, t)
         want = oracle.interpolate(prev, curr, mv.astype(np.float32), t, semantics=oracle.INTENDED)
-        d = np.abs(got.astype(np.int16) - want.astype(np.int16))
-        assert d.max() <= 1, f"max diff {d.max()}"
-        assert (d != 0).mean() < 1e-3
+        assert (got == want).all(), f"t = {t}: {first_bad(got, want)}"
 
 
 def test_lanes_keep_frames_in_flight_apart():

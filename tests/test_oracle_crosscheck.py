@@ -8,6 +8,7 @@ import pytest
 
 from linux_fg_amd import synth
 from oracle import numpy_restatement as npr
+from tests import cases
 
 RNG = np.random.default_rng(99)
 
@@ -57,3 +58,18 @@ def test_interpolate_non_pow2_width_c_equals_numpy(oracle):
     p, c = rand_frame(W, H), rand_frame(W, H)
     mv = np.zeros((H, W, 2), np.float32)
     assert (oracle.interpolate(p, c, mv, 0.5) == npr.interpolate(p, c, mv, 0.5)).all()
+
+
+@pytest.mark.parametrize("t", [0.25, 0.5, 0.3, 0.9])
+@pytest.mark.parametrize("wh", [(64, 32), (30, 18)])
+def test_interpolate_both_semantics_c_equals_numpy(oracle, wh, t):
+    """On the scene that samples (zero, small and full-range vectors per pixel), at a size where uv and the vector's division
+    by the image size are exact in fp32 and at one where they are not: the intended semantics have a second restatement too."""
+    p, c, mv = cases.sampling_scene(*wh, seed=7)
+    mv = mv.astype(np.float32)
+    both = []
+    for sem in (oracle.REFERENCE, oracle.INTENDED):
+        a = oracle.interpolate(p, c, mv, t, semantics=sem)
+        assert (a == npr.interpolate(p, c, mv, t, semantics=sem)).all(), f"semantics {sem}"
+        both.append(a)
+    assert (both[0] != both[1]).any()
