@@ -398,6 +398,53 @@ int  lfg_motion_refine(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
  * Any other radius: LFG_ERR_INVALID and no change. */
 int  lfg_set_vector_refinement(lfg_context *ctx, int radius);
 
+/* Pair statistics: how well a vector field explains a pair of frames.  No reference counterpart.  A pair whose two frames do
+ * not show the same scene (a cut, a cold start, a channel change) has no vectors that mean anything, and hardly any pixel
+ * passes the compensated interpolator's match gate; moving content of every kind passes it almost everywhere (DESIGN.md
+ * section 4.9: above 750 per thousand against below 30).  Integer arithmetic only; it does not depend on lfg_set_semantics.
+ *   Inputs: prev, curr RGBA8 and mv LFG_FORMAT_MV_S8X2 (any byte values), all W x H; 0 <= match_sad <= 1020.
+ *   With v = mv(q): sad(q) = sum over c of |curr(q)_c - prev(q + v)_c|, prev outside the image read as 0 -- the match gate of
+ *   lfg_interpolate_compensated, word for word.
+ *   pixels = W * H;  matched = the number of q with sad(q) <= match_sad;  sad_sum = the sum over q of sad(q).
+ * All three are integers, so neither the order of evaluation nor any tiling changes a result.  The call WRITES the three
+ * words of `device_stats` (24 bytes of device memory, 8-byte aligned): it does not accumulate into them.
+ * Frames: 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4), 2-byte aligned mv.  Any violation, a NULL pointer or
+ * a misaligned device_stats returns LFG_ERR_INVALID before anything is enqueued.  Enqueued on the selected lane (a clear of
+ * the record, one launch of a fixed grid); keeps no device memory; timed under LFG_STAGE_MOTION. */
+typedef struct lfg_pair_stats { uint64_t pixels, matched, sad_sum; } lfg_pair_stats;
+int  lfg_pair_match(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                    int match_sad, void *device_stats /* 24 bytes of device memory, 8-byte aligned */);
+/* The fallback of a cut: a source frame instead of a generated one.  No reference counterpart.  `device_stats` is a record as
+ * lfg_pair_match writes it, read ON THE DEVICE when the call's turn on the lane comes: the host never waits for the verdict.
+ *   The pair is a cut when matched * 1000 < min_matched_permille * pixels, in 64 bits; so 0 never cuts.
+ *   A cut: every outs[i] becomes a copy of prev where factors[i] < 0.5f and of curr otherwise (a NaN factor: curr).  Only the
+ *   width * 4 bytes of each row are written, never the row padding.  No cut: no byte of any output is written.
+ * 0 <= min_matched_permille <= 1000, 1 <= count <= LFG_MAX_FACTORS; prev, curr and every output RGBA8 of one size, 4-byte
+ * aligned rows, the outputs overlapping neither an input nor each other; device_stats 8-byte aligned.  Any violation or a
+ * NULL pointer returns LFG_ERR_INVALID before anything is enqueued.  One launch of a small fixed grid on the selected lane,
+ * for all outputs; every wave of it reads the record and returns if the pair is no cut.  Keeps no device memory; timed
+ * under LFG_STAGE_INTERPOLATE. */
+int  lfg_cut_fallback(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
+                      int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count);
+/* Cut detection in lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else).  No reference counterpart.
+ *   min_matched_permille = -1 (default): off; every path as before;
+ *   0 .. 1000: the vectors as before (the selected estimator, then the refinement if it is on); lfg_pair_match on those
+ *       vectors with the context's match_sad (lfg_set_interpolator; 48 unless changed) into a record the lane owns; a copy of
+ *       that record into pinned host memory with an event behind it; the selected interpolator as before; lfg_cut_fallback
+ *       with this threshold on its outputs.  The outputs must then satisfy lfg_cut_fallback's rules as well, which are
+ *       checked before anything is enqueued.  lfg_set_fused_motion_interpolate does not apply.  The record, its pinned copy
+ *       and the event are made by a lane's first such call and freed with the lane.
+ * Any other value: LFG_ERR_INVALID and no change.
+ * lfg_last_pair_stats: the record of the SELECTED lane's last such call, and in *out_cut whether that call was a cut under the
+ * threshold it ran with (either pointer may be NULL).  It waits for that record's event only -- if the lane has been
+ * synchronised since, it returns at once -- and returns LFG_ERR_INVALID if the lane has made no such call.
+ * What this does NOT do: it does not make a cut cheap.  The estimator and the interpolator still run, and the full search on an
+ * uncorrelated 4K pair still costs about 7.5 ms; skipping that work would take the host waiting for
+ * the verdict, or a change to the existing kernels.  lfg_motion_pyramid costs the same on any content, so on that route a cut
+ * costs nothing extra. */
+int  lfg_set_cut_detection(lfg_context *ctx, int min_matched_permille);   /* -1 (default): off; 0 .. 1000 */
+int  lfg_last_pair_stats(lfg_context *ctx, lfg_pair_stats *out_stats, int *out_cut);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

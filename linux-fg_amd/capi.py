@@ -39,6 +39,14 @@ class Frame(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class PairStats(ctypes.Structure):
+    """struct lfg_pair_stats."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("matched", ctypes.c_uint64), ("sad_sum", ctypes.c_uint64)]
+
+    def as_tuple(self):
+        return int(self.pixels), int(self.matched), int(self.sad_sum)
+
+
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 _FP = ctypes.POINTER(Frame)
 
@@ -98,6 +106,10 @@ SIGNATURES = {
     "lfg_set_interpolator": (_i, [_vp, _i, _i]),
     "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_vector_refinement": (_i, [_vp, _i]),
+    "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
+    "lfg_cut_fallback": (_i, [_vp, _FP, _FP, _vp, _i, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
+    "lfg_set_cut_detection": (_i, [_vp, _i]),
+    "lfg_last_pair_stats": (_i, [_vp, ctypes.POINTER(PairStats), ctypes.POINTER(_i)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
     "lfg_mv_export_rgba32f": (_i, [_vp, _FP, _vp]),
@@ -414,6 +426,42 @@ class Context:
         """-1 (default: off) or 0..2: lfg_motion_refine with that radius between the estimator and the interpolator of
         interpolate_frames[_multi]."""
         self._check(self.lib.lfg_set_vector_refinement(self.h, int(radius)), "lfg_set_vector_refinement")
+
+    # -- scene-cut detection.  A record is 24 bytes of device memory: here a 6 x 1 RGBA8 frame, so upload() and download()
+    # move it (write_pair_record / read_pair_record).
+    def create_pair_record(self) -> Frame:
+        return self.create_frame(ctypes.sizeof(PairStats) // 4, 1)
+
+    def write_pair_record(self, record: Frame, pixels: int, matched: int, sad_sum: int):
+        self.upload(record, np.array([pixels, matched, sad_sum], np.uint64).view(np.uint8).reshape(1, -1, 4))
+
+    def read_pair_record(self, record: Frame):
+        """(pixels, matched, sad_sum) of a record in device memory; waits for the context."""
+        return tuple(int(v) for v in self.download(record).reshape(-1).view(np.uint64))
+
+    def pair_match(self, prev: Frame, curr: Frame, mv: Frame, record: Frame, match_sad: int = DEFAULT_MATCH_SAD):
+        """Pair statistics (lfg_pair_match): how many pixels pass the compensated interpolator's match gate under the
+        vectors `mv`, and the sum of their SADs, written into `record` (create_pair_record)."""
+        self._check(self.lib.lfg_pair_match(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv), int(match_sad),
+                                            _vp(record.data)), "lfg_pair_match")
+
+    def cut_fallback(self, prev: Frame, curr: Frame, record: Frame, min_matched_permille: int, outs, factors):
+        """lfg_cut_fallback: where `record` says the pair is a cut, every output becomes prev (factor < 0.5) or curr;
+        otherwise nothing is written.  The decision is taken on the device."""
+        po, pf, n = self._multi_args(outs, factors)
+        self._check(self.lib.lfg_cut_fallback(self.h, ctypes.byref(prev), ctypes.byref(curr), _vp(record.data),
+                                              int(min_matched_permille), po, pf, n), "lfg_cut_fallback")
+
+    def set_cut_detection(self, min_matched_permille: int):
+        """-1 (default: off) or 0..1000: interpolate_frames[_multi] measure each pair (lfg_pair_match on the vectors they
+        use) and show a source frame instead of a generated one where fewer than that many pixels per thousand match."""
+        self._check(self.lib.lfg_set_cut_detection(self.h, int(min_matched_permille)), "lfg_set_cut_detection")
+
+    def last_pair_stats(self):
+        """((pixels, matched, sad_sum), cut) of the selected lane's last call with cut detection on (lfg_last_pair_stats)."""
+        s, cut = PairStats(), ctypes.c_int()
+        self._check(self.lib.lfg_last_pair_stats(self.h, ctypes.byref(s), ctypes.byref(cut)), "lfg_last_pair_stats")
+        return s.as_tuple(), bool(cut.value)
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

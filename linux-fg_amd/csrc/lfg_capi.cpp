@@ -486,6 +486,9 @@ void lane_release(lfg_lane_state &l) {
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
     if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
+    if (l.cut.event) (void)hipEventDestroy(l.cut.event);
+    if (l.cut.pinned) (void)hipHostFree(l.cut.pinned);
+    if (l.cut.device) (void)hipFree(l.cut.device);
     if (l.own_stream) (void)hipStreamDestroy(l.own_stream);
     l = lfg_lane_state{};
 }
@@ -1138,11 +1141,52 @@ int frame_vectors(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr
     return lfg_motion_refine(ctx, prev, curr, &cur.mv_tmp, &cur.mv_refined, ctx->refine_radius);
 }
 
+int cut_fallback_check(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
+                       int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count);
+int cut_fallback_enqueue(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
+                         int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count);
+
+// lfg_interpolate_frames[_multi] with lfg_set_cut_detection on: the vectors, their match statistics into the lane's record
+// (and a copy of it on its way to the host, for lfg_last_pair_stats), the selected interpolator, then the fallback, which
+// reads the record on the device.  Everything that can fail on an argument is checked before the first launch.
+int detecting_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame *const *outs, const float *factors,
+                     uint32_t count, bool multi) {
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    lfg::CutDetectState &cut = ctx->cur().cut;
+    if (!cut.device) LFG_HIP(ctx, hipMalloc((void **)&cut.device, sizeof(lfg_pair_stats)));
+    if (!cut.pinned) LFG_HIP(ctx, hipHostMalloc((void **)&cut.pinned, sizeof(lfg_pair_stats), hipHostMallocDefault));
+    if (!cut.event) LFG_HIP(ctx, hipEventCreateWithFlags(&cut.event, hipEventDisableTiming));
+    const int permille = ctx->cut_permille;
+    int rc = cut_fallback_check(ctx, prev, curr, cut.device, permille, outs, factors, count);
+    if (rc != LFG_OK) return rc;
+    const lfg_frame *vectors = nullptr;
+    rc = frame_vectors(ctx, prev, curr, &vectors);
+    if (rc != LFG_OK) return rc;
+    rc = lfg_pair_match(ctx, prev, curr, vectors, ctx->match_sad, cut.device);
+    if (rc != LFG_OK) return rc;
+    LFG_HIP(ctx, hipMemcpyAsync(cut.pinned, cut.device, sizeof(lfg_pair_stats), hipMemcpyDeviceToHost, ctx->cur().stream));
+    LFG_HIP(ctx, hipEventRecord(cut.event, ctx->cur().stream));
+    cut.recorded = true;
+    cut.permille = permille;
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
+        rc = multi ? lfg_interpolate_compensated_multi(ctx, prev, curr, vectors, outs, factors, count, ctx->match_sad)
+                   : lfg_interpolate_compensated(ctx, prev, curr, vectors, outs[0], factors[0], ctx->match_sad);
+    else
+        rc = multi ? lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count)
+                   : lfg_interpolate(ctx, prev, curr, vectors, outs[0], factors[0]);
+    if (rc != LFG_OK) return rc;
+    return cut_fallback_enqueue(ctx, prev, curr, cut.device, permille, outs, factors, count);
+}
+
 }  // namespace
 
 LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                       lfg_frame *out, float factor) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: NULL argument");
+    if (ctx->cut_permille >= 0) {
+        lfg_frame *const outs[1] = {out};
+        return detecting_frames(ctx, prev, curr, outs, &factor, 1, false);
+    }
     // The fused motion kernels are the full search's and write the shader's interpolation: every other setting takes the stages.
     if (ctx->fuse_motion_interpolate && ctx->estimator == LFG_ESTIMATOR_FULL_SEARCH && ctx->refine_radius < 0 &&
         ctx->interpolator == LFG_INTERPOLATOR_SHADER) {
@@ -1204,6 +1248,7 @@ LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, co
 LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                             lfg_frame *const *outs, const float *factors, uint32_t count) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames_multi: NULL argument");
+    if (ctx->cut_permille >= 0) return detecting_frames(ctx, prev, curr, outs, factors, count, true);
     const lfg_frame *vectors = nullptr;
     int rc = frame_vectors(ctx, prev, curr, &vectors);
     if (rc != LFG_OK) return rc;
@@ -1311,6 +1356,94 @@ LFG_EXPORT int lfg_set_vector_refinement(lfg_context *ctx, int radius) {
     if (!ctx) return LFG_ERR_INVALID;
     if (radius < -1 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_set_vector_refinement: radius must be -1 (off) or in [0, 2]");
     ctx->refine_radius = radius;
+    return LFG_OK;
+}
+
+// ---- scene-cut detection (pair_stats.hip)
+
+LFG_EXPORT int lfg_pair_match(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                              int match_sad, void *device_stats) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(mv, LFG_FORMAT_MV_S8X2))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_pair_match: prev/curr must be RGBA8 and mv MV_S8X2, all non-empty");
+    if (!same_size(prev, curr) || !same_size(curr, mv))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_pair_match: prev, curr and mv differ in size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u || mv->pitch % 2u || (uintptr_t)mv->data % 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_pair_match: RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
+    if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, "lfg_pair_match: match_sad must be in [0, 1020]");
+    if (!device_stats || (uintptr_t)device_stats % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_pair_match: device_stats must be non-NULL and 8-byte aligned");
+    StageTimer timer(ctx, LFG_STAGE_MOTION);
+    hipError_t e = lfg::launch_pair_match(ctx->cur().stream, *prev, *curr, *mv, match_sad, ctx->device_cus, device_stats);
+    if (e != hipSuccess) return fail_hip(ctx, e, "pair match kernel launch");
+    return LFG_OK;
+}
+
+namespace {
+
+int cut_fallback_check(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
+                       int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count) {
+    if (!outs || !factors || count == 0 || count > LFG_MAX_FACTORS)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: count must be in [1, LFG_MAX_FACTORS] and outs/factors non-NULL");
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: prev/curr must be non-empty RGBA8");
+    if (!same_size(prev, curr)) return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: prev and curr differ in size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: RGBA8 frames must be 4-byte aligned");
+    if (!device_stats || (uintptr_t)device_stats % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: device_stats must be non-NULL and 8-byte aligned");
+    if (min_matched_permille < 0 || min_matched_permille > 1000)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: min_matched_permille must be in [0, 1000]");
+    for (uint32_t i = 0; i < count; ++i) {
+        const lfg_frame *o = outs[i];
+        if (!frame_ok(o, LFG_FORMAT_RGBA8_UNORM) || !same_size(curr, o) || o->pitch % 4u || (uintptr_t)o->data % 4u)
+            return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: bad output frame (NULL, empty, wrong format, size or alignment)");
+        if (frames_overlap(o, prev) || frames_overlap(o, curr))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: an output overlaps an input");
+        for (uint32_t j = 0; j < i; ++j)
+            if (frames_overlap(outs[j], o)) return fail(ctx, LFG_ERR_INVALID, "lfg_cut_fallback: two outputs overlap each other");
+    }
+    return LFG_OK;
+}
+
+int cut_fallback_enqueue(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
+                         int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count) {
+    StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
+    hipError_t e = lfg::launch_cut_fallback(ctx->cur().stream, *prev, *curr, device_stats, min_matched_permille, outs, factors,
+                                            (int)count, ctx->device_cus);
+    if (e != hipSuccess) return fail_hip(ctx, e, "cut fallback kernel launch");
+    return LFG_OK;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_cut_fallback(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
+                                int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = cut_fallback_check(ctx, prev, curr, device_stats, min_matched_permille, outs, factors, count);
+    if (rc != LFG_OK) return rc;
+    return cut_fallback_enqueue(ctx, prev, curr, device_stats, min_matched_permille, outs, factors, count);
+}
+
+LFG_EXPORT int lfg_set_cut_detection(lfg_context *ctx, int min_matched_permille) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (min_matched_permille < -1 || min_matched_permille > 1000)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_cut_detection: min_matched_permille must be -1 (off) or in [0, 1000]");
+    ctx->cut_permille = min_matched_permille;
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_last_pair_stats(lfg_context *ctx, lfg_pair_stats *out_stats, int *out_cut) {
+    if (!ctx) return LFG_ERR_INVALID;
+    const lfg::CutDetectState &cut = ctx->cur().cut;
+    if (!cut.recorded) return fail(ctx, LFG_ERR_INVALID, "lfg_last_pair_stats: the selected lane has made no call with cut detection on");
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    LFG_HIP(ctx, hipEventSynchronize(cut.event));
+    const lfg_pair_stats s = *cut.pinned;
+    if (out_stats) *out_stats = s;
+    if (out_cut) *out_cut = s.matched * 1000ull < (uint64_t)cut.permille * s.pixels ? 1 : 0;
     return LFG_OK;
 }
 

@@ -147,6 +147,16 @@ struct ProfileSlot {
     int stage = 0;
 };
 
+// Scene-cut detection behind lfg_interpolate_frames[_multi] (lfg_set_cut_detection): the lane's record on the device, the
+// pinned copy that each detecting call refreshes, and the event behind that copy.  Made by the lane's first such call.
+struct CutDetectState {
+    lfg_pair_stats *device = nullptr;          // what lfg_pair_match writes and lfg_cut_fallback reads
+    lfg_pair_stats *pinned = nullptr;          // host copy (lfg_last_pair_stats)
+    hipEvent_t event = nullptr;                // recorded behind the copy
+    bool recorded = false;                     // the lane has made a detecting call
+    int permille = -1;                         // the threshold that call ran with
+};
+
 }  // namespace lfg
 
 // What a lane (lfg_lanes: one of several frames in flight on a GPU) owns apart from the context: its stream, the temporaries
@@ -171,6 +181,7 @@ struct lfg_lane_state {
     hipEvent_t mark = nullptr;                 // lfg_lane_mark
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
+    lfg::CutDetectState cut;                   // lfg_set_cut_detection: the record of the lane's last detecting call
 };
 
 struct lfg_context {
@@ -195,6 +206,7 @@ struct lfg_context {
     int interpolator = 0;                      // lfg_interpolate_frames[_multi]: LFG_INTERPOLATOR_SHADER / _COMPENSATED (lfg_set_interpolator)
     int match_sad = 48;                        // ... and the compensated interpolator's match gate
     int refine_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_refine's radius, -1 = off (lfg_set_vector_refinement)
+    int cut_permille = -1;                     // lfg_interpolate_frames[_multi]: lfg_cut_fallback's threshold, -1 = off (lfg_set_cut_detection)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -300,6 +312,12 @@ hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, 
 // Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
                                 const lfg_frame &mvOut, int radius);
+// Scene-cut detection (pair_stats.hip): launch_pair_match clears the 24-byte record `stats` and enqueues the fixed grid that
+// fills it; launch_cut_fallback enqueues the kernel that reads it and, on a cut, copies prev or curr over every output.
+hipError_t launch_pair_match(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv, int matchSad,
+                             int deviceCus, void *stats);
+hipError_t launch_cut_fallback(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const void *stats, int minMatchedPermille,
+                               const lfg_frame *const *outs, const float *factors, int count, int deviceCus);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

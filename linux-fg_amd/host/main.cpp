@@ -39,6 +39,8 @@ static void PrintUsage() {
               << "                           compensated: vectors projected to the frame's time, holes filled; wants --semantics intended)\n"
               << "  --refine-vectors R       Per-pixel vector refinement between motion and interpolation (default -1: off;\n"
               << "                           0..2: each pixel takes the nearby vector that fits its (2R+1)^2 window best)\n"
+              << "  --cut-threshold P        Scene-cut detection (default -1: off; 0..1000: a pair of which fewer than P pixels per\n"
+              << "                           thousand match under its vectors shows a source frame instead of a generated one)\n"
               << "  --frames N               Number of input frames to process (default: 10)\n"
               << "  --device N               HIP device ordinal (default: 0)\n"
               << "  --dump-dir DIR           Write every presented frame to DIR as raw RGBA8\n"
@@ -63,7 +65,7 @@ int main(int argc, char* argv[]) {
     int frames = 10, device = 0;
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
-    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1;
+    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false;
@@ -116,6 +118,12 @@ int main(int argc, char* argv[]) {
             if (!end || *end != '\0' || r < -1 || r > 2) { LOG_ERROR("Invalid --refine-vectors (-1, 0, 1 or 2)"); return 1; }
             refineRadius = (int)r;
         }
+        else if (strcmp(argv[i], "--cut-threshold") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long p = strtol(argv[++i], &end, 10);
+            if (!end || *end != '\0' || p < -1 || p > 1000) { LOG_ERROR("Invalid --cut-threshold (-1, or 0 to 1000)"); return 1; }
+            cutThreshold = (int)p;
+        }
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--device") == 0 && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--dump-dir") == 0 && i + 1 < argc) dumpDir = argv[++i];
@@ -152,7 +160,8 @@ int main(int argc, char* argv[]) {
     if (lfg_set_semantics(HipContext::Get().GetDevice(), semantics) != LFG_OK ||
         lfg_set_motion_estimator(HipContext::Get().GetDevice(), estimator) != LFG_OK ||
         lfg_set_interpolator(HipContext::Get().GetDevice(), interpolator, 48) != LFG_OK ||
-        lfg_set_vector_refinement(HipContext::Get().GetDevice(), refineRadius) != LFG_OK) {
+        lfg_set_vector_refinement(HipContext::Get().GetDevice(), refineRadius) != LFG_OK ||
+        lfg_set_cut_detection(HipContext::Get().GetDevice(), cutThreshold) != LFG_OK) {
         LOG_ERROR("Failed to set the motion options: ", lfg_last_error(HipContext::Get().GetDevice()));
         HipContext::Get().Cleanup();
         return 1;
@@ -177,6 +186,7 @@ int main(int argc, char* argv[]) {
     }
     Scaler::Get().SetPipelined(!syncPresent);
     Scaler::Get().SetFramesInFlight(inFlight);
+    Scaler::Get().SetCutCounting(cutThreshold >= 0);
     if (!factors.empty()) Scaler::Get().SetInterpolationFactors(factors);
     FILE* rawOut = nullptr;
     if (!outputRaw.empty()) {
@@ -213,16 +223,17 @@ int main(int argc, char* argv[]) {
     ok = ok && Scaler::Get().Flush();                           // the last call's frames
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
+    const uint64_t cuts = Scaler::Get().GetCuts();
     // Teardown order as src/main.cpp:138-141.
     Scaler::Get().Cleanup();
     FrameManager::Get().Cleanup();
     HipContext::Get().Cleanup();
     if (!ok) { LOG_ERROR("ProcessFrame failed: ", Logger::Get().GetLastError()); return 1; }
     if (rawOut && rawOut != stdout) fclose(rawOut);
-    fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"seconds\": %.4f, "
+    fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
            "\"note\": \"includes %s, PCIe upload and readback\"}\n",
-           frames, (unsigned long long)presented, (unsigned long long)generated, sec, presented / sec,
+           frames, (unsigned long long)presented, (unsigned long long)generated, (unsigned long long)cuts, sec, presented / sec,
            (unsigned long long)checksum, syncPresent ? "false" : "true", replay, presentNull ? "true" : "false", inFlight,
            replay > 0 ? "one memcpy per input frame into the staging slot" : "host frame synthesis");
     return 0;

@@ -168,7 +168,7 @@ bool Scaler::QueueReadback(Frame& frame, bool interpolated) {
         return false;
     }
     m_lastReadback[frame.data] = slot;
-    m_pending.push_back(Pending{host, slot, frame.width, frame.height, interpolated});
+    m_pending.push_back(Pending{host, slot, frame.width, frame.height, interpolated, -1, 0});
     return true;
 }
 
@@ -181,6 +181,8 @@ bool Scaler::PresentPending(size_t keep) {
             LOG_ERROR("Failed to wait for a read-back: ", lfg_last_error(Ctx()));
             return false;
         }
+        // (the frame has arrived, so the record of its pair has: the read-back was enqueued behind the record's event)
+        if (p.statsLane >= 0 && m_unreadStats[(size_t)p.statsLane] == p.statsCall && !ReadCut(p.statsLane)) return false;
         if (m_presenter) m_presenter(static_cast<const uint8_t*>(p.host), p.width, p.height, p.interpolated);
         ++m_presented;
     }
@@ -188,6 +190,18 @@ bool Scaler::PresentPending(size_t keep) {
 }
 
 bool Scaler::Flush() { return m_readbackRing ? PresentPending(0) : true; }
+
+// The record of `lane`'s last detecting call; the selected lane is put back.
+bool Scaler::ReadCut(int lane) {
+    const int selected = lfg_lane_current(Ctx());
+    int cut = 0;
+    const bool ok = lfg_lane_select(Ctx(), lane) == LFG_OK && lfg_last_pair_stats(Ctx(), nullptr, &cut) == LFG_OK;
+    if (!ok) LOG_ERROR("Failed to read the pair statistics: ", lfg_last_error(Ctx()));
+    (void)lfg_lane_select(Ctx(), selected);
+    m_unreadStats[(size_t)lane] = 0;
+    m_cuts += ok && cut ? 1 : 0;
+    return ok;
+}
 
 bool Scaler::ProcessFrame() {
     if (!m_initialized) {
@@ -259,6 +273,12 @@ bool Scaler::ProcessFrame() {
         for (Frame& f : m_interpolatedFrames) fenceBeforeWrite(f);
         auto& fm = FrameManager::Get();
         bool ok;
+        if (m_countCuts) {
+            // One lane, pipelined: the previous pair's frames are presented at the end of THIS call, after this call has
+            // reused the lane's record -- so that record is read here, one call after its event was recorded.
+            m_unreadStats.resize((size_t)m_lanes, 0);
+            if (m_unreadStats[(size_t)lane] && !ReadCut(lane)) return false;
+        }
         if (m_factors.size() == 1) {                          // the reference's own entry point
             ok = m_pipelined ? fm.InterpolateFramesAsync(m_previousOutput, m_outputFrame, m_interpolatedFrames[0], m_factors[0])
                              : fm.InterpolateFrames(m_previousOutput, m_outputFrame, m_interpolatedFrames[0], m_factors[0]);
@@ -273,8 +293,13 @@ bool Scaler::ProcessFrame() {
             return false;
         }
         // Presentation order: previous real frame (presented by the last call), generated frames t1 .. tN, this real frame.
+        const size_t first = m_pending.size();
         for (Frame& f : m_interpolatedFrames)
             if (!QueueReadback(f, true)) return false;
+        if (m_countCuts) {
+            m_pending[first].statsLane = lane;
+            m_pending[first].statsCall = m_unreadStats[(size_t)lane] = m_calls;      // (already incremented: 1-based)
+        }
     }
     if (!QueueReadback(m_outputFrame, false)) return false;
     // Pipelined: present what earlier calls queued while this call's work runs (one call back; with n > 2 lanes the
@@ -333,6 +358,7 @@ void Scaler::Cleanup() {
     m_lanes = 1;
     m_factors.clear();
     m_havePrevious = false;
+    m_unreadStats.clear();
     m_frameTimings.clear();
     m_initialized = false;
 }
