@@ -1,5 +1,5 @@
 // lfg_capi.cpp -- implementation of the C-ABI in include/linuxfg_hip.h.
-// The only translation units that touch HIP are this file and the three kernel files.
+// The only translation units that touch HIP are this file, lfg_comm.cpp and the kernel files (*.hip).
 // There is no CPU fallback anywhere: every entry point needs a live HIP device.
 #include <cmath>
 #include <cstdio>

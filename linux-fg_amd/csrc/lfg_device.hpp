@@ -1,4 +1,4 @@
-// Device-side helpers shared by the three kernels.  gfx950 only.
+// Device-side helpers shared by every kernel file.  gfx950 only.
 //
 // The whole library is compiled with -ffp-contract=off: an fp32 multiply followed by an add stays
 // two roundings unless the source says __builtin_fmaf.  The motion and interpolate kernels rely on
@@ -133,6 +133,12 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// A packed RGBA8 texel as one dword, what the opt-in stages compare with v_sad_u8: img(x, y), 0 outside the image.  Branching:
+// no load for a position outside.
+__device__ __forceinline__ uint32_t texel_or_zero_branch(const uint8_t *__restrict__ img, size_t pitch, int x, int y, int W, int H) {
+    return (x < 0 || y < 0 || x >= W || y >= H) ? 0u : *reinterpret_cast<const uint32_t *>(img + (size_t)y * pitch + (size_t)x * 4u);
+}
 
 // The largest of a wave's 64 unsigned values, as a wave-uniform (scalar) result.  Six DPP steps in the VALU -- within
 // quads (quad_perm), within half rows and rows (row_half_mirror, row_mirror), then across rows (row_bcast15, row_bcast31:

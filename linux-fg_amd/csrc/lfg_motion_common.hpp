@@ -5,9 +5,11 @@
 //   motion_literal.hip    the shader's own 64-term chain for every (pixel, candidate): whole frames, flagged tiles, any B / R
 //   motion_order.hip      this call's visiting order: hint kernel, order kernel, the candidate tables
 //   motion_lean.hip       whole interior tiles whose pixels all find their answer in the call's first hints
+//   motion_strip.hip      the strips a moving frame exposes at its edges, every candidate summed in full (LFG_MOTION_STRIP)
 //   motion_prefilter.hip  the persistent kernel: every other work unit (prefilter_*.inc: one unit, phase by phase)
 //   motion_resolve.hip    the literal chain for the candidates the prefilter could not separate
 //   motion_plan.hip       host side: work-unit tables and the workspace layout
+//   motion_pyramid.hip    the opt-in coarse-to-fine estimator: shares the vector word (lfg_vector_word.hpp), nothing else
 #pragma once
 
 #include "lfg_device.hpp"
@@ -16,6 +18,7 @@
 #include "lfg_motion_tile.hpp"
 #include "lfg_motion_tune.hpp"
 #include "lfg_motion_diag.hpp"
+#include "lfg_vector_word.hpp"
 
 namespace lfg {
 

@@ -28,6 +28,7 @@
 #include "lfg_device.hpp"
 #include "lfg_internal.hpp"
 #include "lfg_motion_tile.hpp"
+#include "lfg_vector_word.hpp"
 
 namespace lfg {
 
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(kPNT, 3) void motion_lean_kernel(
             for (int i = 0; i < kRun; ++i) {
                 const uint32_t r = kRankIsScan ? rankOf[hb][i] : (uint32_t)sScan[min(rankOf[hb][i], (uint32_t)kCand - 1u)];
                 const uint32_t dyi = (r * 1986u) >> 16, dxi = r - 33u * dyi;
-                rows[(8 * hb + r8) * kPTW + kRun * q + i] = (uint16_t)(uint8_t)(int8_t)((int)dxi - kR) | (uint16_t)((uint16_t)(uint8_t)(int8_t)((int)dyi - kR) << 8);
+                rows[(8 * hb + r8) * kPTW + kRun * q + i] = mv_word((int)dxi - kR, (int)dyi - kR);
             }
         }
         wave_lds_sync();

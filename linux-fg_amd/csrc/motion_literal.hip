@@ -246,7 +246,7 @@ __device__ __forceinline__ void exact_tile(
         for (int i = 0; i < 8; ++i) {
             const int scan = (int)rank2scan[bestCand[i]];
             const int dyi = scan / kSide, dxi = scan - dyi * kSide;
-            const uint32_t v = (uint32_t)(uint8_t)(int8_t)(dxi - kR) | ((uint32_t)(uint8_t)(int8_t)(dyi - kR) << 8);
+            const uint32_t v = mv_word(dxi - kR, dyi - kR);
             o[i >> 1] |= v << (16 * (i & 1));
             if (kFused && fo.data && px0 + i < W) fused_pixel(fo, prev, prevPitch, curr, currPitch, W, H, px0 + i, py, dxi - kR, dyi - kR);
         }

@@ -18,6 +18,7 @@
 // order changes a result.  No data-dependent exits: every call costs the same on every content.
 #include "lfg_internal.hpp"
 #include "lfg_device.hpp"
+#include "lfg_vector_word.hpp"
 
 namespace lfg {
 namespace {
@@ -26,15 +27,6 @@ constexpr int kQ = 8;                  // quads per tile side: a wave = 8 x 8 qu
 constexpr int kTile = 2 * kQ;
 constexpr int kWin = 9;                // a quad's curr window side (8 + 1)
 constexpr int kSearchWaves = 8;        // waves of a search workgroup
-
-__device__ __forceinline__ uint32_t cand_rank(int vx, int vy) {
-    return ((uint32_t)(vx * vx + vy * vy) << 16) | ((uint32_t)(vy + 128) << 8) | (uint32_t)(vx + 128);
-}
-
-__device__ __forceinline__ uint32_t load_px(const uint8_t *base, size_t pitch, int x, int y, int W, int H) {
-    if (x < 0 || y < 0 || x >= W || y >= H) return 0u;
-    return *reinterpret_cast<const uint32_t *>(base + (size_t)y * pitch + (size_t)x * 4u);
-}
 
 // Nine consecutive dwords of an LDS row, starting at an index whose parity is ODD (wave-uniform): four 8-byte reads and one
 // 4-byte read instead of nine 4-byte ones (ds_read_b64 moves twice the bytes per LDS cycle).
@@ -103,7 +95,7 @@ __device__ __forceinline__ void load_quad_curr(QuadCurr &q, const uint8_t *curr,
 #pragma unroll
     for (int r = 0; r < kWin; ++r)
 #pragma unroll
-        for (int i = 0; i < kWin; ++i) q.c[r * kWin + i] = load_px(curr, pitch, 2 * X - 4 + i, 2 * Y - 4 + r, W, H);
+        for (int i = 0; i < kWin; ++i) q.c[r * kWin + i] = texel_or_zero_branch(curr, pitch, 2 * X - 4 + i, 2 * Y - 4 + r, W, H);
 }
 
 __device__ __forceinline__ void keep_min(uint64_t &best, uint32_t cost, uint32_t rank) {
@@ -118,9 +110,8 @@ __device__ __forceinline__ void store_quad(uint8_t *mv, size_t pitch, int W, int
         for (int i = 0; i < 2; ++i) {
             const int x = 2 * X + i, y = 2 * Y + j;
             if (x >= W || y >= H) continue;
-            const uint32_t r = (uint32_t)best[j * 2 + i];
-            const int vx = (int)(r & 0xffu) - 128, vy = (int)((r >> 8) & 0xffu) - 128;
-            *reinterpret_cast<uint16_t *>(mv + (size_t)y * pitch + (size_t)x * 2u) = (uint16_t)((uint32_t)(vx & 0xff) | ((uint32_t)(vy & 0xff) << 8));
+            const Mv v = mv_order_decode((uint32_t)best[j * 2 + i]);
+            *reinterpret_cast<uint16_t *>(mv + (size_t)y * pitch + (size_t)x * 2u) = mv_word(v.x, v.y);
         }
 }
 
@@ -138,7 +129,7 @@ __device__ __forceinline__ void search_all(const QuadCurr &q, const uint32_t *ba
             uint32_t cost[4];
             if ((vx + Rc) & 1) quad_costs<EDGE, 1>(q.c, q.colOk, q.rowOk, row + vx, side, cost);
             else quad_costs<EDGE, 0>(q.c, q.colOk, q.rowOk, row + vx, side, cost);
-            const uint32_t rank = cand_rank(vx, vy);
+            const uint32_t rank = mv_order_key(vx, vy);
 #pragma unroll
             for (int k = 0; k < 4; ++k) keep_min(best[k], cost[k], rank);
         }
@@ -154,7 +145,7 @@ __device__ __forceinline__ void refine_all(const QuadCurr &q, const uint32_t *wi
             uint32_t cost[4];
             if ((dx + Rr) & 1) quad_costs<EDGE, 1>(q.c, q.colOk, q.rowOk, row + dx + Rr, side, cost);
             else quad_costs<EDGE, 0>(q.c, q.colOk, q.rowOk, row + dx + Rr, side, cost);
-            const uint32_t rank = cand_rank(cx + dx, cy + dy);
+            const uint32_t rank = mv_order_key(cx + dx, cy + dy);
 #pragma unroll
             for (int k = 0; k < 4; ++k) keep_min(best[k], cost[k], rank);
         }
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(64 * kSearchWaves) void pyramid_search_kernel(const
     const int ox = x0 - 4 - Rc, oy = y0 - 4 - Rc;
     for (int i = (int)threadIdx.x; i < side * side; i += 64 * kSearchWaves) {
         const int r = i / side, col = i - r * side;
-        sPrev[i] = load_px(prev, pitch, ox + col, oy + r, W, H);
+        sPrev[i] = texel_or_zero_branch(prev, pitch, ox + col, oy + r, W, H);
     }
     const int lane = (int)threadIdx.x % 64, wave = (int)threadIdx.x / 64;
     const int qx = lane % kQ, qy = lane / kQ;
@@ -232,9 +223,8 @@ __global__ __launch_bounds__(64) void pyramid_refine_kernel(const uint8_t *__res
     const int Wp = (W + 1) / 2, Hp = (H + 1) / 2;
     int cx = 0, cy = 0;
     if (X < Wp && Y < Hp) {
-        const uint16_t pv = *reinterpret_cast<const uint16_t *>(parent + (size_t)Y * parentPitch + (size_t)X * 2u);
-        cx = 2 * (int)(int8_t)(pv & 0xffu);
-        cy = 2 * (int)(int8_t)(pv >> 8);
+        const Mv pv = mv_unpack(*reinterpret_cast<const uint16_t *>(parent + (size_t)Y * parentPitch + (size_t)X * 2u));
+        cx = 2 * pv.x, cy = 2 * pv.y;
     }
     QuadCurr q;
     load_quad_curr(q, curr, currPitch, W, H, X, Y);
@@ -244,15 +234,15 @@ __global__ __launch_bounds__(64) void pyramid_refine_kernel(const uint8_t *__res
     uint64_t best[4];
     {
         for (int r = 0; r < kWin; ++r)
-            for (int i = 0; i < kWin; ++i) win[r * pitch + i] = load_px(prev, prevPitch, 2 * X - 4 + i, 2 * Y - 4 + r, W, H);
+            for (int i = 0; i < kWin; ++i) win[r * pitch + i] = texel_or_zero_branch(prev, prevPitch, 2 * X - 4 + i, 2 * Y - 4 + r, W, H);
         uint32_t cost[4];
         quad_costs<true, 0>(q.c, q.colOk, q.rowOk, win, pitch, cost);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) best[k] = ((uint64_t)cost[k] << 32) | cand_rank(0, 0);
+        for (int k = 0; k < 4; ++k) best[k] = ((uint64_t)cost[k] << 32) | mv_order_key(0, 0);
     }
     const int wx = 2 * X - 4 + cx - Rr, wy = 2 * Y - 4 + cy - Rr;
     for (int r = 0; r < side; ++r)
-        for (int i = 0; i < side; ++i) win[r * pitch + i] = load_px(prev, prevPitch, wx + i, wy + r, W, H);
+        for (int i = 0; i < side; ++i) win[r * pitch + i] = texel_or_zero_branch(prev, prevPitch, wx + i, wy + r, W, H);
     const int x0 = (int)blockIdx.x * kTile, y0 = (int)blockIdx.y * kTile;
     if (tile_inside(x0, y0, W, H)) refine_all<false>(q, win, pitch, Rr, cx, cy, best);
     else refine_all<true>(q, win, pitch, Rr, cx, cy, best);

@@ -293,7 +293,7 @@ LFG_STAMP(
         if (kFused && sp.fused.data) fused_pixel(sp.fused, prev, prevPitch, curr, currPitch, W, H, px, py, dxi - kR, dyi - kR);
         int8_t *dst = mv + (size_t)py * (size_t)mvPitch + (size_t)px * 2u;
         if (!kFused || sp.fused.storeMv)
-        *reinterpret_cast<uint16_t *>(dst) = (uint16_t)(uint8_t)(int8_t)(dxi - kR) | (uint16_t)((uint16_t)(uint8_t)(int8_t)(dyi - kR) << 8);   // both components, one store
+        *reinterpret_cast<uint16_t *>(dst) = mv_word(dxi - kR, dyi - kR);   // both components, one store
     }
 LFG_STAMP(
     if ((threadIdx.x & 63) == 0) {

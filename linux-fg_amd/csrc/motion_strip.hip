@@ -439,8 +439,7 @@ __device__ __forceinline__ void strip_item(const StripArgs &a, const int L0, con
         const int px = kTall ? I0 + i : L0 + l, py = kTall ? L0 + l : I0 + i;
         const int scan = (int)a.rank2scan[sFinal[e]];
         const int dyi = scan / kSide, dxi = scan - dyi * kSide;
-        *reinterpret_cast<uint16_t *>(a.mv + (size_t)py * (size_t)a.mvPitch + (size_t)px * 2u) =
-            (uint16_t)(uint8_t)(int8_t)(dxi - kR) | (uint16_t)((uint16_t)(uint8_t)(int8_t)(dyi - kR) << 8);
+        *reinterpret_cast<uint16_t *>(a.mv + (size_t)py * (size_t)a.mvPitch + (size_t)px * 2u) = mv_word(dxi - kR, dyi - kR);
     }
     if (tid < kStripPix && L0 + tid < laneSize) atomicOr(&(kTall ? a.colBand : a.rowBand)[L0 + tid], bit);
 }

@@ -141,7 +141,7 @@ LFG_STAMP_PHASE(
                 for (int i = 0; i < kRun; ++i) {
                     const int scan = scanOf[hb][i];
                     const int dyi = scan / kSide, dxi = scan - dyi * kSide;
-                    rows[(8 * hb + r8E) * kPTW + kRun * qE + i] = (uint16_t)(uint8_t)(int8_t)(dxi - kR) | (uint16_t)((uint16_t)(uint8_t)(int8_t)(dyi - kR) << 8);
+                    rows[(8 * hb + r8E) * kPTW + kRun * qE + i] = mv_word(dxi - kR, dyi - kR);
                 }
             }
             wave_lds_sync();
@@ -286,7 +286,7 @@ LFG_STAMP_PHASE(
                         if (kFused && sp.fused.data) fused_pixel(sp.fused, prev, prevPitch, curr, currPitch, W, H, px0 + i, py, dxi - kR, dyi - kR);
                         int8_t *dst = mv + (size_t)py * (size_t)mvPitch + (size_t)(px0 + i) * 2u;
                         if (!kFused || sp.fused.storeMv)
-                        *reinterpret_cast<uint16_t *>(dst) = (uint16_t)(uint8_t)(int8_t)(dxi - kR) | (uint16_t)((uint16_t)(uint8_t)(int8_t)(dyi - kR) << 8);   // both components, one store
+                        *reinterpret_cast<uint16_t *>(dst) = mv_word(dxi - kR, dyi - kR);   // both components, one store
                     }
                 }
                 open = open || !settled;

@@ -23,6 +23,23 @@ def ctx():
         yield c
 
 
+ESTIMATOR = {"full": capi.ESTIMATOR_FULL_SEARCH, "pyramid": capi.ESTIMATOR_PYRAMID}
+INTERPOLATOR = {"shader": capi.INTERPOLATOR_SHADER, "compensated": capi.INTERPOLATOR_COMPENSATED}
+DEFAULT = ("full", -1, "shader", capi.SEMANTICS_REFERENCE)
+
+
+def apply(ctx, setting, fused=False, match_sad=capi.DEFAULT_MATCH_SAD, threshold=-1):
+    """The setters a host calls for setting = (estimator, refinement radius, interpolator, semantics), the fused order and
+    cut detection, which is set to off (-1) unless a threshold is given.  None of them waits for the GPU."""
+    estimator, radius, interpolator, semantics = setting
+    ctx.set_motion_estimator(ESTIMATOR[estimator])
+    ctx.set_vector_refinement(radius)
+    ctx.set_interpolator(INTERPOLATOR[interpolator], match_sad)
+    ctx.set_semantics(semantics)
+    ctx.set_fused_motion_interpolate(fused)
+    ctx.set_cut_detection(threshold)
+
+
 def gpu_vectors(ctx, prev, curr, estimator):
     """The vectors of "full" (lfg_motion) or "pyramid" (lfg_motion_pyramid at 2, 16, 2) under the intended semantics."""
     h, w = prev.shape[:2]
@@ -93,20 +110,21 @@ def seam_rows(in_h):
 
 
 def host_stream(tmp_path, frames, *options):
-    """`frames` through lfg_host as a raw file, under the intended semantics and `options`: the 2 n - 1 frames it presents."""
+    """`frames` through lfg_host as a raw file, under the intended semantics and `options`: (its report line, the 2 n - 1
+    frames it presents)."""
     if not os.path.exists(HOST):
         import __graft_entry__ as entry
         entry.build()
     n, (h, w) = len(frames), frames[0].shape[:2]
-    src = tmp_path / "in.rgba"
+    tmp_path.mkdir(exist_ok=True)
+    src, out = tmp_path / "in.rgba", tmp_path / "out.rgba"
     np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    out = tmp_path / "out.rgba"
     p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
                         "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended", *options],
                        capture_output=True, text=True, timeout=300, check=True)
     info = json.loads(p.stdout.strip().splitlines()[-1])
     assert info["presented"] == 2 * n - 1
-    return np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+    return info, np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
 
 
 def three_lanes(ctx, inputs, enqueue, alone):

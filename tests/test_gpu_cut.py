@@ -3,9 +3,6 @@ on hand-written records, both behind lfg_interpolate_frames[_multi] against the 
 to off, three lanes, argument checks, and the host's --cut-threshold.  The threshold of 500 rests on
 tests/test_pair_model.py: moving content matches on 700 pixels per thousand or more, cuts on 50 or fewer."""
 import ctypes
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +10,7 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import cases
 from tests import pair_model as pair
-from tests.gpu_kit import HOST, ctx, first_bad, pitched, three_lanes
+from tests.gpu_kit import DEFAULT, apply, ctx, first_bad, host_stream, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -175,22 +172,9 @@ def test_cut_fallback_with_every_output(ctx):
 
 # ---- 4. behind both entry points, held to the CPU chain
 
-ESTIMATOR = {"full": capi.ESTIMATOR_FULL_SEARCH, "pyramid": capi.ESTIMATOR_PYRAMID}
-INTERPOLATOR = {"shader": capi.INTERPOLATOR_SHADER, "compensated": capi.INTERPOLATOR_COMPENSATED}
-DEFAULT = ("full", -1, "shader", capi.SEMANTICS_REFERENCE)
 SETTINGS = [("full", -1, "shader", 0), ("full", -1, "shader", 1), ("full", 1, "compensated", 1),
             ("pyramid", -1, "compensated", 1), ("pyramid", 2, "compensated", 0), ("pyramid", 0, "shader", 1)]
 FACTORS = [cases.MATRIX_FACTOR] + cases.MATRIX_FACTORS         # the single call, then the multi call
-
-
-def apply(ctx, setting, fused=False, threshold=-1):
-    estimator, radius, interpolator, semantics = setting
-    ctx.set_motion_estimator(ESTIMATOR[estimator])
-    ctx.set_vector_refinement(radius)
-    ctx.set_interpolator(INTERPOLATOR[interpolator], capi.DEFAULT_MATCH_SAD)
-    ctx.set_semantics(semantics)
-    ctx.set_fused_motion_interpolate(fused)
-    ctx.set_cut_detection(threshold)
 
 
 def cut_scene(w=200, h=120):
@@ -237,7 +221,7 @@ def scenes(ctx):
 @pytest.mark.parametrize("setting", SETTINGS, ids=lambda s: "-".join(str(v) for v in s))
 def test_entry_points_equal_the_chain(ctx, scenes, setting, fused):
     try:
-        apply(ctx, setting, fused, THRESHOLD)
+        apply(ctx, setting, fused, threshold=THRESHOLD)
         results = {name: both_calls(ctx, p, c, outs, True) for name, (_, p, c, outs) in scenes.items()}
     finally:
         apply(ctx, DEFAULT)
@@ -428,27 +412,12 @@ def test_invalid_arguments_launch_nothing(ctx):
 
 # ---- 8. lfg_host --cut-threshold
 
-def host_run(tmp_path, frames, *options):
-    """gpu_kit.host_stream, returning the report line too: (report, the 2 n - 1 presented frames)."""
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
-    n, (h, w) = len(frames), frames[0].shape[:2]
-    tmp_path.mkdir(exist_ok=True)
-    src, out = tmp_path / "in.rgba", tmp_path / "out.rgba"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
-                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended", *options],
-                       capture_output=True, text=True, timeout=300, check=True)
-    return json.loads(p.stdout.strip().splitlines()[-1]), np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
-
-
 def test_host_shows_a_source_frame_across_a_cut(ctx, tmp_path):
     w, h = 96, 64
     a, b = synth.make_prev(w, h, synth.BASE_SEED), synth.make_prev(w, h, synth.BASE_SEED + 1)
     frames = [a, synth.translate(a, (3, -2), synth.BASE_SEED), b, synth.translate(b, (3, -2), synth.BASE_SEED + 1)]
-    plain_report, plain = host_run(tmp_path / "plain", frames)
-    report, got = host_run(tmp_path / "cut", frames, "--cut-threshold", str(THRESHOLD))
+    plain_report, plain = host_stream(tmp_path / "plain", frames)
+    report, got = host_stream(tmp_path / "cut", frames, "--cut-threshold", str(THRESHOLD))
     assert plain_report["cuts"] == 0 and plain_report["presented"] == 7
     assert report["cuts"] == 1 and report["presented"] == 7 and report["interpolated"] == 3
     for k in (0, 2, 4, 6):                                    # the real frames: the scale at equal sizes is the identity

@@ -7,23 +7,9 @@ import pytest
 
 from linux_fg_amd import capi
 from tests import cases
-from tests.gpu_kit import ctx, first_bad
+from tests.gpu_kit import DEFAULT, apply, ctx, first_bad
 
 pytestmark = pytest.mark.gpu
-
-ESTIMATOR = {"full": capi.ESTIMATOR_FULL_SEARCH, "pyramid": capi.ESTIMATOR_PYRAMID}
-INTERPOLATOR = {"shader": capi.INTERPOLATOR_SHADER, "compensated": capi.INTERPOLATOR_COMPENSATED}
-DEFAULT = ("full", -1, "shader", capi.SEMANTICS_REFERENCE)
-
-
-def apply(ctx, setting, fused=False, match_sad=capi.DEFAULT_MATCH_SAD):
-    """The setters a host calls, and nothing else.  None of them waits for the GPU."""
-    estimator, radius, interpolator, semantics = setting
-    ctx.set_motion_estimator(ESTIMATOR[estimator])
-    ctx.set_vector_refinement(radius)
-    ctx.set_interpolator(INTERPOLATOR[interpolator], match_sad)
-    ctx.set_semantics(semantics)
-    ctx.set_fused_motion_interpolate(fused)
 
 
 def restore(ctx):

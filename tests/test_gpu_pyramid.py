@@ -199,7 +199,7 @@ def test_host_pyramid_stream_matches_capi(tmp_path):
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (20, 0), synth.BASE_SEED + k))
-    got = host_stream(tmp_path, frames, "--motion", "pyramid")
+    _, got = host_stream(tmp_path, frames, "--motion", "pyramid")
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

@@ -273,7 +273,7 @@ def test_host_refined_stream_matches_capi(tmp_path):
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (12, -6), synth.BASE_SEED + k))
-    got = host_stream(tmp_path, frames, "--interpolator", "compensated", "--refine-vectors", "1")
+    _, got = host_stream(tmp_path, frames, "--interpolator", "compensated", "--refine-vectors", "1")
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

@@ -1,5 +1,5 @@
 """Host-side logic that needs no GPU: the synthetic frame source (C++ vs Python), the exact 1/255
-split used by the kernels, the golden fixtures against the oracle, the motion launch policy, and the sharding helpers."""
+split used by the kernels, the golden fixtures against the oracle, the motion launch policy, the vector word, and the sharding helpers."""
 import os
 import subprocess
 
@@ -73,6 +73,19 @@ def test_motion_launch_policy_equals_its_pre_refactor_form(tmp_path):
     assert r.returncode == 0, r.stdout
     assert r.stdout.startswith("ok "), r.stdout
     assert int(r.stdout.split()[1]) > 1_000_000
+
+
+def test_vector_word_and_keys_equal_their_pre_refactor_forms(tmp_path):
+    """tests/cpp/vector_word_check.cpp: csrc/lfg_vector_word.hpp (MV_S8X2 pack and unpack, the order key, the longest-first key)
+    compiled with g++ alone: every word survives unpack then pack, every helper equals each expression it replaced, and both
+    keys order all pairs of 625 vectors as their tuples do."""
+    out = tmp_path / "vector_word_check"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "linux-fg_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "vector_word_check.cpp"), "-o", str(out)])
+    r = subprocess.run([str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    assert r.stdout.startswith("ok "), r.stdout
+    assert int(r.stdout.split()[1]) > 65_536 + 625 * 625
 
 
 def test_stream_assignment_covers_every_stream_once():
