@@ -445,6 +445,35 @@ int  lfg_cut_fallback(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *
 int  lfg_set_cut_detection(lfg_context *ctx, int min_matched_permille);   /* -1 (default): off; 0 .. 1000 */
 int  lfg_last_pair_stats(lfg_context *ctx, lfg_pair_stats *out_stats, int *out_cut);
 
+/* Frame comparison: how far two frames that live on the device are from each other.  No reference counterpart.  Integer
+ * arithmetic only; it depends on no setting of the context.
+ *   Inputs: a, b RGBA8, both W x H; channel_mask in 1 .. 15, bit c standing for channel c (byte c of the texel).
+ *   For pixel q and channel c: d_c(q) = |a(q)_c - b(q)_c|;  m(q) = the largest d_c(q) over the channels of channel_mask.
+ *   pixels = W * H;  sse[c] = the sum over q of d_c(q)^2, for all four channels whatever the mask;
+ *   hist[k] = the number of q with m(q) = k.
+ * All 261 words are 64-bit integers, so neither the order of evaluation nor any tiling changes a result.
+ *   accumulate = 0: the call WRITES the 261 words of `device_stats` (2,088 bytes of device memory, 8-byte aligned);
+ *   accumulate = 1: the call ADDS to them, pixels included: several pairs go into one record with no host wait between them.
+ * Frames: 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4); a and b may overlap or be the same frame (nothing is
+ * written to them); a view made with lfg_frame_wrap into a larger frame is a region of interest.  A NULL pointer, a wrong
+ * format, differing sizes, a misaligned frame or record, a mask outside 1 .. 15 or any other value of accumulate returns
+ * LFG_ERR_INVALID before anything is enqueued.  Enqueued on the selected lane (a clear of the record unless accumulate is 1,
+ * one launch of a fixed grid); keeps no device memory; outside the stage timers (a comparison is no stage of the path). */
+typedef struct lfg_frame_diff_stats { uint64_t pixels; uint64_t sse[4]; uint64_t hist[256]; } lfg_frame_diff_stats;   /* 2,088 bytes */
+int  lfg_frame_diff(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, uint32_t channel_mask,
+                    int accumulate, void *device_stats /* 2,088 bytes of device memory, 8-byte aligned */);
+/* A record in HOST memory (copied from the device by the caller) as the figures one quotes.  A pure host function: no
+ * context, no GPU.  channel_mask should be the one the record was made with: hist depends on that mask, sse does not.
+ *   differing = pixels - hist[0];  over_1 = differing - hist[1] (the pixels beyond +-1 LSB);
+ *   max_abs = the largest k with hist[k] > 0, 0 if there is none;
+ *   pP for P = 50, 99 = the smallest k with 100 * (hist[0] + .. + hist[k]) >= P * pixels, in 64 bits;
+ *   mse = (the sum of sse[c] over the channels of channel_mask) / (popcount(channel_mask) * pixels), in double;
+ *   psnr_db = 10 * log10(65025 / mse), HUGE_VAL where mse is 0.
+ * Returns LFG_ERR_INVALID for a NULL pointer, a mask outside 1 .. 15, pixels = 0 or a histogram that does not sum to
+ * pixels (the record's own consistency check: a record of several masks, or one that was never written). */
+typedef struct lfg_frame_diff_summary { uint64_t pixels, differing, over_1; uint32_t max_abs, p50, p99; double mse, psnr_db; } lfg_frame_diff_summary;
+int  lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, uint32_t channel_mask, lfg_frame_diff_summary *out);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

@@ -47,6 +47,24 @@ class PairStats(ctypes.Structure):
         return int(self.pixels), int(self.matched), int(self.sad_sum)
 
 
+class FrameDiffStats(ctypes.Structure):
+    """struct lfg_frame_diff_stats."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("sse", ctypes.c_uint64 * 4), ("hist", ctypes.c_uint64 * 256)]
+
+    def as_tuple(self):
+        return int(self.pixels), tuple(int(v) for v in self.sse), tuple(int(v) for v in self.hist)
+
+
+class FrameDiffSummary(ctypes.Structure):
+    """struct lfg_frame_diff_summary."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("differing", ctypes.c_uint64), ("over_1", ctypes.c_uint64),
+                ("max_abs", ctypes.c_uint32), ("p50", ctypes.c_uint32), ("p99", ctypes.c_uint32),
+                ("mse", ctypes.c_double), ("psnr_db", ctypes.c_double)]
+
+    def as_dict(self):
+        return {name: (float if name in ("mse", "psnr_db") else int)(getattr(self, name)) for name, _ in self._fields_}
+
+
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 _FP = ctypes.POINTER(Frame)
 
@@ -110,6 +128,8 @@ SIGNATURES = {
     "lfg_cut_fallback": (_i, [_vp, _FP, _FP, _vp, _i, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
     "lfg_set_cut_detection": (_i, [_vp, _i]),
     "lfg_last_pair_stats": (_i, [_vp, ctypes.POINTER(PairStats), ctypes.POINTER(_i)]),
+    "lfg_frame_diff": (_i, [_vp, _FP, _FP, _u32, _i, _vp]),
+    "lfg_frame_diff_summarize": (_i, [ctypes.POINTER(FrameDiffStats), _u32, ctypes.POINTER(FrameDiffSummary)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
     "lfg_mv_export_rgba32f": (_i, [_vp, _FP, _vp]),
@@ -136,6 +156,17 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+def summarize(record, channel_mask: int = 0xF) -> dict:
+    """A record (pixels, sse, hist) -- read_diff_record's tuple -- as lfg_frame_diff_summarize's figures: a dict of pixels,
+    differing, over_1, max_abs, p50, p99, mse and psnr_db (inf on identical frames).  Needs no context and no GPU."""
+    pixels, sse, hist = record
+    s, out = FrameDiffStats(int(pixels), (ctypes.c_uint64 * 4)(*sse), (ctypes.c_uint64 * 256)(*hist)), FrameDiffSummary()
+    rc = load().lfg_frame_diff_summarize(ctypes.byref(s), int(channel_mask), ctypes.byref(out))
+    if rc != 0:
+        raise LfgError(f"lfg_frame_diff_summarize failed ({rc}): bad mask, no pixels, or a histogram that does not sum to them")
+    return out.as_dict()
 
 
 def load() -> ctypes.CDLL:
@@ -462,6 +493,21 @@ class Context:
         s, cut = PairStats(), ctypes.c_int()
         self._check(self.lib.lfg_last_pair_stats(self.h, ctypes.byref(s), ctypes.byref(cut)), "lfg_last_pair_stats")
         return s.as_tuple(), bool(cut.value)
+
+    # -- frame comparison.  A record is 2,088 bytes of device memory: here a 522 x 1 RGBA8 frame, as the pair record above.
+    def create_diff_record(self) -> Frame:
+        return self.create_frame(ctypes.sizeof(FrameDiffStats) // 4, 1)
+
+    def frame_diff(self, a: Frame, b: Frame, record: Frame, channel_mask: int = 0xF, accumulate: bool = False):
+        """Frame comparison (lfg_frame_diff): the squared differences per channel and the histogram of the largest
+        difference over the channels of `channel_mask`, written into `record` (create_diff_record) or added to it."""
+        self._check(self.lib.lfg_frame_diff(self.h, ctypes.byref(a), ctypes.byref(b), int(channel_mask), int(accumulate),
+                                            _vp(record.data)), "lfg_frame_diff")
+
+    def read_diff_record(self, record: Frame):
+        """(pixels, sse tuple, hist tuple) of a record in device memory; waits for the context."""
+        words = [int(v) for v in self.download(record).reshape(-1).view(np.uint64)]
+        return words[0], tuple(words[1:5]), tuple(words[5:])
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -1447,6 +1447,60 @@ LFG_EXPORT int lfg_last_pair_stats(lfg_context *ctx, lfg_pair_stats *out_stats, 
     return LFG_OK;
 }
 
+// ---- frame comparison (frame_diff.hip)
+
+LFG_EXPORT int lfg_frame_diff(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, uint32_t channel_mask,
+                              int accumulate, void *device_stats) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(a, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(b, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_diff: a and b must be non-empty RGBA8");
+    if (!same_size(a, b)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_diff: a and b differ in size");
+    if ((a->pitch | b->pitch) % 4u || ((uintptr_t)a->data | (uintptr_t)b->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_diff: RGBA8 frames must be 4-byte aligned");
+    if (channel_mask < 1u || channel_mask > 15u) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_diff: channel_mask must be in [1, 15]");
+    if (accumulate != 0 && accumulate != 1) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_diff: accumulate must be 0 or 1");
+    if (!device_stats || (uintptr_t)device_stats % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_diff: device_stats must be non-NULL and 8-byte aligned");
+    hipError_t e = lfg::launch_frame_diff(ctx->cur().stream, *a, *b, channel_mask, accumulate == 1, ctx->device_cus, device_stats);
+    if (e != hipSuccess) return fail_hip(ctx, e, "frame diff kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, uint32_t channel_mask, lfg_frame_diff_summary *out) {
+    if (!host_stats || !out || channel_mask < 1u || channel_mask > 15u || host_stats->pixels == 0) return LFG_ERR_INVALID;
+    const uint64_t pixels = host_stats->pixels;
+    uint64_t total = 0;
+    for (int k = 0; k < 256; ++k) {
+        if (host_stats->hist[k] > pixels - total) return LFG_ERR_INVALID;       // (no sum past pixels: no wrap either)
+        total += host_stats->hist[k];
+    }
+    if (total != pixels) return LFG_ERR_INVALID;
+    lfg_frame_diff_summary s{};
+    s.pixels = pixels;
+    s.differing = pixels - host_stats->hist[0];
+    s.over_1 = s.differing - host_stats->hist[1];
+    // the quantiles: 100 * below >= P * pixels.  64 bits hold both products for any record the device can have written
+    // (pixels below 2^57); a hand-made record may be larger, hence the wider type
+    bool have50 = false, have99 = false;
+    uint64_t below = 0;
+    for (uint32_t k = 0; k < 256u; ++k) {
+        below += host_stats->hist[k];
+        if (host_stats->hist[k] > 0) s.max_abs = k;
+        const unsigned __int128 lhs = (unsigned __int128)100u * below;
+        if (!have50 && lhs >= (unsigned __int128)50u * pixels) { s.p50 = k; have50 = true; }
+        if (!have99 && lhs >= (unsigned __int128)99u * pixels) { s.p99 = k; have99 = true; }
+    }
+    double sum = 0.0;
+    int channels = 0;
+    for (int c = 0; c < 4; ++c)
+        if ((channel_mask >> c) & 1u) { sum += (double)host_stats->sse[c]; ++channels; }
+    s.mse = sum / ((double)channels * (double)pixels);
+    s.psnr_db = s.mse > 0.0 ? 10.0 * std::log10(65025.0 / s.mse) : HUGE_VAL;
+    *out = s;
+    return LFG_OK;
+}
+
 LFG_EXPORT int lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled) {
     if (!ctx) return LFG_ERR_INVALID;
     ctx->fuse_motion_interpolate = enabled != 0;

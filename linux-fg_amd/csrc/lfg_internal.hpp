@@ -318,6 +318,10 @@ hipError_t launch_pair_match(hipStream_t s, const lfg_frame &prev, const lfg_fra
                              int deviceCus, void *stats);
 hipError_t launch_cut_fallback(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const void *stats, int minMatchedPermille,
                                const lfg_frame *const *outs, const float *factors, int count, int deviceCus);
+// Frame comparison (frame_diff.hip): clears the 2,088-byte record `stats` unless `accumulate`, then enqueues the fixed grid
+// that adds the pair's sums and histogram to it; 16-byte loads where base and pitch of both frames allow, dword loads otherwise.
+hipError_t launch_frame_diff(hipStream_t s, const lfg_frame &a, const lfg_frame &b, uint32_t channelMask, bool accumulate,
+                             int deviceCus, void *stats);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

@@ -1,0 +1,23 @@
+// lfg_host --evaluate: how close the generated frames come to frames that were held out.  No reference counterpart (its
+// roadmap lists "Evaluate quality and performance metrics" as open).  Source frames 0, 2, 4, ... are the stream and 1, 3, 5, ...
+// the truth; every frame is upscaled to the output size, where a viewer would look, and per pair k
+//     lfg_interpolate_frames(up[2k], up[2k+2], out, 0.5)          under the context's settings, whatever they are
+//     lfg_frame_diff(out,    up[2k+1], generated, 0xF, k > 0)
+//     lfg_frame_diff(up[2k], up[2k+1], repeated,  0xF, k > 0)     the yardstick: showing the previous frame again
+// on one lane, with no wait before the end: one lfg_sync, one download of both records, lfg_frame_diff_summarize on each.
+// Nothing is presented.  Scaler::ProcessFrame is not involved.
+#pragma once
+#include <string>
+
+#include "frame_source.hpp"
+
+struct EvaluationResult {
+    uint64_t pairs = 0;
+    double seconds = 0.0;
+    std::string json;              // {"pairs": P, "generated": {...}, "repeated": {...}}
+};
+
+// `frames` >= 3 source frames of inputWidth x inputHeight from `source` (a trailing unpaired frame is not read), compared at
+// outputWidth x outputHeight.  HipContext must be initialized and carry the settings to evaluate.
+bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeight, uint32_t outputWidth, uint32_t outputHeight,
+                   int frames, EvaluationResult& result);

@@ -8,6 +8,7 @@
 #include <iostream>
 #include <string>
 
+#include "evaluate.hpp"
 #include "scaler.hpp"
 
 static void PrintUsage() {
@@ -41,6 +42,12 @@ static void PrintUsage() {
               << "                           0..2: each pixel takes the nearby vector that fits its (2R+1)^2 window best)\n"
               << "  --cut-threshold P        Scene-cut detection (default -1: off; 0..1000: a pair of which fewer than P pixels per\n"
               << "                           thousand match under its vectors shows a source frame instead of a generated one)\n"
+              << "  --evaluate               Measure instead of presenting: source frames 0, 2, 4, ... are the stream, 1, 3, 5, ... are\n"
+              << "                           held out; each pair's frame at 0.5 is generated under the options above and compared on the\n"
+              << "                           GPU, at the output size, with the frame held out -- as is the pair's first frame, shown\n"
+              << "                           again.  The report gains \"evaluation\" (PSNR, error quantiles, differing pixels of both).\n"
+              << "                           Needs --frames >= 3; not with --ranks, --factors, --no-interpolation, --output-raw,\n"
+              << "                           --dump-dir or --replay\n"
               << "  --frames N               Number of input frames to process (default: 10)\n"
               << "  --device N               HIP device ordinal (default: 0)\n"
               << "  --dump-dir DIR           Write every presented frame to DIR as raw RGBA8\n"
@@ -68,7 +75,7 @@ int main(int argc, char* argv[]) {
     int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
-    bool syncPresent = false, presentNull = false;
+    bool syncPresent = false, presentNull = false, evaluate = false;
     int replay = 0;
 
     for (int i = 1; i < argc; i++) {
@@ -124,6 +131,7 @@ int main(int argc, char* argv[]) {
             if (!end || *end != '\0' || p < -1 || p > 1000) { LOG_ERROR("Invalid --cut-threshold (-1, or 0 to 1000)"); return 1; }
             cutThreshold = (int)p;
         }
+        else if (strcmp(argv[i], "--evaluate") == 0) evaluate = true;
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--device") == 0 && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--dump-dir") == 0 && i + 1 < argc) dumpDir = argv[++i];
@@ -155,6 +163,13 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (evaluate) {                                             // before a context is made
+        const char* clash = ranks > 0 ? "--ranks" : !factors.empty() ? "--factors" : !config.enableInterpolation ? "--no-interpolation"
+                          : !outputRaw.empty() ? "--output-raw" : !dumpDir.empty() ? "--dump-dir" : replay > 0 ? "--replay" : nullptr;
+        if (clash) { LOG_ERROR("--evaluate cannot be combined with ", clash); return 2; }
+        if (frames < 3) { LOG_ERROR("--evaluate needs --frames of 3 or more"); return 2; }
+    }
+
     if (!HipContext::Get().Initialize(device)) { LOG_ERROR("Failed to initialize HIP"); return 1; }
     // (library settings, like --in-flight: ScalerConfig keeps the reference's fields)
     if (lfg_set_semantics(HipContext::Get().GetDevice(), semantics) != LFG_OK ||
@@ -170,6 +185,22 @@ int main(int argc, char* argv[]) {
         LOG_ERROR("Failed to initialize frame manager");
         HipContext::Get().Cleanup();
         return 1;
+    }
+    if (evaluate) {
+        std::unique_ptr<FrameSource> source;
+        if (!inputRaw.empty()) source = std::make_unique<RawFileCapture>(inputRaw);
+        else source = std::make_unique<SyntheticCapture>(stream);
+        EvaluationResult result;
+        const bool ok = RunEvaluation(*source, config.inputWidth, config.inputHeight, config.outputWidth, config.outputHeight, frames, result);
+        source.reset();
+        FrameManager::Get().Cleanup();
+        HipContext::Get().Cleanup();
+        if (!ok) { LOG_ERROR("Evaluation failed: ", Logger::Get().GetLastError()); return 1; }
+        printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
+               "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
+               "\"note\": \"nothing is presented: every second source frame is held out and compared on the GPU\", \"evaluation\": %s}\n",
+               frames, (unsigned long long)result.pairs, result.seconds, presentNull ? "true" : "false", result.json.c_str());
+        return 0;
     }
     if (ranks > 0) {
         if (commFile.empty() || rank < 0 || rank >= ranks) { LOG_ERROR("--ranks needs --rank in range and --comm-file"); return 1; }

@@ -1,0 +1,94 @@
+"""How close each route's generated frame comes to a frame that was held out, measured on the GPU: the table of DESIGN.md
+section 4.11 at 1080p and 4K.  The pair is frames 0 and 2 of a synth triple, frame 1 is the truth, the factor 0.5; PSNR and
+differing pixels are taken over R, G and B (mask 0x7).  Three triples: a pan of (3, -2) per frame; a pan of (20, -12) per
+frame, whose pair's (40, -24) is beyond the full search's 16 px and inside the pyramid's reach; the first pan with +-4 levels
+of independent noise on all three frames.  Six routes: repeating frame 0, and lfg_interpolate_frames under five settings.
+Everything goes through lfg_interpolate_frames + lfg_frame_diff, with one sync per route (the read of its record).
+
+    python tools/quality_report.py [--sizes 1080p,4k] [--json out.json] [--out report.txt]
+"""
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import sys
+
+import numpy as np
+
+from stage_bench import SIZES, emit, write_json                # (puts the repository root on sys.path)
+from linux_fg_amd import capi, synth  # noqa: E402
+
+MASK = 0x7
+ROUTES = [                                                     # (name, estimator, refinement radius, interpolator, semantics)
+    ("full search, shader, reference semantics (the default)", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_SHADER, capi.SEMANTICS_REFERENCE),
+    ("full search, shader, intended semantics", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_SHADER, capi.SEMANTICS_INTENDED),
+    ("full search, compensated", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED),
+    ("full search, refine radius 1, compensated", capi.ESTIMATOR_FULL_SEARCH, 1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED),
+    ("pyramid, compensated", capi.ESTIMATOR_PYRAMID, -1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED),
+]
+
+
+def triples(w, h):
+    """(name, frame 0, frame 1, frame 2)"""
+    for name, shift in (("pan(3,-2)", (3, -2)), ("pan(20,-12)", (20, -12))):
+        f0 = synth.make_prev(w, h)
+        f1 = synth.translate(f0, shift)
+        yield name, f0, f1, synth.translate(f1, shift)
+    f0 = synth.make_prev(w, h)
+    f1 = synth.translate(f0, (3, -2))
+    clean = [f0, f1, synth.translate(f1, (3, -2))]
+    rng = np.random.default_rng(11)
+    yield ("pan(3,-2)+-4noise", *[np.clip(f.astype(np.int16) + rng.integers(-4, 5, f.shape), 0, 255).astype(np.uint8) for f in clean])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1080p,4k")
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows = []
+    with capi.Context(0) as ctx:
+        for size in a.sizes.split(","):
+            w, h = SIZES[size]
+            for content, f0, f1, f2 in triples(w, h):
+                p, t, c, o = ctx.frame_from(f0), ctx.frame_from(f1), ctx.frame_from(f2), ctx.create_frame(w, h)
+                r = ctx.create_diff_record()
+
+                def row(route):
+                    s = capi.summarize(ctx.read_diff_record(r), MASK)       # the route's one sync
+                    emit(rows, {"size": size, "content": content, "route": route, "psnr_db": s["psnr_db"], "differing": s["differing"],
+                                "over_1": s["over_1"], "p50": s["p50"], "p99": s["p99"], "max_abs": s["max_abs"], "pixels": s["pixels"]})
+
+                ctx.frame_diff(p, t, r, MASK)
+                row("repeat prev (no generation)")
+                for name, estimator, radius, interpolator, semantics in ROUTES:
+                    ctx.set_motion_estimator(estimator)
+                    ctx.set_vector_refinement(radius)
+                    ctx.set_interpolator(interpolator)
+                    ctx.set_semantics(semantics)
+                    ctx.interpolate_frames(p, c, o, 0.5)
+                    ctx.frame_diff(o, t, r, MASK)
+                    row(name)
+                for f in (p, t, c, o, r):
+                    ctx.destroy_frame(f)
+    write_json(a.json, rows)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(f"# lib_sha16 {hashlib.sha256(open(capi.LIB_PATH, 'rb').read()).hexdigest()[:16]}\n")
+            f.write(f"# python tools/quality_report.py {' '.join(sys.argv[1:])}: frames 0 and 2 of a synth triple generate frame 1 at 0.5;\n"
+                    "# lfg_interpolate_frames + lfg_frame_diff on one MI355X, PSNR and differing pixels over R, G and B (mask 0x7).\n")
+            for row_ in rows:
+                f.write(json.dumps(row_) + "\n")
+            for size in a.sizes.split(","):
+                f.write(f"\n## {size}: PSNR dB / differing px of {SIZES[size][0] * SIZES[size][1]:,}\n")
+                names = list(dict.fromkeys(x["content"] for x in rows))
+                f.write("| route | " + " | ".join(names) + " |\n|---|" + "---|" * len(names) + "\n")
+                for route in dict.fromkeys(x["route"] for x in rows):
+                    cells = [next(x for x in rows if (x["size"], x["content"], x["route"]) == (size, n, route)) for n in names]
+                    f.write(f"| {route} | " + " | ".join(f"{x['psnr_db']:.2f} / {x['differing']:,}" for x in cells) + " |\n")
+
+
+if __name__ == "__main__":
+    main()
