@@ -474,6 +474,46 @@ int  lfg_frame_diff(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, ui
 typedef struct lfg_frame_diff_summary { uint64_t pixels, differing, over_1; uint32_t max_abs, p50, p99; double mse, psnr_db; } lfg_frame_diff_summary;
 int  lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, uint32_t channel_mask, lfg_frame_diff_summary *out);
 
+/* NV12 input and output: colour conversion between 4:2:0 YUV as decoders write it and encoders read it, and the RGBA8 frames of
+ * every other call.  No reference counterpart (the reference captures and presents RGBA only, src/frame_manager.hpp:15).
+ * Integer arithmetic only; it depends on no setting of the context.  NV12 is no lfg_format: the planes are described by an
+ * lfg_nv12 of caller-owned device memory.
+ *   Planes: y is W x H bytes, rows y_pitch >= W apart, any alignment; uv is W/2 x H/2 interleaved (Cb, Cr) byte pairs, rows
+ *   uv_pitch >= W apart, uv_pitch even and uv 2-byte aligned.  W and H are even.
+ *   Coefficients (lfg_yuv_coefficients, the numbers the kernels use): Kr, Kb = 0.299, 0.114 (LFG_YUV_BT601) or 0.2126, 0.0722
+ *   (LFG_YUV_BT709), Kg = 1 - Kr - Kb; LFG_YUV_LIMITED: sy = 255/219, sc = 255/224, o = 16; LFG_YUV_FULL: sy = sc = 1, o = 0.
+ *   Each is round(x * 2^14) of the real value x computed in double (none is a tie), but for three that make the rows sum exactly:
+ *     to_rgb = {cY, cRV, cGU, cGV, cBU} = sy, 2 (1 - Kr) sc, 2 Kb (1 - Kb) / Kg sc, 2 Kr (1 - Kr) / Kg sc, 2 (1 - Kb) sc;
+ *     to_yuv = {yR, yG, yB, uR, uG, uB, vR, vG, vB}: yR = Kr / sy, yB = Kb / sy, yG = round(2^14 / sy) - yR - yB;
+ *       uR = -Kr / (2 (1 - Kb)) / sc, uB = 0.5 / sc, uG = -uR - uB;  vR = 0.5 / sc, vB = -Kb / (2 (1 - Kr)) / sc, vG = -vR - vB.
+ *   Chroma at luma pixel (x, y), scaled by 8, with i = x >> 1, j = y >> 1 and C the Cb or the Cr plane, indices clamped to it:
+ *     LFG_CHROMA_REPLICATE: c8 = 8 C[j][i];
+ *     LFG_CHROMA_LEFT (MPEG-2 siting: co-sited with the even columns, midway between the rows):
+ *       h(r) = 2 C[r][i] for even x, C[r][i] + C[r][i + 1] for odd x;
+ *       c8 = 3 h(j) + h(j - 1) for even y, 3 h(j) + h(j + 1) for odd y.
+ *   lfg_nv12_to_rgba: y' = Y - o, cb = cb8 - 1024, cr = cr8 - 1024;
+ *     R = clamp((8 cY y' + cRV cr + 2^16) >> 17), G = clamp((8 cY y' - cGU cb - cGV cr + 2^16) >> 17),
+ *     B = clamp((8 cY y' + cBU cb + 2^16) >> 17), A = 255; clamp to [0, 255], >> the arithmetic shift (floor).
+ *   lfg_rgba_to_nv12: Y = clamp(o + ((yR R + yG G + yB B + 2^13) >> 14)).  The pair (i, j) from the channel sums S over the luma
+ *     rows 2j and 2j + 1: LFG_CHROMA_REPLICATE the columns 2i, 2i + 1 with weight 1 (shift 16); LFG_CHROMA_LEFT the columns
+ *     2i - 1, 2i, 2i + 1 with weights 1, 2, 1, the column index clamped to the image (shift 17);
+ *     Cb = clamp(128 + ((uR S_R + uG S_G + uB S_B + 2^(shift - 1)) >> shift)), Cr likewise with the v row.  Alpha is ignored.
+ *   Every intermediate fits 32 bits.  Hence a grey input gives Cb = Cr = 128 and, under the full range, R = G = B = Y.
+ * Frames: W and H even and equal to the RGBA frame's (at most 8,388,480 x 524,280); the RGBA frame 4-byte aligned with a pitch
+ * that is a multiple of 4; the output overlaps no input, and the two planes of an output do not overlap each other.  Any
+ * violation, a NULL pointer or an unknown matrix, range or siting returns LFG_ERR_INVALID before anything is enqueued.  Each call
+ * is one launch on the selected lane; it keeps no device memory and is outside the stage timers (a conversion is no stage of
+ * the path).  Only the W (or W * 4) bytes of each output row are written, never the row padding.  Offset pointers into larger
+ * planes are a region of interest (even offsets, so that the chroma pairs line up). */
+typedef struct lfg_nv12 { void *y; void *uv; uint32_t width, height, y_pitch, uv_pitch; } lfg_nv12;  /* caller-owned device memory */
+typedef enum { LFG_YUV_BT601 = 0, LFG_YUV_BT709 = 1 } lfg_yuv_matrix;
+typedef enum { LFG_YUV_LIMITED = 0, LFG_YUV_FULL = 1 } lfg_yuv_range;
+typedef enum { LFG_CHROMA_REPLICATE = 0, LFG_CHROMA_LEFT = 1 } lfg_chroma_siting;
+int  lfg_nv12_to_rgba(lfg_context *ctx, const lfg_nv12 *in, lfg_frame *out, int matrix, int range, int siting);
+int  lfg_rgba_to_nv12(lfg_context *ctx, const lfg_frame *in, const lfg_nv12 *out, int matrix, int range, int siting);
+/* The coefficients above.  A pure host function: no context, no GPU.  LFG_ERR_INVALID for a NULL pointer or an unknown enum. */
+int  lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_yuv[9]);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

@@ -23,6 +23,9 @@ SEMANTICS_REFERENCE, SEMANTICS_INTENDED = 0, 1
 ESTIMATOR_FULL_SEARCH, ESTIMATOR_PYRAMID = 0, 1
 INTERPOLATOR_SHADER, INTERPOLATOR_COMPENSATED = 0, 1
 DEFAULT_MATCH_SAD = 48
+YUV_BT601, YUV_BT709 = 0, 1
+YUV_LIMITED, YUV_FULL = 0, 1
+CHROMA_REPLICATE, CHROMA_LEFT = 0, 1
 _BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2}
 COMM_ID_BYTES = 128
 MAX_LANES = 4
@@ -37,6 +40,12 @@ class Frame(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
                 ("pitch", ctypes.c_uint32), ("format", ctypes.c_uint32), ("owned", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class Nv12(ctypes.Structure):
+    """struct lfg_nv12."""
+    _fields_ = [("y", ctypes.c_void_p), ("uv", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("y_pitch", ctypes.c_uint32), ("uv_pitch", ctypes.c_uint32)]
 
 
 class PairStats(ctypes.Structure):
@@ -130,6 +139,9 @@ SIGNATURES = {
     "lfg_last_pair_stats": (_i, [_vp, ctypes.POINTER(PairStats), ctypes.POINTER(_i)]),
     "lfg_frame_diff": (_i, [_vp, _FP, _FP, _u32, _i, _vp]),
     "lfg_frame_diff_summarize": (_i, [ctypes.POINTER(FrameDiffStats), _u32, ctypes.POINTER(FrameDiffSummary)]),
+    "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
+    "lfg_rgba_to_nv12": (_i, [_vp, _FP, ctypes.POINTER(Nv12), _i, _i, _i]),
+    "lfg_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
     "lfg_mv_export_rgba32f": (_i, [_vp, _FP, _vp]),
@@ -167,6 +179,16 @@ def summarize(record, channel_mask: int = 0xF) -> dict:
     if rc != 0:
         raise LfgError(f"lfg_frame_diff_summarize failed ({rc}): bad mask, no pixels, or a histogram that does not sum to them")
     return out.as_dict()
+
+
+def yuv_coefficients(matrix: int, yuv_range: int):
+    """(to_rgb, to_yuv) of lfg_yuv_coefficients: the 5 + 9 integers, scaled by 2^14, that the conversion kernels use.  Needs no
+    context and no GPU."""
+    to_rgb, to_yuv = (ctypes.c_int32 * 5)(), (ctypes.c_int32 * 9)()
+    rc = load().lfg_yuv_coefficients(int(matrix), int(yuv_range), to_rgb, to_yuv)
+    if rc != 0:
+        raise LfgError(f"lfg_yuv_coefficients failed ({rc}): unknown matrix or range")
+    return tuple(int(v) for v in to_rgb), tuple(int(v) for v in to_yuv)
 
 
 def load() -> ctypes.CDLL:
@@ -508,6 +530,38 @@ class Context:
         """(pixels, sse tuple, hist tuple) of a record in device memory; waits for the context."""
         words = [int(v) for v in self.download(record).reshape(-1).view(np.uint64)]
         return words[0], tuple(words[1:5]), tuple(words[5:])
+
+    # -- NV12 input and output.  The planes are caller-owned device memory; create_nv12 keeps both in one MV_S8X2 frame of
+    # W/2 x 3H/2 (W bytes per row: H rows of luma, then H/2 rows of pairs), so upload() and download() move them.
+    def create_nv12(self, width: int, height: int):
+        """(the frame that owns the memory, the lfg_nv12 that describes it): tightly packed planes, luma first."""
+        if width % 2 or height % 2 or width <= 0 or height <= 0:
+            raise ValueError("NV12 wants an even width and height")
+        f = self.create_frame(width // 2, height * 3 // 2, FORMAT_MV_S8X2)
+        return f, Nv12(f.data, f.data + width * height, width, height, width, width)
+
+    def nv12_from(self, y: np.ndarray, uv: np.ndarray):
+        """create_nv12 holding the luma plane y (H, W) and the pairs uv (H/2, W/2, 2), both uint8."""
+        h, w = y.shape
+        f, planes = self.create_nv12(w, h)
+        self.upload(f, np.concatenate([y.reshape(-1), uv.reshape(-1)]).view(np.int8).reshape(h * 3 // 2, w // 2, 2))
+        return f, planes
+
+    def download_nv12(self, f: Frame):
+        """(y, uv) of a frame made by create_nv12."""
+        w, h = f.width * 2, f.height * 2 // 3
+        raw = self.download(f).view(np.uint8).reshape(-1)
+        return raw[:w * h].reshape(h, w), raw[w * h:].reshape(h // 2, w // 2, 2)
+
+    def nv12_to_rgba(self, planes: Nv12, out: Frame, matrix: int = YUV_BT709, yuv_range: int = YUV_LIMITED, siting: int = CHROMA_LEFT):
+        """lfg_nv12_to_rgba: the NV12 planes as an RGBA8 frame of the same size (A = 255); one launch on the selected lane."""
+        self._check(self.lib.lfg_nv12_to_rgba(self.h, ctypes.byref(planes), ctypes.byref(out), int(matrix), int(yuv_range), int(siting)),
+                    "lfg_nv12_to_rgba")
+
+    def rgba_to_nv12(self, src: Frame, planes: Nv12, matrix: int = YUV_BT709, yuv_range: int = YUV_LIMITED, siting: int = CHROMA_LEFT):
+        """lfg_rgba_to_nv12: an RGBA8 frame into NV12 planes of the same size (alpha ignored); one launch on the selected lane."""
+        self._check(self.lib.lfg_rgba_to_nv12(self.h, ctypes.byref(src), ctypes.byref(planes), int(matrix), int(yuv_range), int(siting)),
+                    "lfg_rgba_to_nv12")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -12,6 +12,11 @@ So the rule is checked on the machine code itself, in every gfx950 code object o
     instruction does not write their data registers), which the compiler's hazard recogniser is trusted with and this
     script re-checks.
 
+A second rule rides on the same disassembly: no kernel may contain v_ashr_pk_u8_i32.  hipcc folds two shifted values, each
+clamped to a byte and packed side by side, into it and takes the upper half of its result for zero; the MI355X leaves that
+half of the destination register as it was (csrc/yuv_convert.hip: kept_apart).  A kernel that brings the pattern back is
+wrong on the device only, so the build refuses it.
+
     check_store_hazard.py <liblinuxfg_hip.so>      exit status 1 and a listing on a violation
 """
 import os
@@ -46,6 +51,7 @@ OBJDUMP = find_objdump()
 BUFFER_WINDOW = 6                 # instructions after a buffer store that must leave its data registers alone
 OTHER_WINDOW = 1                  # documented: one wait state
 STORE = re.compile(r"\b(buffer|global|flat|scratch)_store_dwordx[34]\b")
+PACKED_SHIFT = re.compile(r"\bv_ashr_pk_u8_i32\b")   # upper half of the result: kept by the hardware, assumed zero by the compiler
 
 
 def reg_range(tok):
@@ -103,12 +109,18 @@ def main():
         if not objs:
             print("check_store_hazard: no gfx950 code object found in", lib)
             return 1
-        bad, stores = [], 0
+        bad, stores, packed = [], 0, []
         for f in objs:
             out = subprocess.run([OBJDUMP, "-d", os.path.join(tmp, f)], check=True, capture_output=True, text=True).stdout
             lines = [l.split("\t", 1)[1] if "\t" in l else l for l in out.splitlines()]
             stores += sum(1 for l in lines if STORE.search(l))
             bad += check(lines, f)
+            packed += [(f, l.strip()) for l in lines if PACKED_SHIFT.search(l)]
+        if packed:
+            print(f"check_store_hazard: {len(packed)} v_ashr_pk_u8_i32 in the library (the upper half of its result is not cleared on the MI355X):")
+            for name, ins in packed[:20]:
+                print(f"  {name}: {ins}")
+            return 1
         if bad:
             print(f"check_store_hazard: {len(bad)} wide store(s) whose data registers are rewritten too early:")
             for name, st, later in bad[:20]:

@@ -1501,6 +1501,87 @@ LFG_EXPORT int lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, 
     return LFG_OK;
 }
 
+// ---- colour conversion (yuv_convert.hip)
+
+LFG_EXPORT int lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_yuv[9]) {
+    if (!to_rgb || !to_yuv || (matrix != LFG_YUV_BT601 && matrix != LFG_YUV_BT709) || (range != LFG_YUV_LIMITED && range != LFG_YUV_FULL))
+        return LFG_ERR_INVALID;
+    const double kr = matrix == LFG_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == LFG_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double sy = range == LFG_YUV_LIMITED ? 255.0 / 219.0 : 1.0, sc = range == LFG_YUV_LIMITED ? 255.0 / 224.0 : 1.0;
+    const auto q14 = [](double x) { return (int32_t)std::llround(x * 16384.0); };        // (none is a tie: tests/yuv_model.py)
+    to_rgb[0] = q14(sy);
+    to_rgb[1] = q14(2.0 * (1.0 - kr) * sc);
+    to_rgb[2] = q14(2.0 * kb * (1.0 - kb) / kg * sc);
+    to_rgb[3] = q14(2.0 * kr * (1.0 - kr) / kg * sc);
+    to_rgb[4] = q14(2.0 * (1.0 - kb) * sc);
+    to_yuv[0] = q14(kr / sy);
+    to_yuv[2] = q14(kb / sy);
+    to_yuv[1] = q14(1.0 / sy) - to_yuv[0] - to_yuv[2];
+    to_yuv[3] = q14(-kr / (2.0 * (1.0 - kb)) / sc);
+    to_yuv[5] = q14(0.5 / sc);
+    to_yuv[4] = -to_yuv[3] - to_yuv[5];
+    to_yuv[6] = q14(0.5 / sc);
+    to_yuv[8] = q14(-kb / (2.0 * (1.0 - kr)) / sc);
+    to_yuv[7] = -to_yuv[6] - to_yuv[8];
+    return LFG_OK;
+}
+
+namespace {
+
+// The bytes a plane or a frame spans, for the overlap rules.
+struct Span { uintptr_t lo, hi; };
+Span span_of(const void *base, uint32_t pitch, uint32_t rows, size_t rowBytes) {
+    return Span{(uintptr_t)base, (uintptr_t)base + (size_t)pitch * (rows - 1u) + rowBytes};
+}
+bool spans_overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// Everything lfg_nv12_to_rgba and lfg_rgba_to_nv12 require; fills `k`.  `planesOut`: the planes are the output.
+int yuv_check(lfg_context *ctx, const lfg_nv12 *p, const lfg_frame *f, int matrix, int range, int siting, bool planesOut,
+              const char *name, lfg::YuvCoefficients &k) {
+    const std::string n = name;
+    if (!p || !p->y || !p->uv || !frame_ok(f, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, n + ": NULL pointer, or the RGBA frame is empty or of another format");
+    if (p->width == 0 || p->height == 0 || p->width % 2u || p->height % 2u || p->width != f->width || p->height != f->height)
+        return fail(ctx, LFG_ERR_INVALID, n + ": width and height must be even, non-zero and equal to the RGBA frame's");
+    if (p->y_pitch < p->width || p->uv_pitch < p->width || p->uv_pitch % 2u || (uintptr_t)p->uv % 2u)
+        return fail(ctx, LFG_ERR_INVALID, n + ": y_pitch and uv_pitch must be at least the width, uv_pitch even and uv 2-byte aligned");
+    if (f->pitch % 4u || (uintptr_t)f->data % 4u)
+        return fail(ctx, LFG_ERR_INVALID, n + ": the RGBA frame must be 4-byte aligned with a pitch that is a multiple of 4");
+    if (siting != LFG_CHROMA_REPLICATE && siting != LFG_CHROMA_LEFT) return fail(ctx, LFG_ERR_INVALID, n + ": unknown chroma siting");
+    if (lfg_yuv_coefficients(matrix, range, k.to_rgb, k.to_yuv) != LFG_OK) return fail(ctx, LFG_ERR_INVALID, n + ": unknown matrix or range");
+    k.offset = range == LFG_YUV_LIMITED ? 16 : 0;
+    const Span y = span_of(p->y, p->y_pitch, p->height, p->width), uv = span_of(p->uv, p->uv_pitch, p->height / 2u, p->width);
+    const Span rgba = span_of(f->data, f->pitch, f->height, (size_t)f->width * 4u);
+    if (spans_overlap(y, rgba) || spans_overlap(uv, rgba)) return fail(ctx, LFG_ERR_INVALID, n + ": the output overlaps an input");
+    if (planesOut && spans_overlap(y, uv)) return fail(ctx, LFG_ERR_INVALID, n + ": the two output planes overlap each other");
+    if (!lfg::yuv_grid_ok(p->width, p->height)) return fail(ctx, LFG_ERR_INVALID, n + ": frame larger than 8,388,480 x 524,280");
+    return LFG_OK;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_nv12_to_rgba(lfg_context *ctx, const lfg_nv12 *in, lfg_frame *out, int matrix, int range, int siting) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    lfg::YuvCoefficients k;
+    const int rc = yuv_check(ctx, in, out, matrix, range, siting, false, "lfg_nv12_to_rgba", k);
+    if (rc != LFG_OK) return rc;
+    hipError_t e = lfg::launch_nv12_to_rgba(ctx->cur().stream, *in, *out, k, siting);
+    if (e != hipSuccess) return fail_hip(ctx, e, "NV12 to RGBA kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_rgba_to_nv12(lfg_context *ctx, const lfg_frame *in, const lfg_nv12 *out, int matrix, int range, int siting) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    lfg::YuvCoefficients k;
+    const int rc = yuv_check(ctx, out, in, matrix, range, siting, true, "lfg_rgba_to_nv12", k);
+    if (rc != LFG_OK) return rc;
+    hipError_t e = lfg::launch_rgba_to_nv12(ctx->cur().stream, *in, *out, k, siting);
+    if (e != hipSuccess) return fail_hip(ctx, e, "RGBA to NV12 kernel launch");
+    return LFG_OK;
+}
+
 LFG_EXPORT int lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled) {
     if (!ctx) return LFG_ERR_INVALID;
     ctx->fuse_motion_interpolate = enabled != 0;

@@ -322,6 +322,12 @@ hipError_t launch_cut_fallback(hipStream_t s, const lfg_frame &prev, const lfg_f
 // that adds the pair's sums and histogram to it; 16-byte loads where base and pitch of both frames allow, dword loads otherwise.
 hipError_t launch_frame_diff(hipStream_t s, const lfg_frame &a, const lfg_frame &b, uint32_t channelMask, bool accumulate,
                              int deviceCus, void *stats);
+// Colour conversion (yuv_convert.hip): the coefficients of lfg_yuv_coefficients and the range's offset as the kernels take them;
+// one launch each; yuv_grid_ok says whether a frame of this size fits the launch's grid.
+struct YuvCoefficients { int32_t to_rgb[5]; int32_t to_yuv[9]; int32_t offset; };
+bool yuv_grid_ok(uint32_t width, uint32_t height);
+hipError_t launch_nv12_to_rgba(hipStream_t s, const lfg_nv12 &in, const lfg_frame &out, const YuvCoefficients &k, int siting);
+hipError_t launch_rgba_to_nv12(hipStream_t s, const lfg_frame &in, const lfg_nv12 &out, const YuvCoefficients &k, int siting);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

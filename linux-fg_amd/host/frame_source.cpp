@@ -78,7 +78,7 @@ bool RawFileCapture::Initialize(uint32_t width, uint32_t height) {
 }
 
 bool RawFileCapture::NextFrame(uint8_t* host) {
-    const size_t need = (size_t)m_width * m_height * 4;
+    const size_t need = FrameBytes();
     size_t got = 0;
     while (m_file && got < need) {                       // pipes deliver short reads
         const size_t n = fread(host + got, 1, need - got, m_file);
@@ -94,7 +94,7 @@ bool RawFileCapture::NextFrame(uint8_t* host) {
 
 bool ReplayCapture::Initialize(uint32_t width, uint32_t height) {
     if (!m_inner || !m_inner->Initialize(width, height)) return false;
-    m_bytes = (size_t)width * height * 4;
+    m_bytes = m_inner->FrameBytes();
     m_frames.resize(m_bytes * m_count);
     for (uint32_t i = 0; i < m_count; ++i)
         if (!m_inner->NextFrame(m_frames.data() + (size_t)i * m_bytes)) { LOG_ERROR("ReplayCapture: the source ended after ", i, " frames"); return false; }

@@ -19,6 +19,11 @@ public:
     // Fill `host` (width*height*4 bytes, RGBA8, tightly packed) with the next frame.
     virtual bool NextFrame(uint8_t* host) = 0;
     virtual bool GetSize(uint32_t& width, uint32_t& height) const = 0;   // WindowCapture::GetWindowSize
+    // Bytes of one frame as NextFrame writes it: width*height*4 unless the source delivers NV12 (RawFileCapture).
+    virtual size_t FrameBytes() const {
+        uint32_t w = 0, h = 0;
+        return GetSize(w, h) ? (size_t)w * h * 4 : 0;
+    }
 };
 
 // Synthetic content, bit-identical to linux-fg_amd/synth.py: frame 0 is gradient + hashed noise,
@@ -56,6 +61,7 @@ public:
     bool Initialize(uint32_t width, uint32_t height) override;
     bool NextFrame(uint8_t* host) override;
     bool GetSize(uint32_t& width, uint32_t& height) const override { return m_inner->GetSize(width, height); }
+    size_t FrameBytes() const override { return m_inner->FrameBytes(); }
 
 private:
     std::unique_ptr<FrameSource> m_inner;
@@ -65,18 +71,21 @@ private:
 };
 
 // Raw RGBA8 frames (tightly packed, back to back) from a file or a pipe ("-" = stdin): the headless stand-in
-// for a capture device.  NextFrame fails at end of input.
+// for a capture device.  NextFrame fails at end of input.  With `nv12` the frames are NV12 as a decoder writes them: width*height
+// bytes of luma, then width*height/2 bytes of interleaved (Cb, Cr) pairs, 1.5 bytes per pixel (Scaler::SetNv12 converts them).
 class RawFileCapture : public FrameSource {
 public:
-    explicit RawFileCapture(std::string path) : m_path(std::move(path)) {}
+    explicit RawFileCapture(std::string path, bool nv12 = false) : m_path(std::move(path)), m_nv12(nv12) {}
     ~RawFileCapture() override { if (m_file && m_file != stdin) fclose(m_file); }
 
     bool Initialize(uint32_t width, uint32_t height) override;
     bool NextFrame(uint8_t* host) override;
     bool GetSize(uint32_t& width, uint32_t& height) const override { width = m_width; height = m_height; return m_width != 0; }
+    size_t FrameBytes() const override { return m_nv12 ? (size_t)m_width * m_height * 3 / 2 : (size_t)m_width * m_height * 4; }
 
 private:
     std::string m_path;
+    bool m_nv12 = false;
     FILE* m_file = nullptr;
     uint32_t m_width = 0, m_height = 0;
 };

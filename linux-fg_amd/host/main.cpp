@@ -51,8 +51,17 @@ static void PrintUsage() {
               << "  --frames N               Number of input frames to process (default: 10)\n"
               << "  --device N               HIP device ordinal (default: 0)\n"
               << "  --dump-dir DIR           Write every presented frame to DIR as raw RGBA8\n"
-              << "  --input-raw FILE         Read input frames (raw RGBA8, tightly packed, back to back) from FILE, '-' = stdin\n"
-              << "  --output-raw FILE        Append every presented frame (raw RGBA8) to FILE, '-' = stdout\n"
+              << "  --input-raw FILE         Read input frames (raw, tightly packed, back to back) from FILE, '-' = stdin\n"
+              << "  --output-raw FILE        Append every presented frame (raw) to FILE, '-' = stdout\n"
+              << "  --input-format rgba|nv12   What --input-raw holds (default rgba).  nv12: width*height bytes of luma, then width*height/2\n"
+              << "                           bytes of (Cb, Cr) pairs; 1.5 bytes per pixel are uploaded and converted on the GPU.  Needs\n"
+              << "                           --input-raw and even sizes; not with --ranks or --evaluate\n"
+              << "  --output-format rgba|nv12  What --output-raw and --dump-dir receive (default rgba).  nv12: every presented frame is\n"
+              << "                           converted on the GPU and 1.5 bytes per pixel are read back.  Even sizes; not with --ranks or --evaluate\n"
+              << "  --yuv-matrix 601|709     Colour matrix of both conversions (default 709)\n"
+              << "  --yuv-range limited|full Range of both conversions (default limited: luma 16..235, chroma 16..240)\n"
+              << "  --chroma replicate|left  Chroma siting of both conversions (default left: MPEG-2, co-sited with the even columns;\n"
+              << "                           replicate: each pair stands for its 2 x 2 pixels)\n"
               << "  --replay N               Produce the source's first N frames once, before the clock starts, and play them back in rotation\n"
               << "                           (the host's frame synthesis, 5 ms per 1080p frame, then does not bound the loop)\n"
               << "  --present-null           The presenter looks at no pixel (default: a strided checksum over every presented frame)\n"
@@ -75,7 +84,8 @@ int main(int argc, char* argv[]) {
     int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
-    bool syncPresent = false, presentNull = false, evaluate = false;
+    bool syncPresent = false, presentNull = false, evaluate = false, inputNv12 = false, outputNv12 = false;
+    Scaler::YuvModes yuv;
     int replay = 0;
 
     for (int i = 1; i < argc; i++) {
@@ -137,6 +147,31 @@ int main(int argc, char* argv[]) {
         else if (strcmp(argv[i], "--dump-dir") == 0 && i + 1 < argc) dumpDir = argv[++i];
         else if (strcmp(argv[i], "--input-raw") == 0 && i + 1 < argc) inputRaw = argv[++i];
         else if (strcmp(argv[i], "--output-raw") == 0 && i + 1 < argc) outputRaw = argv[++i];
+        else if ((strcmp(argv[i], "--input-format") == 0 || strcmp(argv[i], "--output-format") == 0) && i + 1 < argc) {
+            bool& nv12 = strcmp(argv[i], "--input-format") == 0 ? inputNv12 : outputNv12;
+            const char* m = argv[++i];
+            if (strcmp(m, "rgba") == 0) nv12 = false;
+            else if (strcmp(m, "nv12") == 0) nv12 = true;
+            else { LOG_ERROR("Invalid ", argv[i - 1], " (rgba|nv12)"); return 1; }
+        }
+        else if (strcmp(argv[i], "--yuv-matrix") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "601") == 0) yuv.matrix = LFG_YUV_BT601;
+            else if (strcmp(m, "709") == 0) yuv.matrix = LFG_YUV_BT709;
+            else { LOG_ERROR("Invalid --yuv-matrix (601|709)"); return 1; }
+        }
+        else if (strcmp(argv[i], "--yuv-range") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "limited") == 0) yuv.range = LFG_YUV_LIMITED;
+            else if (strcmp(m, "full") == 0) yuv.range = LFG_YUV_FULL;
+            else { LOG_ERROR("Invalid --yuv-range (limited|full)"); return 1; }
+        }
+        else if (strcmp(argv[i], "--chroma") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "replicate") == 0) yuv.siting = LFG_CHROMA_REPLICATE;
+            else if (strcmp(m, "left") == 0) yuv.siting = LFG_CHROMA_LEFT;
+            else { LOG_ERROR("Invalid --chroma (replicate|left)"); return 1; }
+        }
         else if (strcmp(argv[i], "--sync-present") == 0) syncPresent = true;
         else if (strcmp(argv[i], "--replay") == 0 && i + 1 < argc) replay = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--present-null") == 0) presentNull = true;
@@ -163,6 +198,15 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (inputNv12 || outputNv12) {                              // before a context is made
+        const char* which = inputNv12 ? "--input-format nv12" : "--output-format nv12";
+        if (ranks > 0 || evaluate) { LOG_ERROR(which, " cannot be combined with ", ranks > 0 ? "--ranks" : "--evaluate"); return 2; }
+        if (inputNv12 && inputRaw.empty()) { LOG_ERROR("--input-format nv12 needs --input-raw (the synthetic source makes RGBA8)"); return 2; }
+        if ((inputNv12 && (config.inputWidth % 2 || config.inputHeight % 2)) || (outputNv12 && (config.outputWidth % 2 || config.outputHeight % 2))) {
+            LOG_ERROR("NV12 needs an even width and height");
+            return 2;
+        }
+    }
     if (evaluate) {                                             // before a context is made
         const char* clash = ranks > 0 ? "--ranks" : !factors.empty() ? "--factors" : !config.enableInterpolation ? "--no-interpolation"
                           : !outputRaw.empty() ? "--output-raw" : !dumpDir.empty() ? "--dump-dir" : replay > 0 ? "--replay" : nullptr;
@@ -198,6 +242,7 @@ int main(int argc, char* argv[]) {
         if (!ok) { LOG_ERROR("Evaluation failed: ", Logger::Get().GetLastError()); return 1; }
         printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
                "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
+               "\"input_format\": \"rgba\", \"output_format\": \"rgba\", "
                "\"note\": \"nothing is presented: every second source frame is held out and compared on the GPU\", \"evaluation\": %s}\n",
                frames, (unsigned long long)result.pairs, result.seconds, presentNull ? "true" : "false", result.json.c_str());
         return 0;
@@ -210,7 +255,7 @@ int main(int argc, char* argv[]) {
     }
     {
         std::unique_ptr<FrameSource> source;
-        if (!inputRaw.empty()) source = std::make_unique<RawFileCapture>(inputRaw);
+        if (!inputRaw.empty()) source = std::make_unique<RawFileCapture>(inputRaw, inputNv12);
         else source = std::make_unique<SyntheticCapture>(stream);
         if (replay > 0) source = std::make_unique<ReplayCapture>(std::move(source), (uint32_t)replay);
         Scaler::Get().SetFrameSource(std::move(source));
@@ -218,6 +263,7 @@ int main(int argc, char* argv[]) {
     Scaler::Get().SetPipelined(!syncPresent);
     Scaler::Get().SetFramesInFlight(inFlight);
     Scaler::Get().SetCutCounting(cutThreshold >= 0);
+    Scaler::Get().SetNv12(inputNv12, outputNv12, yuv);
     if (!factors.empty()) Scaler::Get().SetInterpolationFactors(factors);
     FILE* rawOut = nullptr;
     if (!outputRaw.empty()) {
@@ -227,14 +273,14 @@ int main(int argc, char* argv[]) {
     FILE* report = rawOut == stdout ? stderr : stdout;          // keep the pixel stream clean
     uint64_t checksum = 0, presented = 0, generated = 0;
     Scaler::Get().SetPresenter([&](const uint8_t* rgba, uint32_t w, uint32_t h, bool interpolated) {
-        const size_t n = (size_t)w * h * 4;
+        const size_t n = Scaler::Get().PresentedBytes(w, h);    // (NV12 with --output-format nv12)
         uint64_t s = 0;
         if (!presentNull) for (size_t i = 0; i < n; i += 64) s += rgba[i];
         checksum = checksum * 1315423911ull + s;
         if (!dumpDir.empty()) {
             char name[512];
-            snprintf(name, sizeof name, "%s/frame_%04llu_%s_%ux%u.rgba", dumpDir.c_str(), (unsigned long long)presented,
-                     interpolated ? "interp" : "real", w, h);
+            snprintf(name, sizeof name, "%s/frame_%04llu_%s_%ux%u.%s", dumpDir.c_str(), (unsigned long long)presented,
+                     interpolated ? "interp" : "real", w, h, outputNv12 ? "nv12" : "rgba");
             if (FILE* f = fopen(name, "wb")) { fwrite(rgba, 1, n, f); fclose(f); }
         }
         if (rawOut) fwrite(rgba, 1, n, rawOut);
@@ -263,9 +309,11 @@ int main(int argc, char* argv[]) {
     if (rawOut && rawOut != stdout) fclose(rawOut);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
+           "\"input_format\": \"%s\", \"output_format\": \"%s\", "
            "\"note\": \"includes %s, PCIe upload and readback\"}\n",
            frames, (unsigned long long)presented, (unsigned long long)generated, (unsigned long long)cuts, sec, presented / sec,
            (unsigned long long)checksum, syncPresent ? "false" : "true", replay, presentNull ? "true" : "false", inFlight,
+           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba",
            replay > 0 ? "one memcpy per input frame into the staging slot" : "host frame synthesis");
     return 0;
 }

@@ -4,6 +4,17 @@
 
 namespace {
 lfg_context* Ctx() { return HipContext::Get().GetDevice(); }
+
+// An NV12 image of w x h in ONE device allocation: an MV_S8X2 frame of w/2 x 3h/2 has exactly its bytes -- w per row, h rows
+// of luma, then h/2 rows of (Cb, Cr) pairs -- so the rings and lfg_frame_create move and make it like any frame, and NV12
+// needs no lfg_format of its own.
+bool CreateNv12(Frame& f, uint32_t w, uint32_t h) {
+    f.format = LFG_FORMAT_MV_S8X2;
+    return FrameManager::Get().CreateFrame(f, w / 2, h / 2 * 3);
+}
+lfg_nv12 PlanesOf(const Frame& f, uint32_t w, uint32_t h) {
+    return lfg_nv12{f.data, static_cast<uint8_t*>(f.data) + (size_t)w * h, w, h, w, w};
+}
 }
 
 bool Scaler::Initialize(const ScalerConfig& config) {
@@ -15,6 +26,14 @@ bool Scaler::Initialize(const ScalerConfig& config) {
     }
     if (config.inputWidth == 0 || config.inputHeight == 0 || config.outputWidth == 0 || config.outputHeight == 0) {
         LOG_ERROR("Scaler::Initialize: input and output sizes must be non-zero");
+        return false;
+    }
+    if ((m_inputNv12 && (config.inputWidth % 2 || config.inputHeight % 2)) || (m_outputNv12 && (config.outputWidth % 2 || config.outputHeight % 2))) {
+        LOG_ERROR("Scaler::Initialize: NV12 needs an even width and height");
+        return false;
+    }
+    if ((m_inputNv12 || m_outputNv12) && m_sharedSource) {
+        LOG_ERROR("Scaler::Initialize: NV12 input and output are not available in batch mode");
         return false;
     }
     if (!m_source) m_source = std::make_unique<SyntheticCapture>();
@@ -44,10 +63,15 @@ bool Scaler::Initialize(const ScalerConfig& config) {
         LOG_ERROR("Failed to create the lanes: ", lfg_last_error(Ctx()));
         return false;
     }
-    const size_t inBytes = (size_t)config.inputWidth * config.inputHeight * 4;
-    const size_t outBytes = (size_t)config.outputWidth * config.outputHeight * 4;
+    if (m_source->FrameBytes() != (size_t)config.inputWidth * config.inputHeight * (m_inputNv12 ? 3 : 8) / 2) {
+        LOG_ERROR("Scaler::Initialize: the frame source does not deliver ", m_inputNv12 ? "NV12" : "RGBA8", " frames");
+        return false;
+    }
+    const size_t inBytes = m_source->FrameBytes();
+    const size_t outBytes = PresentedBytes(config.outputWidth, config.outputHeight);
+    m_readbackSlots = (uint32_t)((1 + m_lanes) * (m_factors.size() + 1) + 2);   // the calls in flight + the one being presented + margin
     if (lfg_ring_create(Ctx(), (uint32_t)(2 + m_lanes), inBytes, &m_uploadRing) != LFG_OK ||
-        lfg_ring_create(Ctx(), (uint32_t)((1 + m_lanes) * (m_factors.size() + 1) + 2), outBytes, &m_readbackRing) != LFG_OK) {   // the calls in flight + the one being presented + margin
+        lfg_ring_create(Ctx(), m_readbackSlots, outBytes, &m_readbackRing) != LFG_OK) {
         LOG_ERROR("Failed to create pinned frame rings: ", lfg_last_error(Ctx()));
         Cleanup();
         return false;
@@ -104,6 +128,22 @@ bool Scaler::CreateFrameResources() {
             return false;
         }
     }
+    if (m_inputNv12 && m_nv12In.empty()) {
+        m_nv12In.resize((size_t)m_lanes);
+        for (Frame& f : m_nv12In)
+            if (!CreateNv12(f, m_config.inputWidth, m_config.inputHeight)) {
+                LOG_ERROR("Failed to create an NV12 input buffer");
+                return false;
+            }
+    }
+    if (m_outputNv12 && m_nv12Out.empty()) {                  // before the loop: an allocation in it would stall the lanes
+        m_nv12Out.resize(m_readbackSlots);
+        for (Frame& f : m_nv12Out)
+            if (!CreateNv12(f, m_config.outputWidth, m_config.outputHeight)) {
+                LOG_ERROR("Failed to create an NV12 output buffer");
+                return false;
+            }
+    }
     if (m_lanes > 1 && m_inputPool.empty()) {
         m_inputPool.push_back(m_currentFrame);
         m_inputPool.push_back(m_previousFrame);
@@ -139,9 +179,25 @@ bool Scaler::CaptureFrom(FrameSource& source, Frame& frame) {
         LOG_ERROR("Failed to capture frame");
         return false;
     }
+    if (m_inputNv12 && &source == m_source.get()) return ConvertInput(slot, frame);
     lfg_frame f = frame.AsAbi();
     if (lfg_ring_upload(m_uploadRing, slot, &f) != LFG_OK) {
         LOG_ERROR("Failed to upload captured frame: ", lfg_last_error(Ctx()));
+        return false;
+    }
+    return true;
+}
+
+// The slot holds an NV12 frame: it goes into the selected lane's NV12 buffer (whose last reader, that lane's previous
+// conversion, the upload is ordered behind) and from there, on the lane, into `frame`.
+bool Scaler::ConvertInput(uint32_t slot, Frame& frame) {
+    const Frame& staged = m_nv12In[(size_t)lfg_lane_current(Ctx())];
+    lfg_frame up = staged.AsAbi();
+    const lfg_nv12 planes = PlanesOf(staged, frame.width, frame.height);
+    lfg_frame f = frame.AsAbi();
+    if (lfg_ring_upload(m_uploadRing, slot, &up) != LFG_OK ||
+        lfg_nv12_to_rgba(Ctx(), &planes, &f, m_yuv.matrix, m_yuv.range, m_yuv.siting) != LFG_OK) {
+        LOG_ERROR("Failed to upload and convert the captured NV12 frame: ", lfg_last_error(Ctx()));
         return false;
     }
     return true;
@@ -162,8 +218,22 @@ bool Scaler::ScaleFrame(const Frame& input, Frame& output) {
 bool Scaler::QueueReadback(Frame& frame, bool interpolated) {
     void* host = nullptr;
     uint32_t slot = 0;
-    const lfg_frame f = frame.AsAbi();
-    if (lfg_ring_acquire(m_readbackRing, &host, &slot) != LFG_OK || lfg_ring_download(m_readbackRing, slot, &f) != LFG_OK) {
+    lfg_frame f = frame.AsAbi();
+    if (lfg_ring_acquire(m_readbackRing, &host, &slot) != LFG_OK) {
+        LOG_ERROR("Failed to acquire a read-back slot: ", lfg_last_error(Ctx()));
+        return false;
+    }
+    if (m_outputNv12) {
+        // the slot is free, so the last download from its NV12 buffer has finished: convert into it, read that back
+        const Frame& converted = m_nv12Out[slot];
+        const lfg_nv12 planes = PlanesOf(converted, frame.width, frame.height);
+        if (lfg_rgba_to_nv12(Ctx(), &f, &planes, m_yuv.matrix, m_yuv.range, m_yuv.siting) != LFG_OK) {
+            LOG_ERROR("Failed to convert a frame to NV12: ", lfg_last_error(Ctx()));
+            return false;
+        }
+        f = converted.AsAbi();
+    }
+    if (lfg_ring_download(m_readbackRing, slot, &f) != LFG_OK) {
         LOG_ERROR("Failed to read back frame: ", lfg_last_error(Ctx()));
         return false;
     }
@@ -341,6 +411,10 @@ void Scaler::Cleanup() {
         fm.DestroyFrame(m_previousFrame);
     }
     m_inputPool.clear();
+    for (Frame& f : m_nv12In) fm.DestroyFrame(f);
+    for (Frame& f : m_nv12Out) fm.DestroyFrame(f);
+    m_nv12In.clear();
+    m_nv12Out.clear();
     fm.DestroyFrame(m_outputFrame);
     fm.DestroyFrame(m_previousOutput);
     for (Frame& f : m_outputPool) fm.DestroyFrame(f);
