@@ -369,6 +369,51 @@ int  lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, 
 typedef enum lfg_interpolator { LFG_INTERPOLATOR_SHADER = 0, LFG_INTERPOLATOR_COMPENSATED = 1 } lfg_interpolator;
 int  lfg_set_interpolator(lfg_context *ctx, int interpolator, int match_sad);
 
+/* Static-overlay protection for the compensated interpolation, opt-in.  No reference counterpart.  A crosshair, a line of text
+ * or a health bar does not move while the scene behind it pans; in a stroke pixel's 8 x 8 block the moving background outvotes
+ * the stroke, and the compensated interpolation then moves the overlay's pixels with the background.
+ * A mask says which pixels are static; the masked call keeps those where they are and keeps them out of what moves past them.
+ *   Mask: one byte per pixel in caller-owned device memory; a non-zero byte means static.  Like lfg_nv12 it is no lfg_format:
+ *   it is described by an lfg_mask.  pitch >= width, any alignment.
+ *   lfg_static_mask: out(q) = 255 when the sum over the four channels c of |prev(q)_c - curr(q)_c| <= tolerance, else 0;
+ *   0 <= tolerance <= 1020.  prev, curr RGBA8 of the mask's W x H, 4-byte aligned rows.  Only the W bytes of each mask row
+ *   are written, never the row padding; the mask overlaps neither frame.  Any violation or a NULL pointer returns
+ *   LFG_ERR_INVALID before anything is enqueued.  One launch on the selected lane; it keeps no device memory and is outside
+ *   the stage timers.  A host that knows its own UI passes its own mask instead.
+ *   lfg_interpolate_compensated_masked[_multi]: lfg_interpolate_compensated[_multi]'s arguments and `mask` after `mv`; its
+ *   definition word for word, with S(q) = (mask(q) != 0) and these five changes:
+ *   1. Projection: every q with S(q) also does atomicMin(K(q), 0).  Key 0 is the static marker: no vector's key is 0, since
+ *      65535 - |v|^2 >= 32767.  q then goes through the match gate and projects its own vector exactly as before (the overlap
+ *      of a flat moving object with itself is static by any such test, and must keep projecting).  A static location
+ *      therefore always ends as 0, whatever lands on it.
+ *   2. Sampling at d with K(d) = 0: mix(unorm(prev(d)_c), unorm(curr(d)_c), t) per channel from the two texels directly;
+ *      the same mix and store rule, no positions.
+ *   3. Hole walk: a pixel whose key is 0 is passed over like a hole and the walk goes on: an overlay is not the surface
+ *      behind it.
+ *   4. Fetch rule, for every d with K(d) != 0, holes included, before the hole's revealed / covered test and before the
+ *      inside test: p = (clamp((int)floorf(P.x), 0, W - 1), likewise y), and c likewise from C.  S(p) && !S(c) -> Cv alone (the
+ *      content is hidden under the overlay in prev); S(c) && !S(p) -> Pv alone; otherwise the sample proceeds as before.
+ *   5. Hence an all-zero mask gives lfg_interpolate_compensated's bytes for any input.
+ * Frames: lfg_interpolate_compensated's rules; the mask has the frames' W x H and overlaps no output; it is only read.  A
+ * NULL mask or mask->data, a size mismatch or pitch < width returns LFG_ERR_INVALID before anything is enqueued.  The same
+ * launches, lane, device memory and stage timer as lfg_interpolate_compensated. */
+typedef struct lfg_mask { void *data; uint32_t width, height, pitch; } lfg_mask;   /* caller-owned device memory */
+int  lfg_static_mask(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, int tolerance, const lfg_mask *out);
+int  lfg_interpolate_compensated_masked(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                        const lfg_mask *mask, lfg_frame *out, float factor, int match_sad);
+int  lfg_interpolate_compensated_masked_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                              const lfg_mask *mask, lfg_frame *const *outs, const float *factors, uint32_t count,
+                                              int match_sad);
+/* Static protection in lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   tolerance = -1 (default): off; every path as before;
+ *   0 .. 1020, with LFG_INTERPOLATOR_COMPENSATED selected: the vectors as before (the selected estimator, then the refinement if
+ *       it is on), lfg_static_mask(prev, curr, tolerance) once per pair into a per-lane temporary (W x H bytes, grown on
+ *       demand, freed with the lane), then lfg_interpolate_compensated_masked[_multi] in lfg_interpolate_compensated[_multi]'s
+ *       place; cut detection runs around it as before;
+ *   with LFG_INTERPOLATOR_SHADER selected the setting is stored and has no effect.
+ * Any other value: LFG_ERR_INVALID and no change. */
+int  lfg_set_static_protection(lfg_context *ctx, int tolerance);
+
 /* Per-pixel vector refinement, opt-in, between motion estimation and interpolation.  No reference counterpart.  Both
  * estimators give each pixel the vector of the 8 x 8 block around it, so near a moving edge a band of up to ~4 px takes the
  * other side's vector; this picks, for each pixel, the nearby vector that fits a small window around that pixel best.

@@ -48,6 +48,11 @@ class Nv12(ctypes.Structure):
                 ("y_pitch", ctypes.c_uint32), ("uv_pitch", ctypes.c_uint32)]
 
 
+class Mask(ctypes.Structure):
+    """struct lfg_mask."""
+    _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("pitch", ctypes.c_uint32)]
+
+
 class PairStats(ctypes.Structure):
     """struct lfg_pair_stats."""
     _fields_ = [("pixels", ctypes.c_uint64), ("matched", ctypes.c_uint64), ("sad_sum", ctypes.c_uint64)]
@@ -131,6 +136,11 @@ SIGNATURES = {
     "lfg_interpolate_compensated": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
     "lfg_interpolate_compensated_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
     "lfg_set_interpolator": (_i, [_vp, _i, _i]),
+    "lfg_static_mask": (_i, [_vp, _FP, _FP, _i, ctypes.POINTER(Mask)]),
+    "lfg_interpolate_compensated_masked": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(Mask), _FP, ctypes.c_float, _i]),
+    "lfg_interpolate_compensated_masked_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(Mask), ctypes.POINTER(_FP),
+                                                      ctypes.POINTER(ctypes.c_float), _u32, _i]),
+    "lfg_set_static_protection": (_i, [_vp, _i]),
     "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_vector_refinement": (_i, [_vp, _i]),
     "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
@@ -468,6 +478,59 @@ class Context:
     def set_interpolator(self, interpolator: int, match_sad: int = DEFAULT_MATCH_SAD):
         """INTERPOLATOR_SHADER (default) or INTERPOLATOR_COMPENSATED for interpolate_frames[_multi]."""
         self._check(self.lib.lfg_set_interpolator(self.h, int(interpolator), int(match_sad)), "lfg_set_interpolator")
+
+    # -- static-overlay protection.  A mask is caller-owned device memory: create_mask keeps it in an RGBA8 frame of
+    # _MASK_ROW bytes per row, so upload() and download() move it (mask_from / download_mask).
+    _MASK_ROW = 4096
+
+    def create_mask(self, width: int, height: int, pitch: int | None = None, offset: int = 0, fill: int = 0):
+        """(the frame that owns the memory, the lfg_mask that describes it): rows `pitch` (default: width) bytes apart, the first
+        `offset` bytes into the allocation; every byte of the allocation set to `fill`."""
+        pitch = width if pitch is None else int(pitch)
+        rows = -(-(offset + pitch * height) // self._MASK_ROW)
+        f = self.frame_from(np.full((rows, self._MASK_ROW // 4, 4), fill, np.uint8))
+        return f, Mask(f.data + offset, width, height, pitch)
+
+    def mask_from(self, host: np.ndarray, pitch: int | None = None, offset: int = 0, fill: int = 0):
+        """create_mask holding `host` (H, W) uint8; the row padding and the bytes in front of the mask hold `fill`."""
+        h, w = host.shape
+        f, m = self.create_mask(w, h, pitch, offset, fill)
+        raw = np.full(f.height * self._MASK_ROW, fill, np.uint8)
+        rows = raw[offset:offset + m.pitch * h].reshape(h, m.pitch)
+        rows[:, :w] = host
+        self.upload(f, raw.reshape(f.height, -1, 4))
+        return f, m
+
+    def download_mask(self, f: Frame, m: Mask):
+        """(the mask's rows with their padding (H, pitch), every byte of the allocation) of a mask made by create_mask."""
+        raw = self.download(f).reshape(-1)
+        offset = m.data - f.data
+        return raw[offset:offset + m.pitch * m.height].reshape(m.height, m.pitch), raw
+
+    def static_mask(self, prev: Frame, curr: Frame, mask: Mask, tolerance: int = 0):
+        """lfg_static_mask: 255 where the pair's four channel differences sum to at most `tolerance`, else 0."""
+        self._check(self.lib.lfg_static_mask(self.h, ctypes.byref(prev), ctypes.byref(curr), int(tolerance), ctypes.byref(mask)),
+                    "lfg_static_mask")
+
+    def interpolate_compensated_masked(self, prev: Frame, curr: Frame, mv: Frame, mask: Mask, out: Frame, factor: float = 0.5,
+                                       match_sad: int = DEFAULT_MATCH_SAD):
+        """lfg_interpolate_compensated_masked: interpolate_compensated that keeps the mask's static pixels where they are."""
+        self._check(self.lib.lfg_interpolate_compensated_masked(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                                ctypes.byref(mask), ctypes.byref(out), factor, int(match_sad)),
+                    "lfg_interpolate_compensated_masked")
+
+    def interpolate_compensated_masked_multi(self, prev: Frame, curr: Frame, mv: Frame, mask: Mask, outs, factors,
+                                             match_sad: int = DEFAULT_MATCH_SAD):
+        """lfg_interpolate_compensated_masked_multi: one generated frame per factor, each equal to the single call."""
+        po, pf, n = self._multi_args(outs, factors)
+        self._check(self.lib.lfg_interpolate_compensated_masked_multi(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                                      ctypes.byref(mask), po, pf, n, int(match_sad)),
+                    "lfg_interpolate_compensated_masked_multi")
+
+    def set_static_protection(self, tolerance: int):
+        """-1 (default: off) or 0..1020: with INTERPOLATOR_COMPENSATED, interpolate_frames[_multi] make the pair's static mask
+        (lfg_static_mask with this tolerance) and run the masked interpolation in the compensated one's place."""
+        self._check(self.lib.lfg_set_static_protection(self.h, int(tolerance)), "lfg_set_static_protection")
 
     def motion_refine(self, prev: Frame, curr: Frame, mv_in: Frame, mv_out: Frame, radius: int = 1):
         """Per-pixel vector refinement (lfg_motion_refine): each pixel takes, of the vectors of mv_in at it and 4 or 8 px

@@ -6,7 +6,8 @@
 //   mc_project_kernel      one thread per source pixel q: the match gate, then one atomicMin of the vector's key into K(q + d);
 //   mc_interpolate_kernel  one thread per output pixel: K, the hole walk where K is a hole, both bilinear fetches, the blend.
 // The second launch starts once every projection is visible, and it never writes K: a hole's walk reads words of its
-// neighbours that other workgroups also read.
+// neighbours that other workgroups also read.  lfg_interpolate_compensated_masked runs the same two launches through
+// mc_project_masked_kernel and mc_interpolate_masked_kernel (below; tests/overlay_model.c).
 //
 // Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 8
 // (two fetches, mostly cached neighbours) + 4 (out) in the interpolation: 34 bytes, 280 MB at 4K.
@@ -110,7 +111,106 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
     *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
 }
 
+// ---- the same two launches with a static mask (lfg_interpolate_compensated_masked; tests/overlay_model.c restates them).
+// Kernels of their own: the two above stay as they are, instruction for instruction.  Key 0 marks a static location: no
+// vector's key is 0 (65535 - |v|^2 >= 32767), and it is the smallest word, so it outlasts whatever is projected onto it.
+// Extra traffic per pixel and factor: 1 byte of mask in the projection, up to 2 gathered bytes in the interpolation.
+
+constexpr uint32_t kMcStatic = 0u;
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_masked_kernel(
+        const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch, int W, int H, float t,
+        int matchSad, uint32_t *__restrict__ keys) {
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const uint8_t isStatic = mask[(size_t)y * maskPitch + (size_t)x];
+    const Mv v = mv_at(mv, mvPitch, x, y);
+    const uint32_t c = texel_u32(curr, currPitch, x, y);
+    if (isStatic != 0) atomicMin(keys + (size_t)y * (size_t)W + (size_t)x, kMcStatic);
+    if (!matched(prev, prevPitch, c, W, H, x, y, v, matchSad)) return;     // a static pixel projects its own vector as any other
+    const float s = 1.0f - t;
+    const int dx = x + (int)__builtin_floorf((float)v.x * s + 0.5f), dy = y + (int)__builtin_floorf((float)v.y * s + 0.5f);
+    if (dx < 0 || dx >= W || dy < 0 || dy >= H) return;
+    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, mc_key(v));
+}
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch,
+        const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad, uint8_t *__restrict__ out, size_t outPitch) {
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const float s = 1.0f - t;
+    uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
+    if (key == kMcStatic) {                                       // the two texels directly: no positions, no gathers
+        const V4 p = unorm4(texel_u32(prev, (size_t)prevPitch, x, y)), c = unorm4(texel_u32(curr, (size_t)currPitch, x, y));
+        *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) =
+            pack_rgba8_unorm(mixf(p.x, c.x, t), mixf(p.y, c.y, t), mixf(p.z, c.z, t), mixf(p.w, c.w, t));
+        return;
+    }
+    const bool hole = key == kMcHole;
+    if (hole) {
+        // mc_interpolate_kernel's walk, which also passes over static pixels: an overlay is not the surface behind it
+        uint32_t best = kMcHole;
+        const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            for (int k = 1; k <= kMcWalk; ++k) {
+                const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
+                if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
+                const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
+                if (n == kMcHole || n == kMcStatic) continue;
+                const uint32_t order = ((65535u - (n >> 16)) << 16) | (n & 0xffffu);
+                best = order < best ? order : best;
+                break;
+            }
+        }
+        key = best == kMcHole ? (128u << 8) | 128u : best;
+    }
+    const Mv u = mc_decode(key);
+    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+    const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
+    const float Cx = px - (float)u.x * s, Cy = py - (float)u.y * s;
+    const SampleTaps sp = pixel_taps(prev, W, H, prevPitch, Px, Py);
+    const SampleTaps sc = pixel_taps(curr, W, H, currPitch, Cx, Cy);
+    const int cx = clampi((int)__builtin_floorf(Cx), 0, W - 1), cy = clampi((int)__builtin_floorf(Cy), 0, H - 1);
+    const int qx = clampi((int)__builtin_floorf(Px), 0, W - 1), qy = clampi((int)__builtin_floorf(Py), 0, H - 1);
+    const SampleTexels tp = sample_load(sp), tc = sample_load(sc);        // eight texels and the two mask bytes in flight
+    const uint8_t maskP = mask[(size_t)qy * maskPitch + (size_t)qx], maskC = mask[(size_t)cy * maskPitch + (size_t)cx];
+    // 0: blend as a projected pixel, 1: prev's sample alone, 2: curr's alone.  The fetch rule first: content under the overlay
+    // in one frame comes from the other.
+    int only = (maskP != 0 && maskC == 0) ? 2 : (maskC != 0 && maskP == 0) ? 1 : 0;
+    if (only == 0 && hole) {
+        const Mv vc = mv_at(mv, mvPitch, cx, cy);
+        if (!matched(prev, (size_t)prevPitch, texel_u32(curr, (size_t)currPitch, cx, cy), W, H, cx, cy, vc, matchSad)) only = 2;
+        else if (vc.x != u.x || vc.y != u.y) only = 1;
+    }
+    if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
+    const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
+    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
+    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+}
+
 }  // namespace
+
+hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                                 const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {
+    const int W = (int)curr.width, H = (int)curr.height;
+    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 4u, s);
+    if (e != hipSuccess) return e;
+    const dim3 block(kMcBlockX, kMcBlockY), grid((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
+    hipLaunchKernelGGL(mc_project_masked_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
+                       (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
+                       (const uint8_t *)mask.data, (size_t)mask.pitch, W, H, factor, matchSad, keys);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mc_interpolate_masked_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
+                       (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
+                       (const uint8_t *)mask.data, (size_t)mask.pitch, (const uint32_t *)keys, W, H, factor, matchSad,
+                       (uint8_t *)out.data, (size_t)out.pitch);
+    return hipGetLastError();
+}
 
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                           const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {

@@ -143,7 +143,7 @@ int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, 
     return lfg_frame_create(ctx, width, height, format, &f);
 }
 
-// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys).  `what` names the allocation in the error.
+// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys, static_mask).  `what` names the allocation in the error.
 template <typename T>
 int lane_buffer_grow(lfg_context *ctx, T *&buf, size_t &have, size_t need, const char *what) {
     if (need <= have) return LFG_OK;
@@ -483,6 +483,7 @@ void lane_release(lfg_lane_state &l) {
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
     if (l.mc_keys) (void)hipFree(l.mc_keys);
+    if (l.static_mask) (void)hipFree(l.static_mask);
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
     if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
@@ -1143,6 +1144,8 @@ int frame_vectors(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr
 
 int cut_fallback_check(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
                        int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count);
+int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *vectors,
+                       lfg_frame *const *outs, const float *factors, uint32_t count, bool multi);
 int cut_fallback_enqueue(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
                          int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count);
 
@@ -1169,8 +1172,7 @@ int detecting_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *c
     cut.recorded = true;
     cut.permille = permille;
     if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
-        rc = multi ? lfg_interpolate_compensated_multi(ctx, prev, curr, vectors, outs, factors, count, ctx->match_sad)
-                   : lfg_interpolate_compensated(ctx, prev, curr, vectors, outs[0], factors[0], ctx->match_sad);
+        rc = compensated_frames(ctx, prev, curr, vectors, outs, factors, count, multi);
     else
         rc = multi ? lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count)
                    : lfg_interpolate(ctx, prev, curr, vectors, outs[0], factors[0]);
@@ -1210,8 +1212,10 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
     const lfg_frame *vectors = nullptr;
     int rc = frame_vectors(ctx, prev, curr, &vectors);
     if (rc != LFG_OK) return rc;
-    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
-        return lfg_interpolate_compensated(ctx, prev, curr, vectors, out, factor, ctx->match_sad);
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {
+        lfg_frame *const outs[1] = {out};
+        return compensated_frames(ctx, prev, curr, vectors, outs, &factor, 1, false);
+    }
     return lfg_interpolate(ctx, prev, curr, vectors, out, factor);
 }
 
@@ -1252,8 +1256,7 @@ LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *p
     const lfg_frame *vectors = nullptr;
     int rc = frame_vectors(ctx, prev, curr, &vectors);
     if (rc != LFG_OK) return rc;
-    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED)
-        return lfg_interpolate_compensated_multi(ctx, prev, curr, vectors, outs, factors, count, ctx->match_sad);
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) return compensated_frames(ctx, prev, curr, vectors, outs, factors, count, true);
     return lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count);
 }
 
@@ -1269,7 +1272,20 @@ bool frames_overlap(const lfg_frame *a, const lfg_frame *b) {
     return a0 < b1 && b0 < a1;
 }
 
-int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+// The bytes a mask's pixels span against a frame's.
+bool mask_overlaps(const lfg_mask *m, const lfg_frame *f) {
+    const uintptr_t a0 = (uintptr_t)m->data, b0 = (uintptr_t)f->data;
+    const uintptr_t a1 = a0 + (size_t)m->pitch * (m->height - 1u) + (size_t)m->width;
+    const uintptr_t b1 = b0 + (size_t)f->pitch * (f->height - 1u) + (size_t)f->width * bytes_per_pixel(f->format);
+    return a0 < b1 && b0 < a1;
+}
+
+bool mask_ok(const lfg_mask *m, const lfg_frame *like) {
+    return m && m->data && m->width == like->width && m->height == like->height && m->pitch >= m->width;
+}
+
+// lfg_interpolate_compensated[_multi] and, with `masked`, lfg_interpolate_compensated_masked[_multi].
+int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_mask *mask, bool masked,
                     lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name) {
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
@@ -1283,13 +1299,15 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u || mv->pitch % 2u || (uintptr_t)mv->data % 2u)
         return fail(ctx, LFG_ERR_INVALID, n + ": RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
     if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, n + ": match_sad must be in [0, 1020]");
+    if (masked && !mask_ok(mask, curr))
+        return fail(ctx, LFG_ERR_INVALID, n + ": mask must be non-NULL, of the frames' size, with pitch >= width");
     for (uint32_t i = 0; i < count; ++i) {
         const lfg_frame *o = outs[i];
         if (!frame_ok(o, LFG_FORMAT_RGBA8_UNORM) || !same_size(curr, o) || o->pitch % 4u || (uintptr_t)o->data % 4u)
             return fail(ctx, LFG_ERR_INVALID, n + ": bad output frame (NULL, empty, wrong format, size or alignment)");
         if (!std::isfinite(factors[i]) || factors[i] < 0.0f || factors[i] > 1.0f)
             return fail(ctx, LFG_ERR_INVALID, n + ": every factor must be a finite number in [0, 1]");
-        if (frames_overlap(o, prev) || frames_overlap(o, curr) || frames_overlap(o, mv))
+        if (frames_overlap(o, prev) || frames_overlap(o, curr) || frames_overlap(o, mv) || (masked && mask_overlaps(mask, o)))
             return fail(ctx, LFG_ERR_INVALID, n + ": an output aliases an input");
         for (uint32_t j = 0; j < i; ++j)
             if (frames_overlap(outs[j], o)) return fail(ctx, LFG_ERR_INVALID, n + ": two outputs alias each other");
@@ -1300,10 +1318,30 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
     for (uint32_t i = 0; i < count; ++i) {                       // one key image, reused in stream order
-        hipError_t e = lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
+        hipError_t e = masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys)
+                              : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
         if (e != hipSuccess) return fail_hip(ctx, e, "compensated interpolate kernel launch");
     }
     return LFG_OK;
+}
+
+// The compensated interpolation of lfg_interpolate_frames[_multi]: as it is, or with lfg_set_static_protection on the pair's
+// static mask into the lane's temporary and the masked call in its place.
+int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *vectors,
+                       lfg_frame *const *outs, const float *factors, uint32_t count, bool multi) {
+    if (ctx->static_tolerance < 0)
+        return compensated_run(ctx, prev, curr, vectors, nullptr, false, outs, factors, count, ctx->match_sad,
+                               multi ? "lfg_interpolate_compensated_multi" : "lfg_interpolate_compensated");
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    lfg_lane_state &cur = ctx->cur();
+    const size_t bytes = (size_t)curr->width * curr->height;
+    int rc = lane_buffer_grow(ctx, cur.static_mask, cur.static_mask_bytes, bytes, "hipMalloc((void **)&cur.static_mask, bytes)");
+    if (rc != LFG_OK) return rc;
+    const lfg_mask mask{cur.static_mask, curr->width, curr->height, curr->width};
+    rc = lfg_static_mask(ctx, prev, curr, ctx->static_tolerance, &mask);
+    if (rc != LFG_OK) return rc;
+    return compensated_run(ctx, prev, curr, vectors, &mask, true, outs, factors, count, ctx->match_sad,
+                           multi ? "lfg_interpolate_compensated_masked_multi" : "lfg_interpolate_compensated_masked");
 }
 
 }  // namespace
@@ -1311,12 +1349,52 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
 LFG_EXPORT int lfg_interpolate_compensated(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                            lfg_frame *out, float factor, int match_sad) {
     lfg_frame *const outs[1] = {out};
-    return compensated_run(ctx, prev, curr, mv, outs, &factor, 1, match_sad, "lfg_interpolate_compensated");
+    return compensated_run(ctx, prev, curr, mv, nullptr, false, outs, &factor, 1, match_sad, "lfg_interpolate_compensated");
 }
 
 LFG_EXPORT int lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                                  lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad) {
-    return compensated_run(ctx, prev, curr, mv, outs, factors, count, match_sad, "lfg_interpolate_compensated_multi");
+    return compensated_run(ctx, prev, curr, mv, nullptr, false, outs, factors, count, match_sad, "lfg_interpolate_compensated_multi");
+}
+
+// ---- static-overlay protection (static_mask.hip, interpolate_mc.hip)
+
+LFG_EXPORT int lfg_static_mask(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, int tolerance, const lfg_mask *out) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_static_mask: prev and curr must be non-empty RGBA8");
+    if (!same_size(prev, curr)) return fail(ctx, LFG_ERR_INVALID, "lfg_static_mask: prev and curr differ in size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_static_mask: RGBA8 frames must be 4-byte aligned");
+    if (tolerance < 0 || tolerance > 1020) return fail(ctx, LFG_ERR_INVALID, "lfg_static_mask: tolerance must be in [0, 1020]");
+    if (!mask_ok(out, curr))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_static_mask: out must be non-NULL, of the frames' size, with pitch >= width");
+    if (mask_overlaps(out, prev) || mask_overlaps(out, curr))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_static_mask: out overlaps an input");
+    hipError_t e = lfg::launch_static_mask(ctx->cur().stream, *prev, *curr, tolerance, *out);
+    if (e != hipSuccess) return fail_hip(ctx, e, "static mask kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_masked(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                                  const lfg_mask *mask, lfg_frame *out, float factor, int match_sad) {
+    lfg_frame *const outs[1] = {out};
+    return compensated_run(ctx, prev, curr, mv, mask, true, outs, &factor, 1, match_sad, "lfg_interpolate_compensated_masked");
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_masked_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                                        const lfg_mask *mask, lfg_frame *const *outs, const float *factors, uint32_t count,
+                                                        int match_sad) {
+    return compensated_run(ctx, prev, curr, mv, mask, true, outs, factors, count, match_sad, "lfg_interpolate_compensated_masked_multi");
+}
+
+LFG_EXPORT int lfg_set_static_protection(lfg_context *ctx, int tolerance) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (tolerance < -1 || tolerance > 1020)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_static_protection: tolerance must be -1 (off) or in [0, 1020]");
+    ctx->static_tolerance = tolerance;
+    return LFG_OK;
 }
 
 LFG_EXPORT int lfg_set_interpolator(lfg_context *ctx, int interpolator, int match_sad) {

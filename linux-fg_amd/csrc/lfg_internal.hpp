@@ -178,6 +178,9 @@ struct lfg_lane_state {
     // lfg_interpolate_compensated: the key image K of one factor (W * H words), grown on demand
     uint32_t *mc_keys = nullptr;
     size_t mc_keys_bytes = 0;
+    // lfg_set_static_protection: the pair's static mask (W * H bytes), grown on demand
+    uint8_t *static_mask = nullptr;
+    size_t static_mask_bytes = 0;
     hipEvent_t mark = nullptr;                 // lfg_lane_mark
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
@@ -207,6 +210,7 @@ struct lfg_context {
     int match_sad = 48;                        // ... and the compensated interpolator's match gate
     int refine_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_refine's radius, -1 = off (lfg_set_vector_refinement)
     int cut_permille = -1;                     // lfg_interpolate_frames[_multi]: lfg_cut_fallback's threshold, -1 = off (lfg_set_cut_detection)
+    int static_tolerance = -1;                 // lfg_interpolate_frames[_multi]: lfg_static_mask's tolerance, -1 = off (lfg_set_static_protection)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -309,6 +313,10 @@ hipError_t launch_motion_pyramid(hipStream_t s, const lfg_frame &prev, const lfg
 // Motion-compensated interpolation (interpolate_mc.hip): clears `keys` (W * H words), projects, interpolates; one factor.
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                           const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
+// The same with a static mask (interpolate_mc.hip), and the mask of a pair (static_mask.hip): one launch.
+hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                                 const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
+hipError_t launch_static_mask(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, int tolerance, const lfg_mask &out);
 // Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
                                 const lfg_frame &mvOut, int radius);

@@ -42,6 +42,9 @@ static void PrintUsage() {
               << "                           0..2: each pixel takes the nearby vector that fits its (2R+1)^2 window best)\n"
               << "  --cut-threshold P        Scene-cut detection (default -1: off; 0..1000: a pair of which fewer than P pixels per\n"
               << "                           thousand match under its vectors shows a source frame instead of a generated one)\n"
+              << "  --protect-static T       Static-overlay protection of the compensated interpolator (default -1: off; 0..1020: pixels\n"
+              << "                           whose four channels differ by at most T in sum between the pair's frames stay where they\n"
+              << "                           are -- a HUD, a crosshair, text; no effect with --interpolator shader)\n"
               << "  --evaluate               Measure instead of presenting: source frames 0, 2, 4, ... are the stream, 1, 3, 5, ... are\n"
               << "                           held out; each pair's frame at 0.5 is generated under the options above and compared on the\n"
               << "                           GPU, at the output size, with the frame held out -- as is the pair's first frame, shown\n"
@@ -81,7 +84,7 @@ int main(int argc, char* argv[]) {
     int frames = 10, device = 0;
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
-    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1;
+    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1, staticTolerance = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false, evaluate = false, inputNv12 = false, outputNv12 = false;
@@ -140,6 +143,12 @@ int main(int argc, char* argv[]) {
             const long p = strtol(argv[++i], &end, 10);
             if (!end || *end != '\0' || p < -1 || p > 1000) { LOG_ERROR("Invalid --cut-threshold (-1, or 0 to 1000)"); return 1; }
             cutThreshold = (int)p;
+        }
+        else if (strcmp(argv[i], "--protect-static") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long t = strtol(argv[++i], &end, 10);
+            if (!end || end == argv[i] || *end != '\0' || t < -1 || t > 1020) { LOG_ERROR("Invalid --protect-static (-1, or 0 to 1020)"); return 1; }
+            staticTolerance = (int)t;
         }
         else if (strcmp(argv[i], "--evaluate") == 0) evaluate = true;
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
@@ -220,7 +229,8 @@ int main(int argc, char* argv[]) {
         lfg_set_motion_estimator(HipContext::Get().GetDevice(), estimator) != LFG_OK ||
         lfg_set_interpolator(HipContext::Get().GetDevice(), interpolator, 48) != LFG_OK ||
         lfg_set_vector_refinement(HipContext::Get().GetDevice(), refineRadius) != LFG_OK ||
-        lfg_set_cut_detection(HipContext::Get().GetDevice(), cutThreshold) != LFG_OK) {
+        lfg_set_cut_detection(HipContext::Get().GetDevice(), cutThreshold) != LFG_OK ||
+        lfg_set_static_protection(HipContext::Get().GetDevice(), staticTolerance) != LFG_OK) {
         LOG_ERROR("Failed to set the motion options: ", lfg_last_error(HipContext::Get().GetDevice()));
         HipContext::Get().Cleanup();
         return 1;
@@ -242,9 +252,9 @@ int main(int argc, char* argv[]) {
         if (!ok) { LOG_ERROR("Evaluation failed: ", Logger::Get().GetLastError()); return 1; }
         printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
                "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
-               "\"input_format\": \"rgba\", \"output_format\": \"rgba\", "
+               "\"input_format\": \"rgba\", \"output_format\": \"rgba\", \"protect_static\": %d, "
                "\"note\": \"nothing is presented: every second source frame is held out and compared on the GPU\", \"evaluation\": %s}\n",
-               frames, (unsigned long long)result.pairs, result.seconds, presentNull ? "true" : "false", result.json.c_str());
+               frames, (unsigned long long)result.pairs, result.seconds, presentNull ? "true" : "false", staticTolerance, result.json.c_str());
         return 0;
     }
     if (ranks > 0) {
@@ -309,11 +319,11 @@ int main(int argc, char* argv[]) {
     if (rawOut && rawOut != stdout) fclose(rawOut);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
-           "\"input_format\": \"%s\", \"output_format\": \"%s\", "
+           "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, "
            "\"note\": \"includes %s, PCIe upload and readback\"}\n",
            frames, (unsigned long long)presented, (unsigned long long)generated, (unsigned long long)cuts, sec, presented / sec,
            (unsigned long long)checksum, syncPresent ? "false" : "true", replay, presentNull ? "true" : "false", inFlight,
-           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba",
+           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance,
            replay > 0 ? "one memcpy per input frame into the staging slot" : "host frame synthesis");
     return 0;
 }

@@ -2,7 +2,9 @@
 section 4.11 at 1080p and 4K.  The pair is frames 0 and 2 of a synth triple, frame 1 is the truth, the factor 0.5; PSNR and
 differing pixels are taken over R, G and B (mask 0x7).  Three triples: a pan of (3, -2) per frame; a pan of (20, -12) per
 frame, whose pair's (40, -24) is beyond the full search's 16 px and inside the pyramid's reach; the first pan with +-4 levels
-of independent noise on all three frames.  Six routes: repeating frame 0, and lfg_interpolate_frames under five settings.
+of independent noise on all three frames; the first pan under a HUD of thin white glyphs and bars that stands still in all three
+frames.  Seven routes: repeating frame 0, and lfg_interpolate_frames under six settings, the last with
+static-overlay protection (lfg_set_static_protection at tolerance 0).
 Everything goes through lfg_interpolate_frames + lfg_frame_diff, with one sync per route (the read of its record).
 
     python tools/quality_report.py [--sizes 1080p,4k] [--json out.json] [--out report.txt]
@@ -20,13 +22,28 @@ from stage_bench import SIZES, emit, write_json                # (puts the repos
 from linux_fg_amd import capi, synth  # noqa: E402
 
 MASK = 0x7
-ROUTES = [                                                     # (name, estimator, refinement radius, interpolator, semantics)
+ROUTES = [                                     # (name, estimator, refinement radius, interpolator, semantics[, static tolerance])
     ("full search, shader, reference semantics (the default)", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_SHADER, capi.SEMANTICS_REFERENCE),
     ("full search, shader, intended semantics", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_SHADER, capi.SEMANTICS_INTENDED),
     ("full search, compensated", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED),
     ("full search, refine radius 1, compensated", capi.ESTIMATOR_FULL_SEARCH, 1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED),
     ("pyramid, compensated", capi.ESTIMATOR_PYRAMID, -1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED),
+    ("full search, compensated, static protection 0", capi.ESTIMATOR_FULL_SEARCH, -1, capi.INTERPOLATOR_COMPENSATED, capi.SEMANTICS_INTENDED, 0),
 ]
+
+
+def glyphs(w, h):
+    """(H, W) bool: the glyph overlay of DESIGN.md section 4.13 -- eight 6 x 9 glyphs of 1 px strokes, a 1 px bar and a 2 px
+    bar per 200 x 120 tile -- repeated over the frame."""
+    tile = np.zeros((120, 200), bool)
+    for k in range(8):
+        x = 20 + 10 * k
+        tile[12:21, x] = True
+        for r in (12, 16, 20):
+            tile[r, x:x + 6] = True
+    tile[100, 10:190] = True
+    tile[96:112, 150:152] = True
+    return np.tile(tile, (-(-h // 120), -(-w // 200)))[:h, :w]
 
 
 def triples(w, h):
@@ -40,6 +57,10 @@ def triples(w, h):
     clean = [f0, f1, synth.translate(f1, (3, -2))]
     rng = np.random.default_rng(11)
     yield ("pan(3,-2)+-4noise", *[np.clip(f.astype(np.int16) + rng.integers(-4, 5, f.shape), 0, 255).astype(np.uint8) for f in clean])
+    hud = [f.copy() for f in clean]
+    for f in hud:
+        f[glyphs(w, h)] = 255
+    yield ("pan(3,-2)+glyphs", *hud)
 
 
 def main():
@@ -63,7 +84,8 @@ def main():
 
                 ctx.frame_diff(p, t, r, MASK)
                 row("repeat prev (no generation)")
-                for name, estimator, radius, interpolator, semantics in ROUTES:
+                for name, estimator, radius, interpolator, semantics, *tolerance in ROUTES:
+                    ctx.set_static_protection(tolerance[0] if tolerance else -1)
                     ctx.set_motion_estimator(estimator)
                     ctx.set_vector_refinement(radius)
                     ctx.set_interpolator(interpolator)
