@@ -559,6 +559,34 @@ int  lfg_rgba_to_nv12(lfg_context *ctx, const lfg_frame *in, const lfg_nv12 *out
 /* The coefficients above.  A pure host function: no context, no GPU.  LFG_ERR_INVALID for a NULL pointer or an unknown enum. */
 int  lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_yuv[9]);
 
+/* Contrast-limited sharpening of a presented frame.  No reference counterpart: the reference presents what scale.comp wrote
+ * (src/scaler.cpp:479-536).  Integer arithmetic only; it depends on no setting of the context.
+ *   Inputs: in, out RGBA8, both W x H with W, H >= 1; 0 <= strength <= 64.
+ *   For pixel q = (x, y) and each of the four channels c (all four alike, as everywhere else in this ABI; a constant alpha is
+ *   flat and so unchanged):
+ *     C = in(x, y)_c;  N, S, W, E = in(x, y - 1)_c, in(x, y + 1)_c, in(x - 1, y)_c, in(x + 1, y)_c, the neighbour coordinates
+ *     clamped to the frame -- the frame the caller described: a view made with lfg_frame_wrap is its own image, and nothing
+ *     outside it is read;
+ *     L = 4 C - N - S - W - E;  lo = min(C, N, S, W, E);  hi = max(C, N, S, W, E);
+ *     out(x, y)_c = clamp(C + ((strength * L + 32) >> 6), lo, hi), >> the arithmetic shift (floor).
+ *   Strength 64 is the classic kernel (0 -1 0 / -1 5 -1 / 0 -1 0) limited to the local range; strength 0 copies.
+ *   |strength * L + 32| reaches 65,312: it fits 32 bits and does NOT fit a 16-bit half; L (+-1020) and the min / max do.
+ *   Limited: a pixel never leaves the range of itself and its four neighbours.  So edges steepen, while hard steps, flat areas,
+ *   linear ramps and every local extremum stay as they are (the upscale's ringing is not amplified, one-pixel strokes get no
+ *   halo), and the minimum and the maximum of a frame do not move.
+ * Where: at the presentation end only, on a copy.  A frame that a motion, mask, cut or interpolation call will read must stay
+ * unsharpened: sharpening raises per-pixel differences, and the match gate, the static mask and the cut statistics are
+ * thresholds on those differences.
+ * Frames: in and out both RGBA8 and both W x H with W, H >= 1; rows 4-byte aligned, the pitch a multiple of 4; out overlaps no
+ * byte of in (every output depends on its neighbours' inputs, so the call cannot run in place); frames of 2 GiB and more are
+ * addressed with size_t offsets.  Any violation, a NULL pointer or NULL data, a wrong format or a strength outside 0 .. 64
+ * returns LFG_ERR_INVALID before anything is enqueued, and latches a message.  Enqueued on the selected lane (one launch
+ * through 16-byte accesses where base and pitch of both frames are multiples of 16, with a second one for the 1 .. 3 columns
+ * past the last multiple of 4; one launch through 4-byte accesses otherwise); keeps no device memory; outside the stage
+ * timers (like a conversion it is no stage of the path).  Only the W * 4 bytes of each output row are written, never the row
+ * padding. */
+int  lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int strength);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

@@ -29,6 +29,7 @@ CHROMA_REPLICATE, CHROMA_LEFT = 0, 1
 _BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2}
 COMM_ID_BYTES = 128
 MAX_LANES = 4
+MAX_SHARPEN = 64
 
 
 class LfgError(RuntimeError):
@@ -151,6 +152,7 @@ SIGNATURES = {
     "lfg_frame_diff_summarize": (_i, [ctypes.POINTER(FrameDiffStats), _u32, ctypes.POINTER(FrameDiffSummary)]),
     "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
     "lfg_rgba_to_nv12": (_i, [_vp, _FP, ctypes.POINTER(Nv12), _i, _i, _i]),
+    "lfg_sharpen": (_i, [_vp, _FP, _FP, _i]),
     "lfg_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
@@ -625,6 +627,11 @@ class Context:
         """lfg_rgba_to_nv12: an RGBA8 frame into NV12 planes of the same size (alpha ignored); one launch on the selected lane."""
         self._check(self.lib.lfg_rgba_to_nv12(self.h, ctypes.byref(src), ctypes.byref(planes), int(matrix), int(yuv_range), int(siting)),
                     "lfg_rgba_to_nv12")
+
+    def sharpen(self, src: Frame, dst: Frame, strength: int):
+        """lfg_sharpen: `src` sharpened into `dst` (both RGBA8, one size, no overlap), strength 0 .. MAX_SHARPEN, limited to
+        the range of each pixel and its four neighbours; for presented frames only, never for one a motion stage reads."""
+        self._check(self.lib.lfg_sharpen(self.h, ctypes.byref(src), ctypes.byref(dst), int(strength)), "lfg_sharpen")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -1660,6 +1660,23 @@ LFG_EXPORT int lfg_rgba_to_nv12(lfg_context *ctx, const lfg_frame *in, const lfg
     return LFG_OK;
 }
 
+// ---- sharpening of presented frames (sharpen.hip)
+
+LFG_EXPORT int lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int strength) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: in and out must be non-empty RGBA8");
+    if (!same_size(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: in and out differ in size");
+    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    if (strength < 0 || strength > 64) return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: strength must be in [0, 64]");
+    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: the output overlaps the input");
+    hipError_t e = lfg::launch_sharpen(ctx->cur().stream, *in, *out, strength);
+    if (e != hipSuccess) return fail_hip(ctx, e, "sharpen kernel launch");
+    return LFG_OK;
+}
+
 LFG_EXPORT int lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled) {
     if (!ctx) return LFG_ERR_INVALID;
     ctx->fuse_motion_interpolate = enabled != 0;

@@ -336,6 +336,9 @@ struct YuvCoefficients { int32_t to_rgb[5]; int32_t to_yuv[9]; int32_t offset; }
 bool yuv_grid_ok(uint32_t width, uint32_t height);
 hipError_t launch_nv12_to_rgba(hipStream_t s, const lfg_nv12 &in, const lfg_frame &out, const YuvCoefficients &k, int siting);
 hipError_t launch_rgba_to_nv12(hipStream_t s, const lfg_frame &in, const lfg_nv12 &out, const YuvCoefficients &k, int siting);
+// Contrast-limited sharpening (sharpen.hip): the 16-byte kernel where base and pitch of both frames allow, with the dword
+// kernel behind it for the 1 .. 3 columns past the last multiple of 4; the dword kernel alone otherwise.
+hipError_t launch_sharpen(hipStream_t s, const lfg_frame &in, const lfg_frame &out, int strength);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

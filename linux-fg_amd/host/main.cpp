@@ -45,6 +45,10 @@ static void PrintUsage() {
               << "  --protect-static T       Static-overlay protection of the compensated interpolator (default -1: off; 0..1020: pixels\n"
               << "                           whose four channels differ by at most T in sum between the pair's frames stay where they\n"
               << "                           are -- a HUD, a crosshair, text; no effect with --interpolator shader)\n"
+              << "  --sharpen S              Contrast-limited sharpening of every presented frame, real and generated alike (default 0: off;\n"
+              << "                           1..64: strength in 64ths of the classic 5-point kernel, each pixel kept within the range of\n"
+              << "                           itself and its four neighbours).  Applied to a copy just before the read-back: motion, masks and\n"
+              << "                           cut detection see the unsharpened frames.  --evaluate does not sharpen\n"
               << "  --evaluate               Measure instead of presenting: source frames 0, 2, 4, ... are the stream, 1, 3, 5, ... are\n"
               << "                           held out; each pair's frame at 0.5 is generated under the options above and compared on the\n"
               << "                           GPU, at the output size, with the frame held out -- as is the pair's first frame, shown\n"
@@ -149,6 +153,12 @@ int main(int argc, char* argv[]) {
             const long t = strtol(argv[++i], &end, 10);
             if (!end || end == argv[i] || *end != '\0' || t < -1 || t > 1020) { LOG_ERROR("Invalid --protect-static (-1, or 0 to 1020)"); return 1; }
             staticTolerance = (int)t;
+        }
+        else if (strcmp(argv[i], "--sharpen") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long v = strtol(argv[++i], &end, 10);
+            if (!end || end == argv[i] || *end != '\0' || v < 0 || v > 64) { LOG_ERROR("Invalid --sharpen (0 to 64)"); return 1; }
+            config.sharpen = (uint32_t)v;
         }
         else if (strcmp(argv[i], "--evaluate") == 0) evaluate = true;
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
@@ -317,13 +327,15 @@ int main(int argc, char* argv[]) {
     HipContext::Get().Cleanup();
     if (!ok) { LOG_ERROR("ProcessFrame failed: ", Logger::Get().GetLastError()); return 1; }
     if (rawOut && rawOut != stdout) fclose(rawOut);
+    char sharpenField[32] = "";
+    if (config.sharpen > 0) snprintf(sharpenField, sizeof sharpenField, "\"sharpen\": %u, ", config.sharpen);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
-           "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, "
+           "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, %s"
            "\"note\": \"includes %s, PCIe upload and readback\"}\n",
            frames, (unsigned long long)presented, (unsigned long long)generated, (unsigned long long)cuts, sec, presented / sec,
            (unsigned long long)checksum, syncPresent ? "false" : "true", replay, presentNull ? "true" : "false", inFlight,
-           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance,
+           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance, sharpenField,
            replay > 0 ? "one memcpy per input frame into the staging slot" : "host frame synthesis");
     return 0;
 }

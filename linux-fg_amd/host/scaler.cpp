@@ -144,6 +144,14 @@ bool Scaler::CreateFrameResources() {
                 return false;
             }
     }
+    if (m_config.sharpen > 0 && m_sharpened.empty()) {       // before the loop, like the NV12 buffers
+        m_sharpened.resize(m_readbackSlots);
+        for (Frame& f : m_sharpened)
+            if (!fm.CreateFrame(f, m_config.outputWidth, m_config.outputHeight)) {
+                LOG_ERROR("Failed to create a sharpened frame");
+                return false;
+            }
+    }
     if (m_lanes > 1 && m_inputPool.empty()) {
         m_inputPool.push_back(m_currentFrame);
         m_inputPool.push_back(m_previousFrame);
@@ -222,6 +230,16 @@ bool Scaler::QueueReadback(Frame& frame, bool interpolated) {
     if (lfg_ring_acquire(m_readbackRing, &host, &slot) != LFG_OK) {
         LOG_ERROR("Failed to acquire a read-back slot: ", lfg_last_error(Ctx()));
         return false;
+    }
+    if (m_config.sharpen > 0) {
+        // the slot is free, so the last download from its sharpened frame has finished: sharpen into it, and that is the frame
+        // presented from here on; `frame` itself, which the next pair's motion may read, stays as it is
+        lfg_frame sharpened = m_sharpened[slot].AsAbi();
+        if (lfg_sharpen(Ctx(), &f, &sharpened, (int)m_config.sharpen) != LFG_OK) {
+            LOG_ERROR("Failed to sharpen a frame: ", lfg_last_error(Ctx()));
+            return false;
+        }
+        f = sharpened;
     }
     if (m_outputNv12) {
         // the slot is free, so the last download from its NV12 buffer has finished: convert into it, read that back
@@ -413,6 +431,8 @@ void Scaler::Cleanup() {
     m_inputPool.clear();
     for (Frame& f : m_nv12In) fm.DestroyFrame(f);
     for (Frame& f : m_nv12Out) fm.DestroyFrame(f);
+    for (Frame& f : m_sharpened) fm.DestroyFrame(f);
+    m_sharpened.clear();
     m_nv12In.clear();
     m_nv12Out.clear();
     fm.DestroyFrame(m_outputFrame);
