@@ -414,6 +414,57 @@ int  lfg_interpolate_compensated_masked_multi(lfg_context *ctx, const lfg_frame 
  * Any other value: LFG_ERR_INVALID and no change. */
 int  lfg_set_static_protection(lfg_context *ctx, int tolerance);
 
+/* Motion-compensated extrapolation, opt-in: the frame at time 1 + a, AHEAD of the newest frame, predicted from the motion just
+ * measured.  No reference counterpart (the reference only generates frames between two real ones).  Every interpolated frame
+ * holds the newest real frame back by a source-frame interval; an extrapolated one does not: the real frame is presented as it
+ * arrives and the generated ones follow it.  curr's content is projected forward along its vectors and curr
+ * alone is fetched along the projected vectors.  Always in pixels and with the vectors' own signs: it does not depend on
+ * lfg_set_semantics.  All float arithmetic is fp32 without contraction.
+ *   Inputs: prev, curr RGBA8 and mv LFG_FORMAT_MV_S8X2 (any byte values), all W x H; `ahead` a finite in [0, 1], prev being at
+ *   time 0 and curr at time 1; 0 <= match_sad <= 1020.
+ *   Match gate: lfg_interpolate_compensated's, word for word: q with v = mv(q) is matched when sum over c of |curr(q)_c -
+ *   prev(q + v)_c| <= match_sad, prev outside the image read as 0.  An unmatched pixel's motion is unknown: it does not project.
+ *   Projection: content at q in curr came from q + v, so it moves by -v per interval.  Every matched q: dx = (int)floorf(0.5f -
+ *   (float)v.x * a), dy likewise, d = q + (dx, dy); outside the image dropped, otherwise atomicMin of
+ *   lfg_interpolate_compensated's key ((65535 - (vx^2 + vy^2)) << 16) | ((vy + 128) << 8) | (vx + 128) into K(d), K starting at
+ *   0xFFFFFFFF (a hole): the longest vector wins, then the smallest vy, then the smallest vx.
+ *   Sampling at d with the vector u decoded from K(d): C = ((float)d.x + 0.5f) + (float)u.x * a, y likewise; the output is curr
+ *   fetched at C with the bilinear clamp-to-edge rule of lfg_interpolate_compensated (same floor, weights and sum order, in
+ *   pixel units), stored as it stores.  prev is never sampled: only the match gate reads it.
+ *   Holes (K(d) = 0xFFFFFFFF): walk from d in the directions +x, -x, +y, -y in that order, k = 1 .. 16, stopping at the image
+ *   edge, and keep each direction's first non-hole pixel n.  Of the kept pixels the one with the smallest (|v|^2, vy, vx) (the
+ *   background-most) is the donor, on an equal triple the earlier direction's; u is its vector and n its position.  If no
+ *   direction kept one, u = (0, 0) and there is no donor.  C as above and c = (clamp((int)floorf(C.x), 0, W - 1), likewise y).
+ *   If there is a donor, c is matched and mv(c) != u, curr shows the foreground at c and the surface behind it is visible in
+ *   neither frame: then C := ((float)n.x + 0.5f) + (float)u.x * a, y likewise -- the background's edge is stretched over what
+ *   the foreground vacates instead of leaving a copy of the foreground behind it.  In every other case C stays.  The output is
+ *   curr fetched at C.
+ *   Hence a = 0 gives curr exactly for any vectors and match_sad; a uniform vector v that matches everywhere gives out(d) =
+ *   curr(d + v) at a = 1 and, for even v, curr(d + v / 2) at a = 0.5, both at every d whose source (d + v, d + v / 2) lies inside
+ *   the image.
+ * Frames and errors: lfg_interpolate_compensated's rules (4-byte aligned RGBA8 rows of any pitch that is a multiple of 4, 2-byte
+ * aligned mv, outputs overlapping neither each other nor an input).  Any violation, and a NaN, infinite or out-of-range `ahead`
+ * or match_sad, returns LFG_ERR_INVALID before anything is enqueued.  Uses the lane's key image of lfg_interpolate_compensated
+ * (4 * W * H bytes, grown on demand) and keeps no other device memory.  Enqueued on the selected lane (clear K, project, sample
+ * per factor); timed under LFG_STAGE_INTERPOLATE.  _multi: 1 <= count <= LFG_MAX_FACTORS, outs[i] for aheads[i], each identical
+ * to the single call.  Not built: a masked (overlay-protected) extrapolation, a projection shared between factors, a > 1. */
+int  lfg_extrapolate_compensated(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                 lfg_frame *out, float ahead, int match_sad);
+int  lfg_extrapolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                       lfg_frame *const *outs, const float *aheads, uint32_t count, int match_sad);
+/* What lfg_interpolate_frames and lfg_interpolate_frames_multi generate (nothing else):
+ *   LFG_GENERATION_INTERPOLATE (default): frames between prev and curr; every path as before;
+ *   LFG_GENERATION_EXTRAPOLATE, with LFG_INTERPOLATOR_COMPENSATED selected: the vectors as before (the selected estimator, then
+ *       the refinement if it is on), then lfg_extrapolate_compensated[_multi] in the compensated interpolator's place, each
+ *       factors[i] read as an `ahead`.  With cut detection on, lfg_pair_match and the record run as before and lfg_cut_fallback
+ *       is enqueued with every factor passed as 1.0f: a cut gives curr, the newest frame repeated, for every output.
+ *       lfg_set_static_protection has no effect on extrapolated frames (a masked extrapolation is not built), and
+ *       lfg_set_fused_motion_interpolate does not apply;
+ *   with LFG_INTERPOLATOR_SHADER selected the setting is stored and has no effect.
+ * Any other value: LFG_ERR_INVALID and no change. */
+typedef enum lfg_generation { LFG_GENERATION_INTERPOLATE = 0, LFG_GENERATION_EXTRAPOLATE = 1 } lfg_generation;
+int  lfg_set_generation(lfg_context *ctx, int generation);
+
 /* Per-pixel vector refinement, opt-in, between motion estimation and interpolation.  No reference counterpart.  Both
  * estimators give each pixel the vector of the 8 x 8 block around it, so near a moving edge a band of up to ~4 px takes the
  * other side's vector; this picks, for each pixel, the nearby vector that fits a small window around that pixel best.

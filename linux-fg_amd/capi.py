@@ -22,6 +22,7 @@ MOTION_PREFILTERED, MOTION_EXACT_ONLY = 0, 1
 SEMANTICS_REFERENCE, SEMANTICS_INTENDED = 0, 1
 ESTIMATOR_FULL_SEARCH, ESTIMATOR_PYRAMID = 0, 1
 INTERPOLATOR_SHADER, INTERPOLATOR_COMPENSATED = 0, 1
+GENERATION_INTERPOLATE, GENERATION_EXTRAPOLATE = 0, 1
 DEFAULT_MATCH_SAD = 48
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
@@ -142,6 +143,9 @@ SIGNATURES = {
     "lfg_interpolate_compensated_masked_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(Mask), ctypes.POINTER(_FP),
                                                       ctypes.POINTER(ctypes.c_float), _u32, _i]),
     "lfg_set_static_protection": (_i, [_vp, _i]),
+    "lfg_extrapolate_compensated": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
+    "lfg_extrapolate_compensated_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
+    "lfg_set_generation": (_i, [_vp, _i]),
     "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_vector_refinement": (_i, [_vp, _i]),
     "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
@@ -533,6 +537,24 @@ class Context:
         """-1 (default: off) or 0..1020: with INTERPOLATOR_COMPENSATED, interpolate_frames[_multi] make the pair's static mask
         (lfg_static_mask with this tolerance) and run the masked interpolation in the compensated one's place."""
         self._check(self.lib.lfg_set_static_protection(self.h, int(tolerance)), "lfg_set_static_protection")
+
+    def extrapolate_compensated(self, prev: Frame, curr: Frame, mv: Frame, out: Frame, ahead: float = 1.0,
+                                match_sad: int = DEFAULT_MATCH_SAD):
+        """Motion-compensated extrapolation (lfg_extrapolate_compensated): the frame at time 1 + `ahead`, curr's content
+        projected forward along its vectors and curr alone fetched along them."""
+        self._check(self.lib.lfg_extrapolate_compensated(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                         ctypes.byref(out), ahead, int(match_sad)), "lfg_extrapolate_compensated")
+
+    def extrapolate_compensated_multi(self, prev: Frame, curr: Frame, mv: Frame, outs, aheads, match_sad: int = DEFAULT_MATCH_SAD):
+        """lfg_extrapolate_compensated_multi: one generated frame per `ahead`, each equal to the single call."""
+        po, pf, n = self._multi_args(outs, aheads)
+        self._check(self.lib.lfg_extrapolate_compensated_multi(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                               po, pf, n, int(match_sad)), "lfg_extrapolate_compensated_multi")
+
+    def set_generation(self, generation: int):
+        """GENERATION_INTERPOLATE (default) or GENERATION_EXTRAPOLATE: with INTERPOLATOR_COMPENSATED, interpolate_frames[_multi]
+        read each factor as an `ahead` and run the extrapolation in the compensated interpolation's place."""
+        self._check(self.lib.lfg_set_generation(self.h, int(generation)), "lfg_set_generation")
 
     def motion_refine(self, prev: Frame, curr: Frame, mv_in: Frame, mv_out: Frame, radius: int = 1):
         """Per-pixel vector refinement (lfg_motion_refine): each pixel takes, of the vectors of mv_in at it and 4 or 8 px

@@ -1177,6 +1177,11 @@ int detecting_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *c
         rc = multi ? lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count)
                    : lfg_interpolate(ctx, prev, curr, vectors, outs[0], factors[0]);
     if (rc != LFG_OK) return rc;
+    if (ctx->generation == LFG_GENERATION_EXTRAPOLATE && ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {
+        float newest[LFG_MAX_FACTORS];                            // a cut repeats the newest frame: curr for every output
+        for (uint32_t i = 0; i < count; ++i) newest[i] = 1.0f;
+        return cut_fallback_enqueue(ctx, prev, curr, cut.device, permille, outs, newest, count);
+    }
     return cut_fallback_enqueue(ctx, prev, curr, cut.device, permille, outs, factors, count);
 }
 
@@ -1284,9 +1289,13 @@ bool mask_ok(const lfg_mask *m, const lfg_frame *like) {
     return m && m->data && m->width == like->width && m->height == like->height && m->pitch >= m->width;
 }
 
-// lfg_interpolate_compensated[_multi] and, with `masked`, lfg_interpolate_compensated_masked[_multi].
-int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_mask *mask, bool masked,
+// The three stages that project the vectors into the lane's key image: lfg_interpolate_compensated[_multi], with a mask
+// lfg_interpolate_compensated_masked[_multi], and lfg_extrapolate_compensated[_multi], whose factors are its `aheads`.
+enum class McKind { Plain, Masked, Extrapolate };
+
+int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_mask *mask, McKind kind,
                     lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name) {
+    const bool masked = kind == McKind::Masked;
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     const std::string n(name);
@@ -1319,18 +1328,24 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
     for (uint32_t i = 0; i < count; ++i) {                       // one key image, reused in stream order
         hipError_t e = masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys)
+                       : kind == McKind::Extrapolate
+                              ? lfg::launch_extrapolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys)
                               : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
-        if (e != hipSuccess) return fail_hip(ctx, e, "compensated interpolate kernel launch");
+        if (e != hipSuccess) return fail_hip(ctx, e, kind == McKind::Extrapolate ? "compensated extrapolate kernel launch" : "compensated interpolate kernel launch");
     }
     return LFG_OK;
 }
 
 // The compensated interpolation of lfg_interpolate_frames[_multi]: as it is, or with lfg_set_static_protection on the pair's
-// static mask into the lane's temporary and the masked call in its place.
+// static mask into the lane's temporary and the masked call in its place; under LFG_GENERATION_EXTRAPOLATE the extrapolation
+// in the place of both.
 int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *vectors,
                        lfg_frame *const *outs, const float *factors, uint32_t count, bool multi) {
+    if (ctx->generation == LFG_GENERATION_EXTRAPOLATE)             // each factor is an `ahead`; static protection does not apply
+        return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Extrapolate, outs, factors, count, ctx->match_sad,
+                               multi ? "lfg_extrapolate_compensated_multi" : "lfg_extrapolate_compensated");
     if (ctx->static_tolerance < 0)
-        return compensated_run(ctx, prev, curr, vectors, nullptr, false, outs, factors, count, ctx->match_sad,
+        return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Plain, outs, factors, count, ctx->match_sad,
                                multi ? "lfg_interpolate_compensated_multi" : "lfg_interpolate_compensated");
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     lfg_lane_state &cur = ctx->cur();
@@ -1340,7 +1355,7 @@ int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
     const lfg_mask mask{cur.static_mask, curr->width, curr->height, curr->width};
     rc = lfg_static_mask(ctx, prev, curr, ctx->static_tolerance, &mask);
     if (rc != LFG_OK) return rc;
-    return compensated_run(ctx, prev, curr, vectors, &mask, true, outs, factors, count, ctx->match_sad,
+    return compensated_run(ctx, prev, curr, vectors, &mask, McKind::Masked, outs, factors, count, ctx->match_sad,
                            multi ? "lfg_interpolate_compensated_masked_multi" : "lfg_interpolate_compensated_masked");
 }
 
@@ -1349,12 +1364,33 @@ int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
 LFG_EXPORT int lfg_interpolate_compensated(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                            lfg_frame *out, float factor, int match_sad) {
     lfg_frame *const outs[1] = {out};
-    return compensated_run(ctx, prev, curr, mv, nullptr, false, outs, &factor, 1, match_sad, "lfg_interpolate_compensated");
+    return compensated_run(ctx, prev, curr, mv, nullptr, McKind::Plain, outs, &factor, 1, match_sad, "lfg_interpolate_compensated");
 }
 
 LFG_EXPORT int lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                                  lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad) {
-    return compensated_run(ctx, prev, curr, mv, nullptr, false, outs, factors, count, match_sad, "lfg_interpolate_compensated_multi");
+    return compensated_run(ctx, prev, curr, mv, nullptr, McKind::Plain, outs, factors, count, match_sad, "lfg_interpolate_compensated_multi");
+}
+
+// ---- motion-compensated extrapolation (extrapolate_mc.hip)
+
+LFG_EXPORT int lfg_extrapolate_compensated(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                           lfg_frame *out, float ahead, int match_sad) {
+    lfg_frame *const outs[1] = {out};
+    return compensated_run(ctx, prev, curr, mv, nullptr, McKind::Extrapolate, outs, &ahead, 1, match_sad, "lfg_extrapolate_compensated");
+}
+
+LFG_EXPORT int lfg_extrapolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                                 lfg_frame *const *outs, const float *aheads, uint32_t count, int match_sad) {
+    return compensated_run(ctx, prev, curr, mv, nullptr, McKind::Extrapolate, outs, aheads, count, match_sad, "lfg_extrapolate_compensated_multi");
+}
+
+LFG_EXPORT int lfg_set_generation(lfg_context *ctx, int generation) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (generation != LFG_GENERATION_INTERPOLATE && generation != LFG_GENERATION_EXTRAPOLATE)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_generation: unknown generation");
+    ctx->generation = generation;
+    return LFG_OK;
 }
 
 // ---- static-overlay protection (static_mask.hip, interpolate_mc.hip)
@@ -1380,13 +1416,13 @@ LFG_EXPORT int lfg_static_mask(lfg_context *ctx, const lfg_frame *prev, const lf
 LFG_EXPORT int lfg_interpolate_compensated_masked(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                                   const lfg_mask *mask, lfg_frame *out, float factor, int match_sad) {
     lfg_frame *const outs[1] = {out};
-    return compensated_run(ctx, prev, curr, mv, mask, true, outs, &factor, 1, match_sad, "lfg_interpolate_compensated_masked");
+    return compensated_run(ctx, prev, curr, mv, mask, McKind::Masked, outs, &factor, 1, match_sad, "lfg_interpolate_compensated_masked");
 }
 
 LFG_EXPORT int lfg_interpolate_compensated_masked_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                                         const lfg_mask *mask, lfg_frame *const *outs, const float *factors, uint32_t count,
                                                         int match_sad) {
-    return compensated_run(ctx, prev, curr, mv, mask, true, outs, factors, count, match_sad, "lfg_interpolate_compensated_masked_multi");
+    return compensated_run(ctx, prev, curr, mv, mask, McKind::Masked, outs, factors, count, match_sad, "lfg_interpolate_compensated_masked_multi");
 }
 
 LFG_EXPORT int lfg_set_static_protection(lfg_context *ctx, int tolerance) {

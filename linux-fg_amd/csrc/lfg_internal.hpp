@@ -211,6 +211,7 @@ struct lfg_context {
     int refine_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_refine's radius, -1 = off (lfg_set_vector_refinement)
     int cut_permille = -1;                     // lfg_interpolate_frames[_multi]: lfg_cut_fallback's threshold, -1 = off (lfg_set_cut_detection)
     int static_tolerance = -1;                 // lfg_interpolate_frames[_multi]: lfg_static_mask's tolerance, -1 = off (lfg_set_static_protection)
+    int generation = 0;                        // lfg_interpolate_frames[_multi]: LFG_GENERATION_INTERPOLATE / _EXTRAPOLATE (lfg_set_generation)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -317,6 +318,9 @@ hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, 
 hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                                  const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
 hipError_t launch_static_mask(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, int tolerance, const lfg_mask &out);
+// Motion-compensated extrapolation (extrapolate_mc.hip): clears `keys` (W * H words), projects past time 1, samples curr; one factor.
+hipError_t launch_extrapolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                          const lfg_frame &out, float ahead, int matchSad, uint32_t *keys);
 // Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
                                 const lfg_frame &mvOut, int radius);

@@ -42,7 +42,7 @@ struct Resources {
 }  // namespace
 
 bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeight, uint32_t outputWidth, uint32_t outputHeight,
-                   int frames, EvaluationResult& result) {
+                   int frames, EvaluationResult& result, bool extrapolate) {
     auto& fm = FrameManager::Get();
     if (!Ctx() || frames < 3) {
         LOG_ERROR("RunEvaluation: needs an initialized HipContext and at least 3 frames");
@@ -86,9 +86,15 @@ bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeigh
         if (!next(*held) || !next(*curr)) return false;
         const lfg_frame p = prev->AsAbi(), h = held->AsAbi(), c = curr->AsAbi();
         lfg_frame o = r.out.AsAbi();
-        if (lfg_interpolate_frames(Ctx(), &p, &c, &o, 0.5f) != LFG_OK ||
-            lfg_frame_diff(Ctx(), &o, &h, kMask, k > 0 ? 1 : 0, generated) != LFG_OK ||
-            lfg_frame_diff(Ctx(), &p, &h, kMask, k > 0 ? 1 : 0, repeated) != LFG_OK) {
+        // interpolate: frames 2k and 2k + 2 give 2k + 1.  extrapolate: frames 2k and 2k + 1 give 2k + 2, one interval ahead of
+        // the newest frame, and the yardstick is that newest frame shown again
+        const bool enqueued = extrapolate ? lfg_interpolate_frames(Ctx(), &p, &h, &o, 1.0f) == LFG_OK &&
+                                                lfg_frame_diff(Ctx(), &o, &c, kMask, k > 0 ? 1 : 0, generated) == LFG_OK &&
+                                                lfg_frame_diff(Ctx(), &h, &c, kMask, k > 0 ? 1 : 0, repeated) == LFG_OK
+                                          : lfg_interpolate_frames(Ctx(), &p, &c, &o, 0.5f) == LFG_OK &&
+                                                lfg_frame_diff(Ctx(), &o, &h, kMask, k > 0 ? 1 : 0, generated) == LFG_OK &&
+                                                lfg_frame_diff(Ctx(), &p, &h, kMask, k > 0 ? 1 : 0, repeated) == LFG_OK;
+        if (!enqueued) {
             LOG_ERROR("Failed to enqueue pair ", k, ": ", lfg_last_error(Ctx()));
             return false;
         }

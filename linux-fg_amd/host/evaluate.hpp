@@ -19,5 +19,8 @@ struct EvaluationResult {
 
 // `frames` >= 3 source frames of inputWidth x inputHeight from `source` (a trailing unpaired frame is not read), compared at
 // outputWidth x outputHeight.  HipContext must be initialized and carry the settings to evaluate.
+// With `extrapolate` (the context then carries LFG_GENERATION_EXTRAPOLATE) pair k's frames 2k and 2k + 1 give the frame one interval
+// ahead, which "generated" compares with frame 2k + 2; "repeated" compares frame 2k + 1, the newest frame shown again, with it.
+// The same frames are read and the report has the same keys.
 bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeight, uint32_t outputWidth, uint32_t outputHeight,
-                   int frames, EvaluationResult& result);
+                   int frames, EvaluationResult& result, bool extrapolate = false);

@@ -21,6 +21,14 @@ bool FrameManager::Initialize(uint32_t /*width*/, uint32_t /*height*/) {
 
 void FrameManager::Cleanup() { m_initialized = false; }
 
+bool FrameManager::SetGeneration(int generation) {
+    if (lfg_set_generation(Ctx(), generation) != LFG_OK) {
+        LOG_ERROR("Failed to set the generation: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
+        return false;
+    }
+    return true;
+}
+
 bool FrameManager::CreateFrame(Frame& frame, uint32_t width, uint32_t height) {
     lfg_frame f{};
     const uint32_t format = frame.format;                    // RGBA8 unless the caller asked otherwise

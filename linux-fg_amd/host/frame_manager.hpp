@@ -66,6 +66,11 @@ public:
     bool InterpolateFramesMultiAsync(const Frame& previous, const Frame& current, const std::vector<Frame*>& outputs,
                                      const std::vector<float>& factors);
 
+    // What the four calls above generate (lfg_set_generation): LFG_GENERATION_INTERPOLATE (default), frames between previous and
+    // current, or LFG_GENERATION_EXTRAPOLATE, frames AHEAD of current by `factor` of an interval (with the compensated
+    // interpolator selected on the device context; the reference has no such mode).
+    bool SetGeneration(int generation);
+
     // The one exchange of the multi-GPU path: broadcast a frame from rank `root` to every rank (asynchronous, on the
     // device context's communication stream) and make later work on the compute queue wait for it.
     bool BroadcastFrame(Frame& frame, int root);

@@ -38,6 +38,10 @@ static void PrintUsage() {
               << "                           written; intended: vectors displace by pixels -- what vectors longer than 1 px need)\n"
               << "  --interpolator shader|compensated  Interpolation of the generated frames (default shader: the reference's;\n"
               << "                           compensated: vectors projected to the frame's time, holes filled; wants --semantics intended)\n"
+              << "  --generation interpolate|extrapolate  Where the generated frames lie (default interpolate: between the last two real\n"
+              << "                           frames, the newest one held back until they are shown; extrapolate: AHEAD of the newest real\n"
+              << "                           frame, which is presented as it arrives, each factor read as the fraction of an interval\n"
+              << "                           ahead).  extrapolate needs --interpolator compensated and is not available with --ranks\n"
               << "  --refine-vectors R       Per-pixel vector refinement between motion and interpolation (default -1: off;\n"
               << "                           0..2: each pixel takes the nearby vector that fits its (2R+1)^2 window best)\n"
               << "  --cut-threshold P        Scene-cut detection (default -1: off; 0..1000: a pair of which fewer than P pixels per\n"
@@ -53,6 +57,8 @@ static void PrintUsage() {
               << "                           held out; each pair's frame at 0.5 is generated under the options above and compared on the\n"
               << "                           GPU, at the output size, with the frame held out -- as is the pair's first frame, shown\n"
               << "                           again.  The report gains \"evaluation\" (PSNR, error quantiles, differing pixels of both).\n"
+              << "                           With --generation extrapolate frames 2k and 2k + 1 predict frame 2k + 2, one interval ahead,\n"
+              << "                           and the yardstick is frame 2k + 1 shown again; the same frames are read, the same keys reported.\n"
               << "                           Needs --frames >= 3; not with --ranks, --factors, --no-interpolation, --output-raw,\n"
               << "                           --dump-dir or --replay\n"
               << "  --frames N               Number of input frames to process (default: 10)\n"
@@ -88,7 +94,8 @@ int main(int argc, char* argv[]) {
     int frames = 10, device = 0;
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
-    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1, staticTolerance = -1;
+    int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1, staticTolerance = -1,
+        generation = LFG_GENERATION_INTERPOLATE;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false, evaluate = false, inputNv12 = false, outputNv12 = false;
@@ -135,6 +142,12 @@ int main(int argc, char* argv[]) {
             if (strcmp(m, "shader") == 0) interpolator = LFG_INTERPOLATOR_SHADER;
             else if (strcmp(m, "compensated") == 0) interpolator = LFG_INTERPOLATOR_COMPENSATED;
             else { LOG_ERROR("Invalid --interpolator (shader|compensated)"); return 1; }
+        }
+        else if (strcmp(argv[i], "--generation") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (strcmp(m, "interpolate") == 0) generation = LFG_GENERATION_INTERPOLATE;
+            else if (strcmp(m, "extrapolate") == 0) generation = LFG_GENERATION_EXTRAPOLATE;
+            else { LOG_ERROR("Invalid --generation (interpolate|extrapolate)"); return 1; }
         }
         else if (strcmp(argv[i], "--refine-vectors") == 0 && i + 1 < argc) {
             char* end = nullptr;
@@ -226,6 +239,10 @@ int main(int argc, char* argv[]) {
             return 2;
         }
     }
+    if (generation == LFG_GENERATION_EXTRAPOLATE) {            // before a context is made
+        if (interpolator != LFG_INTERPOLATOR_COMPENSATED) { LOG_ERROR("--generation extrapolate needs --interpolator compensated"); return 2; }
+        if (ranks > 0) { LOG_ERROR("--generation extrapolate cannot be combined with --ranks"); return 2; }
+    }
     if (evaluate) {                                             // before a context is made
         const char* clash = ranks > 0 ? "--ranks" : !factors.empty() ? "--factors" : !config.enableInterpolation ? "--no-interpolation"
                           : !outputRaw.empty() ? "--output-raw" : !dumpDir.empty() ? "--dump-dir" : replay > 0 ? "--replay" : nullptr;
@@ -245,7 +262,7 @@ int main(int argc, char* argv[]) {
         HipContext::Get().Cleanup();
         return 1;
     }
-    if (!FrameManager::Get().Initialize(config.outputWidth, config.outputHeight)) {
+    if (!FrameManager::Get().Initialize(config.outputWidth, config.outputHeight) || !FrameManager::Get().SetGeneration(generation)) {
         LOG_ERROR("Failed to initialize frame manager");
         HipContext::Get().Cleanup();
         return 1;
@@ -255,7 +272,8 @@ int main(int argc, char* argv[]) {
         if (!inputRaw.empty()) source = std::make_unique<RawFileCapture>(inputRaw);
         else source = std::make_unique<SyntheticCapture>(stream);
         EvaluationResult result;
-        const bool ok = RunEvaluation(*source, config.inputWidth, config.inputHeight, config.outputWidth, config.outputHeight, frames, result);
+        const bool ok = RunEvaluation(*source, config.inputWidth, config.inputHeight, config.outputWidth, config.outputHeight, frames, result,
+                                      generation == LFG_GENERATION_EXTRAPOLATE);
         source.reset();
         FrameManager::Get().Cleanup();
         HipContext::Get().Cleanup();
@@ -283,6 +301,7 @@ int main(int argc, char* argv[]) {
     Scaler::Get().SetPipelined(!syncPresent);
     Scaler::Get().SetFramesInFlight(inFlight);
     Scaler::Get().SetCutCounting(cutThreshold >= 0);
+    Scaler::Get().SetRealFrameFirst(generation == LFG_GENERATION_EXTRAPOLATE);
     Scaler::Get().SetNv12(inputNv12, outputNv12, yuv);
     if (!factors.empty()) Scaler::Get().SetInterpolationFactors(factors);
     FILE* rawOut = nullptr;

@@ -357,6 +357,8 @@ bool Scaler::ProcessFrame() {
         return false;
     }
     const size_t inFlightBefore = m_pending.size();
+    // Extrapolation: the real frame is not held behind the frames generated from it -- they lie ahead of it.
+    if (m_realFirst && !QueueReadback(m_outputFrame, false)) return false;
     if (m_config.enableInterpolation && m_havePrevious) {
         for (Frame& f : m_interpolatedFrames) fenceBeforeWrite(f);
         auto& fm = FrameManager::Get();
@@ -380,7 +382,8 @@ bool Scaler::ProcessFrame() {
             LOG_ERROR("Failed to interpolate frame");
             return false;
         }
-        // Presentation order: previous real frame (presented by the last call), generated frames t1 .. tN, this real frame.
+        // Presentation order: previous real frame (presented by the last call), generated frames t1 .. tN, this real frame;
+        // extrapolating: this real frame (queued above), then generated frames k + a1 .. k + aN.
         const size_t first = m_pending.size();
         for (Frame& f : m_interpolatedFrames)
             if (!QueueReadback(f, true)) return false;
@@ -389,7 +392,7 @@ bool Scaler::ProcessFrame() {
             m_pending[first].statsCall = m_unreadStats[(size_t)lane] = m_calls;      // (already incremented: 1-based)
         }
     }
-    if (!QueueReadback(m_outputFrame, false)) return false;
+    if (!m_realFirst && !QueueReadback(m_outputFrame, false)) return false;
     // Pipelined: present what earlier calls queued while this call's work runs (one call back; with n > 2 lanes the
     // last n - 1 calls stay in flight); otherwise everything now.
     m_queuedPerCall.push_back(m_pending.size() - inFlightBefore);

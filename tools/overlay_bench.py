@@ -33,9 +33,9 @@ FACTORS = [0.25, 0.5, 0.75]
 KERNELS = "mc_project_kernel|mc_interpolate_kernel|mc_project_masked_kernel|mc_interpolate_masked_kernel|static_mask_kernelILb[01]E"
 
 
-def kernel_resources():
-    """{kernel: "vgprs ..., sgprs ..., lds ..., scratch ..., waves/SIMD ..."} of the unmasked and the masked kernels and of the mask
-    kernel's two instances, from the notes of the library's code objects."""
+def kernel_resources(kernels=KERNELS):
+    """{kernel: "vgprs ..., sgprs ..., lds ..., scratch ..., waves/SIMD ..."} of the kernels named by the pattern `kernels` (default:
+    the unmasked and the masked kernels and the mask kernel's two instances), from the notes of the library's code objects."""
     llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
     found = {}
     with tempfile.TemporaryDirectory() as d:
@@ -44,7 +44,7 @@ def kernel_resources():
         for f in sorted(glob.glob(os.path.join(d, "*gfx950*"))):
             notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", f], capture_output=True, text=True).stdout
             for block in notes.split("  - .agpr_count:")[1:]:
-                name = re.search(rf"\.name:\s+\S*?\d\d({KERNELS})E", block)
+                name = re.search(rf"\.name:\s+\S*?\d\d({kernels})E", block)
                 if not name:
                     continue
                 get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", block)[1])  # noqa: E731
