@@ -1,7 +1,8 @@
 // extrapolate_mc.hip -- motion-compensated extrapolation (lfg_extrapolate_compensated, include/linuxfg_hip.h): curr's content is
 // projected past time 1 along the vectors just measured, and curr alone is fetched along the projected vectors.  No reference
-// counterpart; opt-in, next to interpolate_mc.hip, whose kernels stay as they are.  tests/extrapolate_model.c restates every
-// step below on the CPU.
+// counterpart; opt-in, next to interpolate_mc.hip, with which it shares the hole word, the reads, the match gate and the
+// launcher's start (lfg_mc.hpp) and the key with its decode (lfg_vector_word.hpp); the batched hole walk is its own.
+// tests/extrapolate_model.c restates every step below on the CPU.
 //
 // Two launches per factor, after the key image K (W * H words, the lane's scratch, interpolate_mc.hip's) has been set to 0xFF
 // bytes in stream order:
@@ -11,68 +12,38 @@
 //
 // Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 4
 // (one fetch, mostly cached neighbours) + 4 (out) in the sampling: 30 bytes, 249 MB at 4K.
-#include "lfg_device.hpp"
-#include "lfg_internal.hpp"
+#include "lfg_mc.hpp"
 #include "lfg_interp.hpp"
 
 namespace lfg {
 
 namespace {
 
-constexpr uint32_t kExHole = 0xFFFFFFFFu;
 constexpr int kExWalk = 16;                    // the hole walk's reach, per axis direction
 constexpr int kExBatch = 4;                    // words of each direction loaded ahead of their comparison
-constexpr int kExBlockX = 64, kExBlockY = 4;   // a wave is 64 pixels of one row
 
-// interpolate_mc.hip's helpers, restated: that file's kernels keep their machine code.
-__device__ __forceinline__ uint32_t ex_texel(const uint8_t *__restrict__ img, size_t pitch, int x, int y) {
-    return *reinterpret_cast<const uint32_t *>(img + (size_t)y * pitch + (size_t)x * 4u);
-}
-
-struct ExMv { int x, y; };
-
-__device__ __forceinline__ ExMv ex_mv_at(const uint8_t *__restrict__ mv, size_t pitch, int x, int y) {
-    const uint16_t w = *reinterpret_cast<const uint16_t *>(mv + (size_t)y * pitch + (size_t)x * 2u);
-    return ExMv{(int)(int8_t)(w & 0xffu), (int)(int8_t)(w >> 8)};
-}
-
-// The match gate: sum over the channels of |curr(q) - prev(q + v)| <= matchSad, prev outside the image read as 0.
-__device__ __forceinline__ bool ex_matched(const uint8_t *__restrict__ prev, size_t prevPitch, uint32_t currTexel,
-                                           int W, int H, int qx, int qy, ExMv v, int matchSad) {
-    const int sx = qx + v.x, sy = qy + v.y;
-    const uint32_t p = (sx >= 0 && sx < W && sy >= 0 && sy < H) ? ex_texel(prev, prevPitch, sx, sy) : 0u;
-    return __builtin_amdgcn_sad_u8(currTexel, p, 0u) <= (uint32_t)matchSad;
-}
-
-// Longest vector first, then the smallest vy, then the smallest vx: the smallest key wins.
-__device__ __forceinline__ uint32_t ex_key(ExMv v) {
-    return ((uint32_t)(65535 - (v.x * v.x + v.y * v.y)) << 16) | ((uint32_t)(v.y + 128) << 8) | (uint32_t)(v.x + 128);
-}
-
-__device__ __forceinline__ ExMv ex_decode(uint32_t key) { return ExMv{(int)(key & 0xffu) - 128, (int)((key >> 8) & 0xffu) - 128}; }
-
-__global__ __launch_bounds__(kExBlockX * kExBlockY) void ex_project_kernel(
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void ex_project_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, int W, int H, float a, int matchSad, uint32_t *__restrict__ keys) {
-    const int x = (int)(blockIdx.x * kExBlockX + threadIdx.x), y = (int)(blockIdx.y * kExBlockY + threadIdx.y);
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
     if (x >= W || y >= H) return;
-    const ExMv v = ex_mv_at(mv, mvPitch, x, y);
-    if (!ex_matched(prev, prevPitch, ex_texel(curr, currPitch, x, y), W, H, x, y, v, matchSad)) return;
+    const Mv v = mv_at(mv, mvPitch, x, y);
+    if (!matched(prev, prevPitch, texel_u32(curr, currPitch, x, y), W, H, x, y, v, matchSad)) return;
     // content at q came from q + v: it moves by -v per interval
     const int dx = x + (int)__builtin_floorf(0.5f - (float)v.x * a), dy = y + (int)__builtin_floorf(0.5f - (float)v.y * a);
     if (dx < 0 || dx >= W || dy < 0 || dy >= H) return;
-    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, ex_key(v));     // the result is unused: one global_atomic_umin
+    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, mv_longest_first_key(v.x, v.y));  // result unused: one global_atomic_umin
 }
 
-__global__ __launch_bounds__(kExBlockX * kExBlockY) void ex_sample_kernel(
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void ex_sample_kernel(
         const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, int W, int H, float a, int matchSad,
         uint8_t *__restrict__ out, size_t outPitch) {
-    const int x = (int)(blockIdx.x * kExBlockX + threadIdx.x), y = (int)(blockIdx.y * kExBlockY + threadIdx.y);
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
     if (x >= W || y >= H) return;
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
-    const bool hole = key == kExHole;
+    const bool hole = key == kMcHole;
     bool donor = false;
     int nx = x, ny = y;
     if (hole) {
@@ -81,7 +52,7 @@ __global__ __launch_bounds__(kExBlockX * kExBlockY) void ex_sample_kernel(
         // A step past the image edge reads as a hole (its address is clamped into the image): every later step of that
         // direction is past the edge too, so the direction keeps nothing, as when the walk stops there.
         const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
-        uint32_t first[4] = {kExHole, kExHole, kExHole, kExHole};
+        uint32_t first[4] = {kMcHole, kMcHole, kMcHole, kMcHole};
         int firstK[4] = {0, 0, 0, 0};
         for (int base = 1; base <= kExWalk; base += kExBatch) {
             uint32_t n[4][kExBatch];
@@ -99,25 +70,25 @@ __global__ __launch_bounds__(kExBlockX * kExBlockY) void ex_sample_kernel(
                 for (int j = 0; j < kExBatch; ++j) {
                     const int qx = x + stepX[d] * (base + j), qy = y + stepY[d] * (base + j);
                     const bool in = qx >= 0 && qx < W && qy >= 0 && qy < H;
-                    if (first[d] == kExHole && in && n[d][j] != kExHole) { first[d] = n[d][j]; firstK[d] = base + j; }
+                    if (first[d] == kMcHole && in && n[d][j] != kMcHole) { first[d] = n[d][j]; firstK[d] = base + j; }
                 }
-                all = all && first[d] != kExHole;
+                all = all && first[d] != kMcHole;
             }
             if (all) break;
         }
-        // The fill vector: the smallest (|v|^2, vy, vx) of the kept words, i.e. the smallest of (65535 - key_hi) << 16 | key_lo;
-        // on an equal triple the earlier direction stays.  (0, 0) and no donor when every direction ran out.
-        uint32_t best = kExHole;
+        // The fill vector: the smallest (|v|^2, vy, vx) of the kept words; on an equal triple the earlier direction stays.
+        // (0, 0) and no donor when every direction ran out.
+        uint32_t best = kMcHole;
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
-            if (first[d] == kExHole) continue;
-            const uint32_t order = ((65535u - (first[d] >> 16)) << 16) | (first[d] & 0xffffu);
+            if (first[d] == kMcHole) continue;
+            const uint32_t order = mv_key_flip_length(first[d]);
             if (order < best) { best = order; nx = x + stepX[d] * firstK[d]; ny = y + stepY[d] * firstK[d]; }
         }
-        donor = best != kExHole;
-        key = donor ? best : (128u << 8) | 128u;                  // only the low 16 bits are decoded
+        donor = best != kMcHole;
+        key = donor ? best : mv_order_key(0, 0);               // only the low 16 bits are decoded
     }
-    const ExMv u = ex_decode(key);
+    const Mv u = mv_order_decode(key);
     const float Cx = px + (float)u.x * a, Cy = py + (float)u.y * a;
     SampleTaps sc = pixel_taps(curr, W, H, currPitch, Cx, Cy);
     SampleTexels tc = sample_load(sc);
@@ -127,11 +98,11 @@ __global__ __launch_bounds__(kExBlockX * kExBlockY) void ex_sample_kernel(
         const int cx = clampi((int)__builtin_floorf(Cx), 0, W - 1), cy = clampi((int)__builtin_floorf(Cy), 0, H - 1);
         const float Nx = ((float)nx + 0.5f) + (float)u.x * a, Ny = ((float)ny + 0.5f) + (float)u.y * a;
         const SampleTaps sn = pixel_taps(curr, W, H, currPitch, Nx, Ny);
-        const ExMv vc = ex_mv_at(mv, mvPitch, cx, cy);
-        const uint32_t cTexel = ex_texel(curr, (size_t)currPitch, cx, cy);
+        const Mv vc = mv_at(mv, mvPitch, cx, cy);
+        const uint32_t cTexel = texel_u32(curr, (size_t)currPitch, cx, cy);
         const SampleTexels tn = sample_load(sn);
         // curr shows the foreground at c, and the surface behind it is in neither frame: the background's edge is stretched
-        if (ex_matched(prev, (size_t)prevPitch, cTexel, W, H, cx, cy, vc, matchSad) && (vc.x != u.x || vc.y != u.y)) {
+        if (matched(prev, (size_t)prevPitch, cTexel, W, H, cx, cy, vc, matchSad) && (vc.x != u.x || vc.y != u.y)) {
             sc = sn;
             tc = tn;
         }
@@ -145,15 +116,15 @@ __global__ __launch_bounds__(kExBlockX * kExBlockY) void ex_sample_kernel(
 hipError_t launch_extrapolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                           const lfg_frame &out, float ahead, int matchSad, uint32_t *keys) {
     const int W = (int)curr.width, H = (int)curr.height;
-    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 4u, s);
+    dim3 grid;
+    hipError_t e = mc_clear_keys(s, keys, W, H, grid);
     if (e != hipSuccess) return e;
-    const dim3 block(kExBlockX, kExBlockY), grid((unsigned)((W + kExBlockX - 1) / kExBlockX), (unsigned)((H + kExBlockY - 1) / kExBlockY));
-    hipLaunchKernelGGL(ex_project_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
+    hipLaunchKernelGGL(ex_project_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
                        (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, ahead,
                        matchSad, keys);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ex_sample_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
+    hipLaunchKernelGGL(ex_sample_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
                        (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
                        (const uint32_t *)keys, W, H, ahead, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
     return hipGetLastError();

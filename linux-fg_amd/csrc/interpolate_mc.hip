@@ -7,61 +7,54 @@
 //   mc_interpolate_kernel  one thread per output pixel: K, the hole walk where K is a hole, both bilinear fetches, the blend.
 // The second launch starts once every projection is visible, and it never writes K: a hole's walk reads words of its
 // neighbours that other workgroups also read.  lfg_interpolate_compensated_masked runs the same two launches through
-// mc_project_masked_kernel and mc_interpolate_masked_kernel (below; tests/overlay_model.c).
+// mc_project_masked_kernel and mc_interpolate_masked_kernel (tests/overlay_model.c).  The project pair is one body,
+// mc_project<Masked>, under two wrappers that keep the kernels' names and argument lists; the interpolate pair is two kernels
+// (see there).  The hole word, the reads, the match gate and the launchers' start are lfg_mc.hpp's, shared with
+// extrapolate_mc.hip; the key, its decode and the hole walk's order are lfg_vector_word.hpp's.
 //
 // Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 8
 // (two fetches, mostly cached neighbours) + 4 (out) in the interpolation: 34 bytes, 280 MB at 4K.
-#include "lfg_device.hpp"
-#include "lfg_internal.hpp"
+#include "lfg_mc.hpp"
 #include "lfg_interp.hpp"
 
 namespace lfg {
 
 namespace {
 
-constexpr uint32_t kMcHole = 0xFFFFFFFFu;
 constexpr int kMcWalk = 16;                    // the hole walk's reach, per axis direction
-constexpr int kMcBlockX = 64, kMcBlockY = 4;   // a wave is 64 pixels of one row
+// Key 0 marks a static location (the masked pair only): no vector's key is 0 (65535 - |v|^2 >= 32767), and it is the smallest
+// word, so it outlasts whatever is projected onto it.
+constexpr uint32_t kMcStatic = 0u;
 
-__device__ __forceinline__ uint32_t texel_u32(const uint8_t *__restrict__ img, size_t pitch, int x, int y) {
-    return *reinterpret_cast<const uint32_t *>(img + (size_t)y * pitch + (size_t)x * 4u);
+// Both project kernels.  Masked: one more byte of traffic per pixel, and a static pixel projects its own vector as any other.
+template <bool Masked>
+__device__ __forceinline__ void mc_project(
+        const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch, int W, int H, float t,
+        int matchSad, uint32_t *__restrict__ keys) {
+    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
+    if (x >= W || y >= H) return;
+    uint8_t isStatic = 0;
+    if constexpr (Masked) isStatic = mask[(size_t)y * maskPitch + (size_t)x];
+    const Mv v = mv_at(mv, mvPitch, x, y);
+    const uint32_t c = texel_u32(curr, currPitch, x, y);
+    if (isStatic != 0) atomicMin(keys + (size_t)y * (size_t)W + (size_t)x, kMcStatic);
+    if (!matched(prev, prevPitch, c, W, H, x, y, v, matchSad)) return;
+    const float s = 1.0f - t;
+    const int dx = x + (int)__builtin_floorf((float)v.x * s + 0.5f), dy = y + (int)__builtin_floorf((float)v.y * s + 0.5f);
+    if (dx < 0 || dx >= W || dy < 0 || dy >= H) return;
+    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, mv_longest_first_key(v.x, v.y));  // result unused: one global_atomic_umin
 }
-
-struct Mv { int x, y; };
-
-__device__ __forceinline__ Mv mv_at(const uint8_t *__restrict__ mv, size_t pitch, int x, int y) {
-    const uint16_t w = *reinterpret_cast<const uint16_t *>(mv + (size_t)y * pitch + (size_t)x * 2u);
-    return Mv{(int)(int8_t)(w & 0xffu), (int)(int8_t)(w >> 8)};
-}
-
-// The match gate: sum over the channels of |curr(q) - prev(q + v)| <= matchSad, prev outside the image read as 0.
-__device__ __forceinline__ bool matched(const uint8_t *__restrict__ prev, size_t prevPitch, uint32_t currTexel,
-                                        int W, int H, int qx, int qy, Mv v, int matchSad) {
-    const int sx = qx + v.x, sy = qy + v.y;
-    const uint32_t p = (sx >= 0 && sx < W && sy >= 0 && sy < H) ? texel_u32(prev, prevPitch, sx, sy) : 0u;
-    return __builtin_amdgcn_sad_u8(currTexel, p, 0u) <= (uint32_t)matchSad;
-}
-
-// Longest vector first, then the smallest vy, then the smallest vx: the smallest key wins.
-__device__ __forceinline__ uint32_t mc_key(Mv v) {
-    return ((uint32_t)(65535 - (v.x * v.x + v.y * v.y)) << 16) | ((uint32_t)(v.y + 128) << 8) | (uint32_t)(v.x + 128);
-}
-
-__device__ __forceinline__ Mv mc_decode(uint32_t key) { return Mv{(int)(key & 0xffu) - 128, (int)((key >> 8) & 0xffu) - 128}; }
 
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, int W, int H, float t, int matchSad, uint32_t *__restrict__ keys) {
-    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
-    if (x >= W || y >= H) return;
-    const Mv v = mv_at(mv, mvPitch, x, y);
-    if (!matched(prev, prevPitch, texel_u32(curr, currPitch, x, y), W, H, x, y, v, matchSad)) return;
-    const float s = 1.0f - t;
-    const int dx = x + (int)__builtin_floorf((float)v.x * s + 0.5f), dy = y + (int)__builtin_floorf((float)v.y * s + 0.5f);
-    if (dx < 0 || dx >= W || dy < 0 || dy >= H) return;
-    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, mc_key(v));     // the result is unused: one global_atomic_umin
+    mc_project<false>(prev, prevPitch, curr, currPitch, mv, mvPitch, nullptr, 0, W, H, t, matchSad, keys);
 }
 
+// The two interpolate kernels are not one body: as wrappers around a shared one they differed from these by two swapped
+// v_mad_u64_u32 factors (the unmasked one also by a few reordered instructions), and a changed kernel has to stay inside the
+// former code's run-to-run spread on every row of the stage tools, which neither did.
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
         const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad,
@@ -72,8 +65,8 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
     uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
     const bool hole = key == kMcHole;
     if (hole) {
-        // The fill vector: of the first non-hole word in each axis direction within kMcWalk, the smallest (|v|^2, vy, vx),
-        // i.e. the smallest of (65535 - key_hi) << 16 | key_lo; (0, 0) when every direction runs out.
+        // The fill vector: of the first non-hole word in each axis direction within kMcWalk, the smallest (|v|^2, vy, vx);
+        // (0, 0) when every direction runs out.
         uint32_t best = kMcHole;
         const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
 #pragma unroll
@@ -83,14 +76,14 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
                 if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
                 const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
                 if (n == kMcHole) continue;
-                const uint32_t order = ((65535u - (n >> 16)) << 16) | (n & 0xffffu);
+                const uint32_t order = mv_key_flip_length(n);
                 best = order < best ? order : best;
                 break;
             }
         }
-        key = best == kMcHole ? (128u << 8) | 128u : best;        // only the low 16 bits are decoded
+        key = best == kMcHole ? mv_order_key(0, 0) : best;     // only the low 16 bits are decoded
     }
-    const Mv u = mc_decode(key);
+    const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
     const float Cx = px - (float)u.x * s, Cy = py - (float)u.y * s;
@@ -111,28 +104,11 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
     *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
 }
 
-// ---- the same two launches with a static mask (lfg_interpolate_compensated_masked; tests/overlay_model.c restates them).
-// Kernels of their own: the two above stay as they are, instruction for instruction.  Key 0 marks a static location: no
-// vector's key is 0 (65535 - |v|^2 >= 32767), and it is the smallest word, so it outlasts whatever is projected onto it.
-// Extra traffic per pixel and factor: 1 byte of mask in the projection, up to 2 gathered bytes in the interpolation.
-
-constexpr uint32_t kMcStatic = 0u;
-
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_masked_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch, int W, int H, float t,
         int matchSad, uint32_t *__restrict__ keys) {
-    const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
-    if (x >= W || y >= H) return;
-    const uint8_t isStatic = mask[(size_t)y * maskPitch + (size_t)x];
-    const Mv v = mv_at(mv, mvPitch, x, y);
-    const uint32_t c = texel_u32(curr, currPitch, x, y);
-    if (isStatic != 0) atomicMin(keys + (size_t)y * (size_t)W + (size_t)x, kMcStatic);
-    if (!matched(prev, prevPitch, c, W, H, x, y, v, matchSad)) return;     // a static pixel projects its own vector as any other
-    const float s = 1.0f - t;
-    const int dx = x + (int)__builtin_floorf((float)v.x * s + 0.5f), dy = y + (int)__builtin_floorf((float)v.y * s + 0.5f);
-    if (dx < 0 || dx >= W || dy < 0 || dy >= H) return;
-    atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, mc_key(v));
+    mc_project<true>(prev, prevPitch, curr, currPitch, mv, mvPitch, mask, maskPitch, W, H, t, matchSad, keys);
 }
 
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_kernel(
@@ -161,14 +137,14 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_k
                 if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
                 const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
                 if (n == kMcHole || n == kMcStatic) continue;
-                const uint32_t order = ((65535u - (n >> 16)) << 16) | (n & 0xffffu);
+                const uint32_t order = mv_key_flip_length(n);
                 best = order < best ? order : best;
                 break;
             }
         }
-        key = best == kMcHole ? (128u << 8) | 128u : best;
+        key = best == kMcHole ? mv_order_key(0, 0) : best;
     }
-    const Mv u = mc_decode(key);
+    const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
     const float Cx = px - (float)u.x * s, Cy = py - (float)u.y * s;
@@ -194,18 +170,19 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_k
 
 }  // namespace
 
+// Each launcher: clear K, project, interpolate.
 hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                                  const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {
     const int W = (int)curr.width, H = (int)curr.height;
-    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 4u, s);
+    dim3 grid;
+    hipError_t e = mc_clear_keys(s, keys, W, H, grid);
     if (e != hipSuccess) return e;
-    const dim3 block(kMcBlockX, kMcBlockY), grid((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
-    hipLaunchKernelGGL(mc_project_masked_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
+    hipLaunchKernelGGL(mc_project_masked_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
                        (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
                        (const uint8_t *)mask.data, (size_t)mask.pitch, W, H, factor, matchSad, keys);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_interpolate_masked_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
+    hipLaunchKernelGGL(mc_interpolate_masked_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
                        (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
                        (const uint8_t *)mask.data, (size_t)mask.pitch, (const uint32_t *)keys, W, H, factor, matchSad,
                        (uint8_t *)out.data, (size_t)out.pitch);
@@ -215,15 +192,15 @@ hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame 
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                           const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {
     const int W = (int)curr.width, H = (int)curr.height;
-    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 4u, s);
+    dim3 grid;
+    hipError_t e = mc_clear_keys(s, keys, W, H, grid);
     if (e != hipSuccess) return e;
-    const dim3 block(kMcBlockX, kMcBlockY), grid((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
-    hipLaunchKernelGGL(mc_project_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
+    hipLaunchKernelGGL(mc_project_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
                        (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, factor,
                        matchSad, keys);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_interpolate_kernel, grid, block, 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
+    hipLaunchKernelGGL(mc_interpolate_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
                        (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
                        (const uint32_t *)keys, W, H, factor, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
     return hipGetLastError();

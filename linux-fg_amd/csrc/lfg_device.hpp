@@ -134,10 +134,20 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// A packed RGBA8 texel as one dword, what the opt-in stages compare with v_sad_u8: img(x, y), 0 outside the image.  Branching:
-// no load for a position outside.
+// A packed RGBA8 texel as one dword, what the opt-in stages compare with v_sad_u8: img(x, y), 0 outside the image, two ways.
+// texel_or_zero_branch: no load for a position outside.  Right where the loads are staged anyway (the pyramid's windows
+// into LDS) and many positions lie outside.
+// texel_or_zero: no branch around the load.  It comes unconditionally from the clamped position and the outside value is
+// selected after it, so every load of a window or a trip is in flight before the first wait (motion_refine.hip,
+// pair_stats.hip).
 __device__ __forceinline__ uint32_t texel_or_zero_branch(const uint8_t *__restrict__ img, size_t pitch, int x, int y, int W, int H) {
     return (x < 0 || y < 0 || x >= W || y >= H) ? 0u : *reinterpret_cast<const uint32_t *>(img + (size_t)y * pitch + (size_t)x * 4u);
+}
+
+__device__ __forceinline__ uint32_t texel_or_zero(const uint8_t *__restrict__ img, size_t pitch, int x, int y, int W, int H) {
+    const bool in = x >= 0 && x < W && y >= 0 && y < H;
+    const uint32_t t = *reinterpret_cast<const uint32_t *>(img + (size_t)min(max(y, 0), H - 1) * pitch + (size_t)min(max(x, 0), W - 1) * 4u);
+    return in ? t : 0u;
 }
 
 // The largest of a wave's 64 unsigned values, as a wave-uniform (scalar) result.  Six DPP steps in the VALU -- within

@@ -1,8 +1,8 @@
 // The MV_S8X2 word of a motion vector and the total orders the opt-in stages put on vectors.  Host and device code
 // share this header; it needs nothing but the standard library, so that tests/cpp/vector_word_check.cpp can hold
-// every definition to the expression it replaces with g++ alone.  In use: mv_word at every store of a vector, and all of
-// the pyramid's.  interpolate_mc.hip, motion_refine.hip and pair_stats.hip still spell their own unpack and keys: moving them
-// here changes their machine code, which wants a measured comparison first.
+// every definition to the expression it replaces with g++ alone.  In use: mv_word at every store of a vector, and every
+// unpack, key and decode of the opt-in stages (the pyramid, the compensated family through lfg_mc.hpp, motion_refine.hip,
+// pair_stats.hip).  What the default path's kernels still spell themselves is listed in DESIGN.md section 4.10.
 #pragma once
 
 #include <cstdint>
@@ -23,7 +23,11 @@ constexpr uint32_t mv_order_key(int vx, int vy) {
 constexpr Mv mv_order_decode(uint32_t key) { return Mv{(int)(key & 0xffu) - 128, (int)((key >> 8) & 0xffu) - 128}; }
 // The same key with the length inverted, 65535 - |v|^2 in the high half, and back again: one function both ways.
 constexpr uint32_t mv_key_flip_length(uint32_t key) { return ((65535u - (key >> 16)) << 16) | (key & 0xffffu); }
-// The compensated interpolator's key: the longest vector first, then the smallest vy, then the smallest vx.
-constexpr uint32_t mv_longest_first_key(int vx, int vy) { return mv_key_flip_length(mv_order_key(vx, vy)); }
+// The compensated family's key: the longest vector first, then the smallest vy, then the smallest vx.  It equals
+// mv_key_flip_length(mv_order_key(vx, vy)) (tests/cpp/vector_word_check.cpp); spelled out because that composition costs each
+// project kernel one more instruction.
+constexpr uint32_t mv_longest_first_key(int vx, int vy) {
+    return ((uint32_t)(65535 - (vx * vx + vy * vy)) << 16) | ((uint32_t)(vy + 128) << 8) | (uint32_t)(vx + 128);
+}
 
 }  // namespace lfg

@@ -17,6 +17,7 @@
 // (2R + 1)^2 dwords of curr and up to 17 (2R + 1)^2 gathered dwords of prev, mostly L1/L2 hits.
 #include "lfg_internal.hpp"
 #include "lfg_device.hpp"
+#include "lfg_vector_word.hpp"
 
 namespace lfg {
 namespace {
@@ -29,14 +30,6 @@ constexpr int kRefCands = 17;
 // Candidate k's offset: k = 0 is (0, 0); k = 1 .. 16 run over s = 4, 8, then b, then a, skipping (a, b) = (0, 0).
 __device__ constexpr int kRefDx[kRefCands] = {0, -4, 0, 4, -4, 4, -4, 0, 4, -8, 0, 8, -8, 8, -8, 0, 8};
 __device__ constexpr int kRefDy[kRefCands] = {0, -4, -4, -4, 0, 0, 4, 4, 4, -8, -8, -8, 0, 0, 8, 8, 8};
-
-// img(x, y), 0 outside the image.  The load itself is unconditional, from a clamped position, and the outside value is
-// selected after it: no branch around a load, so every load of a window is in flight before the first wait.
-__device__ __forceinline__ uint32_t texel_or_zero(const uint8_t *__restrict__ img, size_t pitch, int x, int y, int W, int H) {
-    const bool in = x >= 0 && x < W && y >= 0 && y < H;
-    const uint32_t t = *reinterpret_cast<const uint32_t *>(img + (size_t)min(max(y, 0), H - 1) * pitch + (size_t)min(max(x, 0), W - 1) * 4u);
-    return in ? t : 0u;
-}
 
 template <int R>
 __global__ __launch_bounds__(kRefBlockX * kRefBlockY) void motion_refine_kernel(
@@ -102,22 +95,21 @@ __global__ __launch_bounds__(kRefBlockX * kRefBlockY) void motion_refine_kernel(
 #pragma unroll
         for (int m = 0; m < k; ++m) fresh = fresh && !(((present >> m) & 1u) && cand[m] == cand[k]);
         if (!fresh) continue;
-        const int vx = (int)(int8_t)(cand[k] & 0xffu), vy = (int)(int8_t)(cand[k] >> 8);
+        const Mv v = mv_unpack((uint16_t)cand[k]);
         uint32_t cost = 0u;
 #pragma unroll
         for (int j = 0; j < D; ++j)
 #pragma unroll
             for (int i = 0; i < D; ++i) {
-                const uint32_t p = texel_or_zero(prev, prevPitch, x + i - R + vx, y + j - R + vy, W, H);
+                const uint32_t p = texel_or_zero(prev, prevPitch, x + i - R + v.x, y + j - R + v.y, W, H);
                 const uint32_t sum = __builtin_amdgcn_sad_u8(cw[j * D + i], p, cost);
                 cost = (inWin >> (j * D + i)) & 1u ? sum : cost;
             }
-        const uint64_t key = ((uint64_t)cost << 32) | ((uint64_t)(vx * vx + vy * vy) << 16) |
-                             ((uint64_t)(vy + 128) << 8) | (uint64_t)(vx + 128);
+        const uint64_t key = ((uint64_t)cost << 32) | mv_order_key(v.x, v.y);
         best = key < best ? key : best;
     }
-    // (vx + 128, vy + 128) back to the two's-complement bytes of MV_S8X2
-    *dst = (uint16_t)(((uint32_t)best ^ 0x8080u) & 0xffffu);
+    const Mv v = mv_order_decode((uint32_t)best);
+    *dst = mv_word(v.x, v.y);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // pair_stats.hip -- scene-cut detection (lfg_pair_match, lfg_cut_fallback, include/linuxfg_hip.h).  No reference counterpart;
 // opt-in, around either interpolator.  tests/pair_model.py restates both definitions on the CPU.
 //
-// pair_match_kernel   how well the vectors explain the pair: the compensated interpolator's match gate (interpolate_mc.hip:
+// pair_match_kernel   how well the vectors explain the pair: the compensated interpolator's match gate (lfg_mc.hpp:
 //                     matched) evaluated at every pixel, counted, and the SADs summed.  One launch behind a clear of the record.
 // cut_fallback_kernel reads that record on the device; a pair that is no cut costs the launch and one load per wave, a cut
 //                     copies prev or curr over every output.  The host never learns the verdict here.
@@ -10,7 +10,7 @@
 // cost at the end is two 64-bit atomics into the same two words, and at 4K a grid of tiles would be 32,400 of them.  Each
 // workgroup walks the 64 x 4 tiles blockIdx.x, blockIdx.x + gridDim.x, ...; a wave is 64 pixels of one row.  Per tile every
 // lane loads its vector, then curr and the gathered prev texel -- unconditionally, from clamped positions, the outside value
-// selected afterwards (motion_refine.hip: texel_or_zero), two tiles per trip so that four waves keep sixteen loads in flight.
+// selected afterwards (lfg_device.hpp: texel_or_zero), two tiles per trip so that four waves keep sixteen loads in flight.
 // Partial sums stay in registers: the SAD per lane, the matched count per wave (ballot + population count, a scalar).  Both
 // are 64-bit, so no frame size can wrap them.  At the end: wave reduction, four values through LDS, one pair of atomicAdd.
 // All three results are integers: neither the walk nor the order of the atomics changes them.
@@ -20,6 +20,7 @@
 
 #include "lfg_internal.hpp"
 #include "lfg_device.hpp"
+#include "lfg_vector_word.hpp"
 
 namespace lfg {
 namespace {
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(kPairBlockX * kPairBlockY) void pair_match_kernel(
     for (uint32_t t0 = blockIdx.x; t0 < tiles; t0 += gridDim.x * kPairUnroll) {
         int x[kPairUnroll], y[kPairUnroll];
         uint32_t vec[kPairUnroll], c[kPairUnroll], p[kPairUnroll];
-        bool inTile[kPairUnroll], inPrev[kPairUnroll];
+        bool inTile[kPairUnroll];
 #pragma unroll
         for (int k = 0; k < kPairUnroll; ++k) {
             const uint32_t t = t0 + (uint32_t)k * gridDim.x;
@@ -59,13 +60,13 @@ __global__ __launch_bounds__(kPairBlockX * kPairBlockY) void pair_match_kernel(
         }
 #pragma unroll
         for (int k = 0; k < kPairUnroll; ++k) {
-            const int sx = min(x[k], W - 1) + (int)(int8_t)(vec[k] & 0xffu), sy = min(y[k], H - 1) + (int)(int8_t)(vec[k] >> 8);
-            inPrev[k] = sx >= 0 && sx < W && sy >= 0 && sy < H;
-            p[k] = *reinterpret_cast<const uint32_t *>(prev + (size_t)min(max(sy, 0), H - 1) * prevPitch + (size_t)min(max(sx, 0), W - 1) * 4u);
+            const Mv v = mv_unpack((uint16_t)vec[k]);
+            p[k] = texel_or_zero(prev, prevPitch, min(x[k], W - 1) + v.x, min(y[k], H - 1) + v.y, W, H);
         }
 #pragma unroll
         for (int k = 0; k < kPairUnroll; ++k) {
-            const uint32_t s = __builtin_amdgcn_sad_u8(c[k], inPrev[k] ? p[k] : 0u, 0u);
+            // the match gate (lfg_mc.hpp: matched), inline: its texels were loaded a loop ahead, and the SAD itself is summed
+            const uint32_t s = __builtin_amdgcn_sad_u8(c[k], p[k], 0u);
             sad += inTile[k] ? s : 0u;
             hits += (unsigned long long)__popcll(__ballot(inTile[k] && s <= matchSad));
         }

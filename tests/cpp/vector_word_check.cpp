@@ -1,6 +1,6 @@
 // Test helper (CPU only): holds csrc/lfg_vector_word.hpp -- the MV_S8X2 word, the order key of a vector, the compensated
-// interpolator's longest-first key -- to the expressions the kernels spelled out before they shared it (interpolate_mc,
-// motion_refine and pair_stats still do), copied below verbatim, and both keys to the tuple orders they stand for.  Prints "ok <cases>" and exits 0, or prints the first difference and exits 1.
+// family's longest-first key -- to the expressions the kernels spelled out before they shared it, copied below verbatim, and
+// both keys to the tuple orders they stand for.  Prints "ok <cases>" and exits 0, or prints the first difference and exits 1.
 #include <cstdint>
 #include <cstdio>
 #include <tuple>
