@@ -109,22 +109,52 @@ def seam_rows(in_h):
     return sorted(r for r in rows if 0 <= r < in_h)
 
 
-def host_stream(tmp_path, frames, *options):
-    """`frames` through lfg_host as a raw file, under the intended semantics and `options`: (its report line, the 2 n - 1
-    frames it presents)."""
+_host_failed = None                                # why no further lfg_host is started in this session
+
+
+def host_run(tmp_path, frames, out_size, *options, timeout=300):
+    """`frames` through lfg_host as a raw file, presented at out_size = (width, height) under `options`, which say everything
+    else -- the semantics and the formats included: (its report line, the frames it presented).  With --input-format nv12 among
+    the options each frame is (y, uv), else an (h, w, 4) array; with --output-format nv12 the presented frames come back as a
+    list of (y, uv), else as one (presented, height, width, 4) array.
+
+    A run that times out or dies from a signal may have left the GPU in a state in which the next run does the same: the first
+    such run fails its test, and every later call fails at once without starting lfg_host again."""
+    global _host_failed
+    if _host_failed:
+        pytest.fail(f"lfg_host is not started again in this session: {_host_failed}", pytrace=False)
     if not os.path.exists(HOST):
         import __graft_entry__ as entry
         entry.build()
-    n, (h, w) = len(frames), frames[0].shape[:2]
+    options = [str(o) for o in options]
+
+    def fmt(name):
+        at = [i for i, o in enumerate(options) if o == name]
+        return options[at[-1] + 1] if at else "rgba"
+
+    nv12_in, nv12_out = fmt("--input-format") == "nv12", fmt("--output-format") == "nv12"
+    (h, w), (ow, oh) = (frames[0][0].shape if nv12_in else frames[0].shape[:2]), out_size
     tmp_path.mkdir(exist_ok=True)
-    src, out = tmp_path / "in.rgba", tmp_path / "out.rgba"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--frames", str(n), "--quiet",
-                        "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended", *options],
-                       capture_output=True, text=True, timeout=300, check=True)
+    src, out = tmp_path / ("in.nv12" if nv12_in else "in.rgba"), tmp_path / ("out.nv12" if nv12_out else "out.rgba")
+    np.concatenate([np.asarray(part).reshape(-1) for f in frames for part in (f if nv12_in else (f,))]).tofile(src)
+    command = [HOST, "--input-width", str(w), "--input-height", str(h), "--output-width", str(ow), "--output-height", str(oh),
+               "--frames", str(len(frames)), "--quiet", "--input-raw", str(src), "--output-raw", str(out), *options]
+    try:
+        p = subprocess.run(command, capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        _host_failed = f"a run did not end within {timeout} s ({' '.join(options)})"
+        pytest.fail(_host_failed, pytrace=False)
+    if p.returncode < 0:
+        _host_failed = f"a run died from signal {-p.returncode} ({' '.join(options)})"
+        pytest.fail(_host_failed + "\n" + p.stderr[-2000:], pytrace=False)
+    assert p.returncode == 0, p.stderr
     info = json.loads(p.stdout.strip().splitlines()[-1])
-    assert info["presented"] == 2 * n - 1
-    return info, np.fromfile(out, np.uint8).reshape(2 * n - 1, h, w, 4)
+    raw = np.fromfile(out, np.uint8)
+    each = ow * oh * 3 // 2 if nv12_out else ow * oh * 4
+    assert raw.size == info["presented"] * each, (raw.size, info["presented"], each)
+    if not nv12_out:
+        return info, raw.reshape(info["presented"], oh, ow, 4)
+    return info, [(f[:ow * oh].reshape(oh, ow), f[ow * oh:].reshape(oh // 2, ow // 2, 2)) for f in raw.reshape(info["presented"], each)]
 
 
 def three_lanes(ctx, inputs, enqueue, alone):

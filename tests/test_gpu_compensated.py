@@ -9,7 +9,7 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import cases
 from tests import mc_model as mc
-from tests.gpu_kit import ctx, first_bad, gpu_vectors, host_stream, pitched, three_lanes
+from tests.gpu_kit import ctx, first_bad, gpu_vectors, host_run, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -337,7 +337,8 @@ def test_host_compensated_stream_matches_capi(tmp_path):
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (12, -6), synth.BASE_SEED + k))
-    _, got = host_stream(tmp_path, frames, "--interpolator", "compensated")
+    _, got = host_run(tmp_path, frames, (w, h), "--semantics", "intended", "--interpolator", "compensated")
+    assert len(got) == 2 * n - 1
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

@@ -10,7 +10,7 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import cases
 from tests import pair_model as pair
-from tests.gpu_kit import DEFAULT, apply, ctx, first_bad, host_stream, pitched, three_lanes
+from tests.gpu_kit import DEFAULT, apply, ctx, first_bad, host_run, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -416,8 +416,8 @@ def test_host_shows_a_source_frame_across_a_cut(ctx, tmp_path):
     w, h = 96, 64
     a, b = synth.make_prev(w, h, synth.BASE_SEED), synth.make_prev(w, h, synth.BASE_SEED + 1)
     frames = [a, synth.translate(a, (3, -2), synth.BASE_SEED), b, synth.translate(b, (3, -2), synth.BASE_SEED + 1)]
-    plain_report, plain = host_stream(tmp_path / "plain", frames)
-    report, got = host_stream(tmp_path / "cut", frames, "--cut-threshold", str(THRESHOLD))
+    plain_report, plain = host_run(tmp_path / "plain", frames, (w, h), "--semantics", "intended")
+    report, got = host_run(tmp_path / "cut", frames, (w, h), "--semantics", "intended", "--cut-threshold", str(THRESHOLD))
     assert plain_report["cuts"] == 0 and plain_report["presented"] == 7
     assert report["cuts"] == 1 and report["presented"] == 7 and report["interpolated"] == 3
     for k in (0, 2, 4, 6):                                    # the real frames: the scale at equal sizes is the identity

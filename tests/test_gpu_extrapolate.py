@@ -3,7 +3,6 @@ switch of lfg_interpolate_frames[_multi] against the CPU chain of the same stage
 --generation option, its presentation order and its --evaluate route."""
 import ctypes
 import json
-import os
 import subprocess
 
 import numpy as np
@@ -13,7 +12,7 @@ from linux_fg_amd import capi, synth
 from tests import cases
 from tests import extrapolate_cases as xc
 from tests import extrapolate_model as ex
-from tests.gpu_kit import DEFAULT, HOST, apply, ctx, first_bad, gpu_vectors, pitched, three_lanes
+from tests.gpu_kit import DEFAULT, HOST, apply, ctx, first_bad, gpu_vectors, host_run, pitched, three_lanes
 from tests.test_diff_model import INT_KEYS
 
 pytestmark = pytest.mark.gpu
@@ -356,30 +355,14 @@ def test_three_lanes_equal_one_lane(ctx):
 
 # ---- lfg_host --generation
 
-def host_run(tmp_path, frames, out_w, out_h, *options):
-    """`frames` through lfg_host as a raw file under the intended semantics: (its report, the frames it presents)."""
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
-    n, (h, w) = len(frames), frames[0].shape[:2]
-    tmp_path.mkdir(exist_ok=True)
-    src, out = tmp_path / "in.rgba", tmp_path / "out.rgba"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--output-width", str(out_w), "--output-height",
-                        str(out_h), "--frames", str(n), "--quiet", "--input-raw", str(src), "--output-raw", str(out),
-                        "--semantics", "intended", *options], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stderr
-    return json.loads(p.stdout.strip().splitlines()[-1]), np.fromfile(out, np.uint8).reshape(-1, out_h, out_w, 4)
-
-
 def test_host_presents_the_real_frame_first(tmp_path):
     w, h, n = 64, 36, 4
     aheads = [0.5, 1.0]
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (3, -2), synth.BASE_SEED + k))
-    options = ("--interpolator", "compensated", "--factors", "0.5,1.0")
-    info, got = host_run(tmp_path / "ahead", frames, 2 * w, 2 * h, "--generation", "extrapolate", *options)
+    options = ("--semantics", "intended", "--interpolator", "compensated", "--factors", "0.5,1.0")
+    info, got = host_run(tmp_path / "ahead", frames, (2 * w, 2 * h), "--generation", "extrapolate", *options)
     assert info["presented"] == len(got) == n + 2 * (n - 1) and info["interpolated"] == 2 * (n - 1)
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
@@ -399,8 +382,8 @@ def test_host_presents_the_real_frame_first(tmp_path):
         assert (g == e).all(), k
     assert not (got[2] == got[1]).all()                               # the generated frames are no copies of the real one
     # --generation interpolate is the run without the option
-    _, plain = host_run(tmp_path / "plain", frames, 2 * w, 2 * h, *options)
-    _, named = host_run(tmp_path / "named", frames, 2 * w, 2 * h, "--generation", "interpolate", *options)
+    _, plain = host_run(tmp_path / "plain", frames, (2 * w, 2 * h), *options)
+    _, named = host_run(tmp_path / "named", frames, (2 * w, 2 * h), "--generation", "interpolate", *options)
     assert plain.shape == named.shape == got.shape and (plain == named).all()
     assert (plain[-1] == want[-3]).all()                              # interpolating, the newest real frame comes last
 

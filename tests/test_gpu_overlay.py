@@ -12,7 +12,7 @@ from tests import cases
 from tests import mc_model as mc
 from tests import overlay_cases as oc
 from tests import overlay_model as ov
-from tests.gpu_kit import apply, ctx, first_bad, gpu_vectors, host_stream, pitched, three_lanes
+from tests.gpu_kit import apply, ctx, first_bad, gpu_vectors, host_run, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -447,7 +447,8 @@ def test_host_protect_static_matches_the_chain(tmp_path):
         f = synth.translate(bg, (k * pan[0], k * pan[1]), oc.SEED) if k else bg.copy()
         f[on] = px[on]
         frames.append(f)
-    info, got = host_stream(tmp_path, frames, "--interpolator", "compensated", "--protect-static", "0")
+    info, got = host_run(tmp_path, frames, (oc.W, oc.H), "--semantics", "intended", "--interpolator", "compensated", "--protect-static", "0")
+    assert len(got) == 2 * n - 1
     assert info["protect_static"] == 0
     with capi.Context(0) as c:
         ups = []

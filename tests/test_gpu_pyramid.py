@@ -9,7 +9,7 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import cases
 from tests import pyramid_model as pm
-from tests.gpu_kit import ctx, host_stream, pitched, three_lanes
+from tests.gpu_kit import ctx, host_run, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -199,7 +199,8 @@ def test_host_pyramid_stream_matches_capi(tmp_path):
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (20, 0), synth.BASE_SEED + k))
-    _, got = host_stream(tmp_path, frames, "--motion", "pyramid")
+    _, got = host_run(tmp_path, frames, (w, h), "--semantics", "intended", "--motion", "pyramid")
+    assert len(got) == 2 * n - 1
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

@@ -11,7 +11,7 @@ from tests import cases
 from tests import mc_model as mc
 from tests import pyramid_model as pm
 from tests import refine_model as rm
-from tests.gpu_kit import ctx, first_bad, gpu_vectors, host_stream, pitched, three_lanes
+from tests.gpu_kit import ctx, first_bad, gpu_vectors, host_run, pitched, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -273,7 +273,8 @@ def test_host_refined_stream_matches_capi(tmp_path):
     frames = [synth.make_prev(w, h)]
     for k in range(1, n):
         frames.append(synth.translate(frames[-1], (12, -6), synth.BASE_SEED + k))
-    _, got = host_stream(tmp_path, frames, "--interpolator", "compensated", "--refine-vectors", "1")
+    _, got = host_run(tmp_path, frames, (w, h), "--semantics", "intended", "--interpolator", "compensated", "--refine-vectors", "1")
+    assert len(got) == 2 * n - 1
     with capi.Context(0) as c:
         c.set_semantics(capi.SEMANTICS_INTENDED)
         ins = [c.frame_from(f) for f in frames]

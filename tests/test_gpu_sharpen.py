@@ -3,10 +3,8 @@ under every layout that changes the path (the 16-byte kernel, its remainder laun
 row, regions of interest, argument checks, three lanes -- and lfg_host --sharpen, whose presented frames must be the model of the
 frames it presents without the option."""
 import ctypes
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +12,7 @@ import pytest
 from linux_fg_amd import capi, synth
 from tests import sharpen_model as sm
 from tests import yuv_model as ym
-from tests.gpu_kit import HOST, ROOT, ctx, host_stream, three_lanes
+from tests.gpu_kit import ROOT, ctx, host_run, three_lanes
 
 pytestmark = pytest.mark.gpu
 
@@ -210,23 +208,7 @@ def test_three_lanes_give_the_same(ctx):
 
 # ---- 5. lfg_host --sharpen
 
-def presented(tmp_path, frames, out_size, *options, fmt="rgba"):
-    """`frames` through lfg_host at another output size (gpu_kit.host_stream presents at the input size), under the intended
-    semantics: (its report line, what it presented as one byte array per frame)."""
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
-    (h, w), (ow, oh) = frames[0].shape[:2], out_size
-    tmp_path.mkdir(exist_ok=True)
-    src, out = tmp_path / "in.rgba", tmp_path / f"out.{fmt}"
-    np.concatenate([f.reshape(-1) for f in frames]).tofile(src)
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--output-width", str(ow), "--output-height", str(oh),
-                        "--frames", str(len(frames)), "--quiet", "--input-raw", str(src), "--output-raw", str(out), "--semantics", "intended",
-                        "--interpolator", "compensated", "--output-format", fmt, *options], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr
-    info = json.loads(p.stdout.strip().splitlines()[-1])
-    raw = np.fromfile(out, np.uint8).reshape(info["presented"], -1)
-    return info, (raw.reshape(info["presented"], oh, ow, 4) if fmt == "rgba" else raw)
+COMPENSATED = ("--semantics", "intended", "--interpolator", "compensated")
 
 
 @pytest.fixture(scope="module")
@@ -236,7 +218,7 @@ def stream(tmp_path_factory):
     frames = [synth.make_prev(w, h, synth.BASE_SEED)]
     for k in (1, 2):
         frames.append(synth.translate(frames[-1], (2, -1), synth.BASE_SEED + k))
-    info, plain = presented(tmp_path_factory.mktemp("plain"), frames, (48, 32))
+    info, plain = host_run(tmp_path_factory.mktemp("plain"), frames, (48, 32), *COMPENSATED)
     assert info["presented"] == 5 and "sharpen" not in info
     return frames, plain
 
@@ -245,7 +227,7 @@ def test_host_sharpens_real_and_generated_frames_alike(stream, tmp_path):
     """All five presented frames are the model of the frames presented without the option: the generated ones could not be if
     the motion stage had seen a sharpened frame."""
     frames, plain = stream
-    info, got = presented(tmp_path / "s", frames, (48, 32), "--sharpen", "24")
+    info, got = host_run(tmp_path / "s", frames, (48, 32), *COMPENSATED, "--sharpen", "24")
     assert info["sharpen"] == 24 and info["presented"] == 5 and info["interpolated"] == 2
     for k in range(5):
         want = sm.sharpen(plain[k], 24)
@@ -255,40 +237,40 @@ def test_host_sharpens_real_and_generated_frames_alike(stream, tmp_path):
 
 def test_host_sharpens_with_three_frames_in_flight(stream, tmp_path):
     frames, plain = stream
-    _, got = presented(tmp_path / "s", frames, (48, 32), "--sharpen", "24", "--in-flight", "3")
+    _, got = host_run(tmp_path / "s", frames, (48, 32), *COMPENSATED, "--sharpen", "24", "--in-flight", "3")
     assert all((got[k] == sm.sharpen(plain[k], 24)).all() for k in range(5))
 
 
 def test_host_sharpens_every_factor(stream, tmp_path):
     frames, _ = stream
     factors = ("--factors", "0.25,0.5,0.75")
-    info, plain = presented(tmp_path / "p", frames, (48, 32), *factors)
-    sharp_info, got = presented(tmp_path / "s", frames, (48, 32), *factors, "--sharpen", "24")
+    info, plain = host_run(tmp_path / "p", frames, (48, 32), *COMPENSATED, *factors)
+    sharp_info, got = host_run(tmp_path / "s", frames, (48, 32), *COMPENSATED, *factors, "--sharpen", "24")
     assert info["presented"] == sharp_info["presented"] == 9
     assert all((got[k] == sm.sharpen(plain[k], 24)).all() for k in range(9))
 
 
 def test_host_sharpen_0_is_the_default(stream, tmp_path):
     frames, plain = stream
-    info, got = presented(tmp_path / "s", frames, (48, 32), "--sharpen", "0")
+    info, got = host_run(tmp_path / "s", frames, (48, 32), *COMPENSATED, "--sharpen", "0")
     assert "sharpen" not in info and (got == plain).all()
 
 
 def test_host_converts_the_sharpened_frames_to_nv12(stream, tmp_path):
     frames, plain = stream
     mode = (ym.BT709, ym.LIMITED, ym.LEFT)                        # lfg_host's defaults
-    _, got = presented(tmp_path / "s", frames, (48, 32), "--sharpen", "24", fmt="nv12")
+    _, got = host_run(tmp_path / "s", frames, (48, 32), *COMPENSATED, "--sharpen", "24", "--output-format", "nv12")
     for k in range(5):
         want_y, want_uv = ym.rgba_to_nv12(sm.sharpen(plain[k], 24), *mode)
-        assert (got[k][:48 * 32].reshape(32, 48) == want_y).all() and (got[k][48 * 32:].reshape(16, 24, 2) == want_uv).all(), k
+        assert (got[k][0] == want_y).all() and (got[k][1] == want_uv).all(), k
 
 
 def test_host_sharpens_at_the_input_size(tmp_path):
-    """Through gpu_kit.host_stream, which presents at the input size (the upscale is then the identity)."""
+    """Presented at the input size (the upscale is then the identity)."""
     frames = [synth.make_prev(24, 16, synth.BASE_SEED)]
     for k in (1, 2):
         frames.append(synth.translate(frames[-1], (2, -1), synth.BASE_SEED + k))
-    _, plain = host_stream(tmp_path / "p", frames, "--interpolator", "compensated")
-    info, got = host_stream(tmp_path / "s", frames, "--interpolator", "compensated", "--sharpen", "24")
-    assert info["sharpen"] == 24
+    _, plain = host_run(tmp_path / "p", frames, (24, 16), *COMPENSATED)
+    info, got = host_run(tmp_path / "s", frames, (24, 16), *COMPENSATED, "--sharpen", "24")
+    assert info["sharpen"] == 24 and len(plain) == len(got) == 5
     assert all((got[k] == sm.sharpen(plain[k], 24)).all() for k in range(5))

@@ -3,16 +3,13 @@
 row, regions of interest, every (Y, Cb, Cr) and every (R, G, B), argument checks, two lanes -- and lfg_host with raw NV12 in and
 out against the chain model -> CPU scale and interpolation models -> model."""
 import ctypes
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from linux_fg_amd import capi
 from tests import yuv_model as ym
-from tests.gpu_kit import HOST, ctx
+from tests.gpu_kit import ctx, host_run
 
 pytestmark = pytest.mark.gpu
 
@@ -327,24 +324,6 @@ def test_two_lanes_give_the_same(ctx):
 
 # ---- 7. lfg_host with raw NV12 in and out
 
-def host_nv12(tmp_path, frames_nv12, out_size, *options):
-    """NV12 frames through `lfg_host --input-format nv12 --output-format nv12`: (report, the presented frames as (y, uv))."""
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
-    (h, w), (ow, oh) = frames_nv12[0][0].shape, out_size
-    tmp_path.mkdir(exist_ok=True)
-    src, out = tmp_path / "in.nv12", tmp_path / "out.nv12"
-    np.concatenate([np.concatenate([y.reshape(-1), uv.reshape(-1)]) for y, uv in frames_nv12]).tofile(src)
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--output-width", str(ow), "--output-height", str(oh),
-                        "--frames", str(len(frames_nv12)), "--quiet", "--input-raw", str(src), "--output-raw", str(out),
-                        "--input-format", "nv12", "--output-format", "nv12", *options], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr
-    info = json.loads(p.stdout.strip().splitlines()[-1])
-    raw = np.fromfile(out, np.uint8).reshape(info["presented"], oh * ow * 3 // 2)
-    return info, [(f[:ow * oh].reshape(oh, ow), f[ow * oh:].reshape(oh // 2, ow // 2, 2)) for f in raw]
-
-
 @pytest.mark.parametrize("options,mode", [((), (ym.BT709, ym.LIMITED, ym.LEFT)),
                                           (("--yuv-matrix", "601", "--yuv-range", "full", "--chroma", "replicate"), (ym.BT601, ym.FULL, ym.REPLICATE))],
                          ids=["defaults", "601-full-replicate"])
@@ -358,18 +337,11 @@ def test_host_nv12_in_and_out(ctx, oracle, tmp_path, options, mode):
     for k in range(1, n):
         rgba.append(synth.translate(rgba[-1], (3, -2), synth.BASE_SEED + k))
     nv12 = [ym.rgba_to_nv12(f, *mode) for f in rgba]
-    info, shown = host_nv12(tmp_path / "nv12", nv12, (2 * w, 2 * h), *options)
+    info, shown = host_run(tmp_path / "nv12", nv12, (2 * w, 2 * h), "--input-format", "nv12", "--output-format", "nv12", *options)
     assert info["presented"] == 2 * n - 1 and info["input_format"] == "nv12" and info["output_format"] == "nv12"
     # the same stream with RGBA out: the frames the NV12 sink converted
-    src = tmp_path / "nv12" / "in.nv12"
-    out = tmp_path / "out.rgba"
-    p = subprocess.run([HOST, "--input-width", str(w), "--input-height", str(h), "--output-width", str(2 * w), "--output-height", str(2 * h),
-                        "--frames", str(n), "--quiet", "--input-raw", str(src), "--output-raw", str(out), "--input-format", "nv12", *options],
-                       capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr
-    report = json.loads(p.stdout.strip().splitlines()[-1])
-    assert report["input_format"] == "nv12" and report["output_format"] == "rgba"
-    frames = np.fromfile(out, np.uint8).reshape(2 * n - 1, 2 * h, 2 * w, 4)
+    report, frames = host_run(tmp_path / "rgba", nv12, (2 * w, 2 * h), "--input-format", "nv12", *options)
+    assert report["input_format"] == "nv12" and report["output_format"] == "rgba" and len(frames) == 2 * n - 1
     for k in range(n):                                        # real frames: the converted input, upscaled
         want = oracle.scale(ym.nv12_to_rgba(*nv12[k], *mode), 2 * w, 2 * h)
         assert np.abs(frames[2 * k].astype(np.int16) - want.astype(np.int16)).max() <= 1, k
