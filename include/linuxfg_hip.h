@@ -638,6 +638,53 @@ int  lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_y
  * padding. */
 int  lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int strength);
 
+/* Resampling with a choice of filter and anti-aliased downscaling.  No reference counterpart: lfg_scale is the reference's
+ * scale.comp, six Lanczos-3 taps per axis at every ratio, which point-samples once the ratio is far below 1 (at 3:1 the
+ * output centres fall on texel centres, where Lanczos-3 is an impulse).  lfg_scale stays as it is; this is a separate call.
+ * Everything past the table is integer arithmetic; it depends on no setting of the context.
+ *   Filters, with support S: LFG_FILTER_NEAREST (one tap); LFG_FILTER_BILINEAR (the triangle 1 - |x|, S = 1);
+ *   LFG_FILTER_CATMULL_ROM (the cubic with B = 0, C = 1/2, S = 2); LFG_FILTER_MITCHELL (the cubic with B = C = 1/3, S = 2);
+ *   LFG_FILTER_LANCZOS2 and LFG_FILTER_LANCZOS3 (a sin(pi x) sin(pi x / a) / (pi x)^2, 1 at 0, 0 for |x| >= a; S = a = 2, 3).
+ *   The cubic: for |x| < 1, ((12 - 9B - 6C)|x|^3 + (-18 + 12B + 6C)|x|^2 + (6 - 2B)) / 6; for 1 <= |x| < 2,
+ *   ((-B - 6C)|x|^3 + (6B + 30C)|x|^2 + (-12B - 48C)|x| + (8B + 24C)) / 6.
+ *   Table of one axis, `in` -> `out` samples (lfg_resample_taps): N(p, k) = (2k + 1) out - (2p + 1) in and D = 2 max(in, out);
+ *   the taps of output p are the integers k with |N| < S D -- integers decide which taps exist, no float does -- and the raw
+ *   weight of a tap is f(N / D) in double.  So the filter is evaluated at the distance between texel centre and output centre
+ *   divided by max(1, in / out): stretched where the axis shrinks (anti-aliasing), the plain kernel where it grows.
+ *   LFG_FILTER_NEAREST is the single tap k = floor((2p + 1) in / (2 out)) with weight 16384.  Then, in this order:
+ *     1. each raw weight is divided by the sum of the row's raw weights, summed in tap order;
+ *     2. each tap is folded onto clamp(k, 0, in - 1), weights that land on one texel added in tap order (edge replication):
+ *        first[p] is the smallest folded index and count[p] the span, so first >= 0 and first + count <= in;
+ *     3. q = rint(w * 16384), ties to even;
+ *     4. 16384 - sum q is added to the first tap of largest |q|: every row sums to exactly 16384.
+ *   A row of more than LFG_RESAMPLE_MAX_TAPS taps before folding (Lanczos-3 from about 10.6 : 1 on), or one with
+ *   sum |q| > 32768, is refused: LFG_ERR_UNSUPPORTED.
+ *   Pixels, horizontal first, all four channels alike, >> the arithmetic shift (floor):
+ *     h (y, p)_c = sum_j wx[p][j] in(y, fx[p] + j)_c          exact in 32 bits
+ *     h'(y, p)_c = (h + 128) >> 8                             fits 16 bits because sum |w| <= 32768
+ *     v (q, p)_c = sum_j wy[q][j] h'(fy[q] + j, p)_c          |v| <= 32640 * 32768 < 2^31
+ *     out(q, p)_c = clamp((v + 2^19) >> 20, 0, 255)
+ *   With in == out every filter but Mitchell, which is no interpolating kernel, returns the input bytes.
+ * Frames: in and out both RGBA8, of any sizes >= 1; rows 4-byte aligned, the pitch a multiple of 4 and at least 4 * width; out
+ * overlaps no byte of in; row offsets are size_t.  A view made with lfg_frame_wrap is its own image: nothing outside it is
+ * read.  Any violation, a NULL pointer or NULL data, a wrong format or an unknown filter returns LFG_ERR_INVALID, a table
+ * that is refused LFG_ERR_UNSUPPORTED -- both before anything is enqueued, with a message latched.  Enqueued on the selected
+ * lane as ONE launch (both passes; the horizontal pass of a tile stays in LDS) and timed under LFG_STAGE_SCALE.  The first
+ * call for a (filter, in, out) triple of an axis builds its table with lfg_resample_taps and uploads it; the context keeps a
+ * bounded number of them.  lfg_scale_last_kernel is not touched.  Only the W * 4 bytes of each output row are written. */
+typedef enum {
+    LFG_FILTER_NEAREST = 0, LFG_FILTER_BILINEAR = 1, LFG_FILTER_CATMULL_ROM = 2, LFG_FILTER_MITCHELL = 3, LFG_FILTER_LANCZOS2 = 4,
+    LFG_FILTER_LANCZOS3 = 5
+} lfg_filter;
+#define LFG_RESAMPLE_MAX_TAPS 64
+int  lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter);
+/* The table above -- the one builder: lfg_resample uploads what this returns.  A pure host function: no context, no GPU.
+ * first and count hold out_size entries, weights out_size * LFG_RESAMPLE_MAX_TAPS: row p starts at p * LFG_RESAMPLE_MAX_TAPS
+ * and its entries from count[p] on are 0.  LFG_ERR_INVALID for a NULL pointer, a size of 0, an in_size of 2^31 or more (first
+ * is an int32_t) or an unknown filter;
+ * LFG_ERR_UNSUPPORTED for a refused table (the arrays are then undefined). */
+int  lfg_resample_taps(int filter, uint32_t in_size, uint32_t out_size, int32_t *first, uint32_t *count, int16_t *weights);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

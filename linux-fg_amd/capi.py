@@ -31,6 +31,9 @@ _BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2}
 COMM_ID_BYTES = 128
 MAX_LANES = 4
 MAX_SHARPEN = 64
+FILTER_NEAREST, FILTER_BILINEAR, FILTER_CATMULL_ROM, FILTER_MITCHELL, FILTER_LANCZOS2, FILTER_LANCZOS3 = range(6)
+RESAMPLE_MAX_TAPS = 64
+ERR_INVALID, ERR_UNSUPPORTED = -1, -4
 
 
 class LfgError(RuntimeError):
@@ -157,6 +160,8 @@ SIGNATURES = {
     "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
     "lfg_rgba_to_nv12": (_i, [_vp, _FP, ctypes.POINTER(Nv12), _i, _i, _i]),
     "lfg_sharpen": (_i, [_vp, _FP, _FP, _i]),
+    "lfg_resample": (_i, [_vp, _FP, _FP, _i]),
+    "lfg_resample_taps": (_i, [_i, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int16)]),
     "lfg_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
@@ -205,6 +210,24 @@ def yuv_coefficients(matrix: int, yuv_range: int):
     if rc != 0:
         raise LfgError(f"lfg_yuv_coefficients failed ({rc}): unknown matrix or range")
     return tuple(int(v) for v in to_rgb), tuple(int(v) for v in to_yuv)
+
+
+def resample_taps(filt: int, n_in: int, n_out: int):
+    """(first[n_out] int32, count[n_out] uint32, weights[n_out, RESAMPLE_MAX_TAPS] int16) of lfg_resample_taps: the table of one
+    axis that lfg_resample uploads.  Needs no context and no GPU.  Raises LfgError, with the code as `.code`, where the call refuses."""
+    n_in, n_out = int(n_in), int(n_out)
+    rows = n_out if 0 < n_out < 2 ** 32 else 0
+    first, count = np.zeros(rows, np.int32), np.zeros(rows, np.uint32)
+    weights = np.zeros((rows, RESAMPLE_MAX_TAPS), np.int16)
+    rc = load().lfg_resample_taps(int(filt), n_in if 0 < n_in < 2 ** 32 else 0, rows,
+                                  first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), count.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                  weights.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
+    if rc != 0:
+        err = LfgError(f"lfg_resample_taps failed ({rc}): " + ("more than RESAMPLE_MAX_TAPS taps per sample" if rc == ERR_UNSUPPORTED
+                                                                 else "a size of 0 or an unknown filter"))
+        err.code = rc
+        raise err
+    return first, count, weights
 
 
 def load() -> ctypes.CDLL:
@@ -654,6 +677,11 @@ class Context:
         """lfg_sharpen: `src` sharpened into `dst` (both RGBA8, one size, no overlap), strength 0 .. MAX_SHARPEN, limited to
         the range of each pixel and its four neighbours; for presented frames only, never for one a motion stage reads."""
         self._check(self.lib.lfg_sharpen(self.h, ctypes.byref(src), ctypes.byref(dst), int(strength)), "lfg_sharpen")
+
+    def resample(self, src: Frame, dst: Frame, filt: int):
+        """lfg_resample: `src` resampled into `dst` (both RGBA8, any sizes, no overlap) under one of FILTER_*, anti-aliased where
+        an axis shrinks; one launch, timed under STAGE_SCALE."""
+        self._check(self.lib.lfg_resample(self.h, ctypes.byref(src), ctypes.byref(dst), int(filt)), "lfg_resample")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -1,6 +1,7 @@
 // lfg_capi.cpp -- implementation of the C-ABI in include/linuxfg_hip.h.
 // The only translation units that touch HIP are this file, lfg_comm.cpp and the kernel files (*.hip).
 // There is no CPU fallback anywhere: every entry point needs a live HIP device.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -505,6 +506,7 @@ LFG_EXPORT void lfg_context_destroy(lfg_context *ctx) {
     for (auto &p : ctx->prof_free) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &t : ctx->tables) { (void)hipFree(t.d_start); (void)hipFree(t.d_weight); (void)hipFree(t.d_class); (void)hipFree(t.d_palette); }
     for (auto &t : ctx->uv_tables) (void)hipFree(t.d_uv);
+    for (auto &t : ctx->resample_tables) (void)hipFree(t.d_base);
     if (ctx->motion_tables) (void)hipFree(ctx->motion_tables);
     delete ctx;
 }
@@ -1710,6 +1712,167 @@ LFG_EXPORT int lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: the output overlaps the input");
     hipError_t e = lfg::launch_sharpen(ctx->cur().stream, *in, *out, strength);
     if (e != hipSuccess) return fail_hip(ctx, e, "sharpen kernel launch");
+    return LFG_OK;
+}
+
+// ---- resampling with a choice of filter (resample.hip)
+
+namespace {
+
+// The cubic of Mitchell and Netravali; |x| < 2.
+double resample_cubic(double x, double B, double C) {
+    x = std::fabs(x);
+    if (x < 1.0) return ((12.0 - 9.0 * B - 6.0 * C) * x * x * x + (-18.0 + 12.0 * B + 6.0 * C) * x * x + (6.0 - 2.0 * B)) / 6.0;
+    if (x < 2.0) return ((-B - 6.0 * C) * x * x * x + (6.0 * B + 30.0 * C) * x * x + (-12.0 * B - 48.0 * C) * x + (8.0 * B + 24.0 * C)) / 6.0;
+    return 0.0;
+}
+
+double resample_lanczos(double x, double a) {
+    if (x == 0.0) return 1.0;
+    if (std::fabs(x) >= a) return 0.0;
+    const double px = 3.141592653589793238462643383279502884 * x;
+    return a * std::sin(px) * std::sin(px / a) / (px * px);
+}
+
+double resample_filter(int filter, double x) {
+    switch (filter) {
+        case LFG_FILTER_BILINEAR: return std::fabs(x) < 1.0 ? 1.0 - std::fabs(x) : 0.0;
+        case LFG_FILTER_CATMULL_ROM: return resample_cubic(x, 0.0, 0.5);
+        case LFG_FILTER_MITCHELL: return resample_cubic(x, 1.0 / 3.0, 1.0 / 3.0);
+        case LFG_FILTER_LANCZOS2: return resample_lanczos(x, 2.0);
+        default: return resample_lanczos(x, 3.0);
+    }
+}
+
+int resample_support(int filter) { return filter == LFG_FILTER_BILINEAR ? 1 : filter == LFG_FILTER_LANCZOS3 ? 3 : 2; }
+
+bool resample_filter_known(int filter) { return filter >= LFG_FILTER_NEAREST && filter <= LFG_FILTER_LANCZOS3; }
+
+__int128 floor_div(__int128 a, __int128 b) {                 // b > 0
+    const __int128 q = a / b;
+    return a % b != 0 && a < 0 ? q - 1 : q;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_resample_taps(int filter, uint32_t in_size, uint32_t out_size, int32_t *first, uint32_t *count, int16_t *weights) {
+    if (!first || !count || !weights || in_size == 0 || out_size == 0 || in_size > 0x7fffffffu || !resample_filter_known(filter))
+        return LFG_ERR_INVALID;
+    constexpr int kMax = LFG_RESAMPLE_MAX_TAPS;
+    const __int128 in = in_size, out = out_size, D = 2 * (in > out ? in : out), lim = resample_support(filter) * D;
+    for (uint32_t p = 0; p < out_size; ++p) {
+        int16_t *row = weights + (size_t)p * kMax;
+        for (int j = 0; j < kMax; ++j) row[j] = 0;
+        const __int128 centre = (2 * (__int128)p + 1) * in;
+        if (filter == LFG_FILTER_NEAREST) {
+            first[p] = (int32_t)floor_div(centre, 2 * out);
+            count[p] = 1u;
+            row[0] = 16384;
+            continue;
+        }
+        // the integers k with |(2k + 1) out - centre| < lim
+        const __int128 k0 = floor_div(centre - lim - out, 2 * out) + 1;
+        const __int128 k1 = floor_div(centre + lim - out + 2 * out - 1, 2 * out) - 1;
+        const __int128 taps = k1 - k0 + 1;
+        if (taps > kMax) return LFG_ERR_UNSUPPORTED;
+        const int n = (int)taps;
+        double raw[kMax], sum = 0.0;
+        for (int j = 0; j < n; ++j) {
+            raw[j] = resample_filter(filter, (double)((2 * (k0 + j) + 1) * out - centre) / (double)D);
+            sum += raw[j];
+        }
+        const auto clamped = [&](__int128 k) { return k < 0 ? (__int128)0 : k > in - 1 ? in - 1 : k; };
+        const __int128 lo = clamped(k0);
+        const int span = (int)(clamped(k1) - lo) + 1;
+        double folded[kMax];
+        for (int j = 0; j < span; ++j) folded[j] = 0.0;
+        for (int j = 0; j < n; ++j) folded[(int)(clamped(k0 + j) - lo)] += raw[j] / sum;
+        long q[kMax], total = 0, magnitude = 0;
+        int big = 0;
+        for (int j = 0; j < span; ++j) {
+            q[j] = std::lrint(folded[j] * 16384.0);           // (ties to even: the default rounding mode)
+            total += q[j];
+            if (std::labs(q[j]) > std::labs(q[big])) big = j;
+        }
+        q[big] += 16384 - total;
+        for (int j = 0; j < span; ++j) magnitude += std::labs(q[j]);
+        if (magnitude > 32768) return LFG_ERR_UNSUPPORTED;
+        first[p] = (int32_t)lo;
+        count[p] = (uint32_t)span;
+        for (int j = 0; j < span; ++j) row[j] = (int16_t)q[j];
+    }
+    return LFG_OK;
+}
+
+namespace {
+
+// Bounded like the axis tables: called at the top of lfg_resample, before either of its tables is looked up, so that the two
+// lookups of a call can never free each other's table.
+void trim_resample_tables(lfg_context *ctx) {
+    while (ctx->resample_tables.size() > 14) {
+        (void)sync_lanes(ctx);                                 // a queued kernel may still read it
+        (void)hipFree(ctx->resample_tables.front().d_base);
+        ctx->resample_tables.erase(ctx->resample_tables.begin());
+    }
+}
+
+// The table of one axis, built and uploaded at its first use.  Returned by value: the pointers in it are the device's.
+int resample_table(lfg_context *ctx, int filter, uint32_t in_size, uint32_t out_size, lfg::ResampleTable *out) {
+    for (const auto &t : ctx->resample_tables)
+        if (t.filter == filter && t.in_size == in_size && t.out_size == out_size) { *out = t; return LFG_OK; }
+    const size_t n = out_size;
+    std::vector<int32_t> first(n);
+    std::vector<uint32_t> count(n);
+    std::vector<int16_t> weights(n * LFG_RESAMPLE_MAX_TAPS);
+    const int rc = lfg_resample_taps(filter, in_size, out_size, first.data(), count.data(), weights.data());
+    if (rc == LFG_ERR_UNSUPPORTED)
+        return fail(ctx, rc, "lfg_resample: " + std::to_string(in_size) + " -> " + std::to_string(out_size) +
+                                 " needs more than LFG_RESAMPLE_MAX_TAPS taps per sample under this filter");
+    if (rc != LFG_OK) return fail(ctx, rc, "lfg_resample: a frame of this size has no table");
+    lfg::ResampleTable t;
+    t.filter = filter; t.in_size = in_size; t.out_size = out_size;
+    t.plan = lfg::resample_plan(first.data(), count.data(), out_size);
+    // the device's rows are as long as the longest row here, rounded up to even, instead of LFG_RESAMPLE_MAX_TAPS
+    uint32_t stride = 2;
+    for (size_t p = 0; p < n; ++p) stride = std::max(stride, (count[p] + 1u) & ~1u);
+    const size_t offCount = n * sizeof(int32_t), offWeights = offCount + n * sizeof(uint32_t), bytes = offWeights + n * stride * sizeof(int16_t);
+    std::vector<uint8_t> host(bytes, 0);
+    memcpy(host.data(), first.data(), n * sizeof(int32_t));
+    memcpy(host.data() + offCount, count.data(), n * sizeof(uint32_t));
+    for (size_t p = 0; p < n; ++p)
+        memcpy(host.data() + offWeights + p * stride * sizeof(int16_t), &weights[p * LFG_RESAMPLE_MAX_TAPS], count[p] * sizeof(int16_t));
+    LFG_HIP(ctx, hipMalloc((void **)&t.d_base, bytes));
+    // A synchronous copy: the pageable host vector goes out of scope when this function returns.
+    const hipError_t e = hipMemcpy(t.d_base, host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(t.d_base); return fail_hip(ctx, e, "hipMemcpy(resample table)"); }
+    t.axis.first = reinterpret_cast<const int32_t *>(t.d_base);
+    t.axis.count = reinterpret_cast<const uint32_t *>(t.d_base + offCount);
+    t.axis.weights = reinterpret_cast<const int16_t *>(t.d_base + offWeights);
+    t.axis.stride = stride;
+    ctx->resample_tables.push_back(t);
+    *out = t;
+    return LFG_OK;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_resample: in and out must be non-empty RGBA8");
+    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_resample: RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    if (!resample_filter_known(filter)) return fail(ctx, LFG_ERR_INVALID, "lfg_resample: unknown filter");
+    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_resample: the output overlaps the input");
+    trim_resample_tables(ctx);
+    lfg::ResampleTable tx, ty;
+    int rc = resample_table(ctx, filter, in->width, out->width, &tx);
+    if (rc == LFG_OK) rc = resample_table(ctx, filter, in->height, out->height, &ty);
+    if (rc != LFG_OK) return rc;
+    StageTimer timer(ctx, LFG_STAGE_SCALE);
+    const hipError_t e = lfg::launch_resample(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan);
+    if (e != hipSuccess) return fail_hip(ctx, e, "resample kernel launch");
     return LFG_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "linuxfg_hip.h"
 #include "lfg_motion_verdict.hpp"
+#include "lfg_resample.hpp"
 
 namespace lfg {
 
@@ -142,6 +143,16 @@ struct PyramidLayout {
     size_t total = 0;
 };
 
+// One axis' table of lfg_resample for one (filter, in, out): what lfg_resample_taps returned, on the device in ONE allocation
+// (first | count | weights, the weight rows `axis.stride` apart), and the tile plan it gives as a vertical table.
+struct ResampleTable {
+    int filter = 0;
+    uint32_t in_size = 0, out_size = 0;
+    uint8_t *d_base = nullptr;
+    ResampleAxis axis{};
+    ResamplePlan plan{};
+};
+
 struct ProfileSlot {
     hipEvent_t begin = nullptr, end = nullptr;
     int stage = 0;
@@ -201,6 +212,7 @@ struct lfg_context {
     std::string error;
     std::vector<lfg::AxisTable> tables;       // small cache, linear search
     std::vector<lfg::UvTable> uv_tables;      // likewise (interpolate)
+    std::vector<lfg::ResampleTable> resample_tables;   // likewise (lfg_resample)
     int motion_slots = 0;                      // prefilter workgroups resident at once on this device (0 = not queried yet)
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only
@@ -343,6 +355,9 @@ hipError_t launch_rgba_to_nv12(hipStream_t s, const lfg_frame &in, const lfg_nv1
 // Contrast-limited sharpening (sharpen.hip): the 16-byte kernel where base and pitch of both frames allow, with the dword
 // kernel behind it for the 1 .. 3 columns past the last multiple of 4; the dword kernel alone otherwise.
 hipError_t launch_sharpen(hipStream_t s, const lfg_frame &in, const lfg_frame &out, int strength);
+// Resampling (resample.hip): one launch, both passes; `plan` is the vertical table's.
+hipError_t launch_resample(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const ResampleAxis &x, const ResampleAxis &y,
+                           const ResamplePlan &plan);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

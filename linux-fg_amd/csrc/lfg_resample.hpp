@@ -1,0 +1,181 @@
+// lfg_resample.hpp -- the tile plan and the two phase bodies of resample.hip (lfg_resample, include/linuxfg_hip.h) as
+// __host__ __device__ functions of block index, thread index and an LDS pointer: the kernel calls them around its one
+// barrier, and tests/cpp/resample_on_host.cpp, compiled with g++ alone, calls them from loops over blocks and threads --
+// phase 1 for every thread of a block, then phase 2.  Nothing here needs the HIP runtime.
+//
+// A workgroup of kResampleThreads = 256 threads owns a tile of kResampleColumns = 64 output columns x T output rows.  The source
+// rows that tile needs are rowLo = fy[q0] .. rowHi = fy[q1 - 1] + cy[q1 - 1] (first and first + count of a table do not
+// decrease; resample_plan checks it anyway), at most kResampleLdsRows = 64 of them, and the horizontal pass of those rows
+// lives in LDS only: one 8-byte word of four int16 per (source row, output column), consecutive columns at consecutive
+// words, 32 KiB at the most.  The host picks T per call (resample_plan): the largest of 16, 8, 4, 2, 1 at which every tile's
+// rows fit; one output row always does, a row having at most 64 taps.
+//
+//   phase 1   thread = (column c, row group g of 4).  A group takes the tile's source rows in blocks of kResampleBlock = 4
+//             (block g, g + 4, ...): the taps of its column are count[p] consecutive dwords of a row from fx[p] on, taken
+//             four at a time -- one 16-byte load from each of the four rows per 8-byte load of weights -- and the 1 .. 3
+//             that remain one by one; neighbouring lanes read neighbouring or the same dwords.  h' goes to LDS as one 8-byte store.
+//   barrier
+//   phase 2   thread (c, g) forms output rows q0 + g, q0 + g + 4, ... of its column from the LDS column (the row, its first
+//             tap and its weights are the same for a whole wave) and stores one dword per pixel: a wave stores 256 contiguous
+//             bytes.
+// The table guarantees first >= 0 and first + count <= in: no index is clamped here.  Byte offsets are size_t.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace lfg {
+
+constexpr uint32_t kResampleColumns = 64;      // output columns of a tile = lanes of a wave
+constexpr uint32_t kResampleGroups = 4;        // row groups = waves of a workgroup
+constexpr uint32_t kResampleThreads = kResampleColumns * kResampleGroups;
+constexpr uint32_t kResampleLdsRows = 64;      // source rows of a tile at the most (= LFG_RESAMPLE_MAX_TAPS)
+constexpr uint32_t kResampleBlock = 4;         // source rows a thread takes per pass over its taps
+constexpr uint32_t kResampleMaxRows = 16;      // the largest T
+
+struct alignas(8) ResampleWord { uint32_t lo, hi; };          // h' of four channels: R | G << 16, B | A << 16
+
+// One axis' table on the device: rows `stride` weights apart (the largest count rounded up to even, not 64).
+struct ResampleAxis { const int32_t *first; const uint32_t *count; const int16_t *weights; uint32_t stride; };
+
+struct ResampleArgs {
+    const uint8_t *in; size_t inPitch;
+    uint8_t *out; size_t outPitch;
+    uint32_t outW, outH;
+    ResampleAxis x, y;
+    uint32_t rows;                             // T
+};
+
+struct ResamplePlan { uint32_t rows, span; };  // T, and the most source rows one of its tiles needs (LDS: span * 512 bytes)
+
+// The plan of a vertical table (host only).
+inline ResamplePlan resample_plan(const int32_t *first, const uint32_t *count, uint32_t outH) {
+    for (uint32_t T = kResampleMaxRows; T > 1u; T /= 2u) {
+        bool ok = true;
+        uint32_t span = 0;
+        for (uint32_t q0 = 0; q0 < outH && ok; q0 += (outH - q0 < T ? outH - q0 : T)) {
+            const uint32_t q1 = outH - q0 < T ? outH : q0 + T;
+            const int64_t lo = first[q0], hi = (int64_t)first[q1 - 1u] + (int64_t)count[q1 - 1u];
+            for (uint32_t q = q0; q < q1; ++q) ok = ok && first[q] >= lo && (int64_t)first[q] + (int64_t)count[q] <= hi;
+            ok = ok && hi - lo <= (int64_t)kResampleLdsRows;
+            if (ok && (uint32_t)(hi - lo) > span) span = (uint32_t)(hi - lo);
+        }
+        if (ok) return ResamplePlan{T, span};
+    }
+    uint32_t span = 0;
+    for (uint32_t q = 0; q < outH; ++q) span = count[q] > span ? count[q] : span;
+    return ResamplePlan{1u, span};
+}
+
+// The tile (tileX, tileY): its output rows q0 .. q1 - 1 and its source rows rowLo .. rowHi - 1.
+struct ResampleTile { uint32_t q0, q1; int32_t rowLo, rowHi; };
+
+__host__ __device__ inline ResampleTile resample_tile(const ResampleArgs &a, uint32_t tileY) {
+    ResampleTile t;
+    t.q0 = tileY * a.rows;
+    t.q1 = a.outH - t.q0 < a.rows ? a.outH : t.q0 + a.rows;
+    t.rowLo = a.y.first[t.q0];
+    t.rowHi = a.y.first[t.q1 - 1u] + (int32_t)a.y.count[t.q1 - 1u];
+    return t;
+}
+
+// A value that has passed through here is not part of the shift-clamp-pack pattern that the compiler folds into an instruction
+// the device gets wrong (yuv_convert.hip: kept_apart; the build's check_store_hazard.py refuses the instruction).
+__host__ __device__ inline int resample_kept_apart(int v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+
+__host__ __device__ inline int resample_byte(int v) {
+    v = (v + (1 << 19)) >> 20;                                          // (arithmetic shift: floor)
+    return resample_kept_apart(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+
+// Four consecutive texels / weights of a row, at the 4-byte alignment a texel and a table row have.
+struct __attribute__((packed, aligned(4))) ResampleTexels4 { uint32_t t[4]; };
+struct __attribute__((packed, aligned(4))) ResampleWeights4 { uint32_t w[2]; };
+
+__host__ __device__ inline void resample_accumulate(int (&acc)[4], int w, uint32_t texel) {
+    acc[0] += w * (int)(texel & 255u);
+    acc[1] += w * (int)((texel >> 8) & 255u);
+    acc[2] += w * (int)((texel >> 16) & 255u);
+    acc[3] += w * (int)(texel >> 24);
+}
+
+// Phase 1 for thread (c, g) of tile (tileX, tileY): h' of column tileX * 64 + c for the source rows of the group's blocks.
+__host__ __device__ inline void resample_phase1(const ResampleArgs &a, uint32_t tileX, uint32_t tileY, uint32_t c, uint32_t g,
+                                                ResampleWord *lds) {
+    const uint32_t p = tileX * kResampleColumns + c;
+    if (p >= a.outW) return;
+    const ResampleTile t = resample_tile(a, tileY);
+    const size_t x0 = (size_t)a.x.first[p] * 4u;
+    const uint32_t n = a.x.count[p];
+    const int16_t *w = a.x.weights + (size_t)p * a.x.stride;
+    for (int32_t r0 = t.rowLo + (int32_t)(g * kResampleBlock); r0 < t.rowHi; r0 += (int32_t)(kResampleGroups * kResampleBlock)) {
+        // rows r0 .. r0 + 3; those past the tile's last row read that row again and are not written
+        const uint8_t *row[kResampleBlock];
+        int acc[kResampleBlock][4];
+#pragma unroll
+        for (uint32_t k = 0; k < kResampleBlock; ++k) {
+            const int32_t r = r0 + (int32_t)k < t.rowHi ? r0 + (int32_t)k : t.rowHi - 1;
+            row[k] = a.in + (size_t)r * a.inPitch + x0;
+            acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0;
+        }
+        // four taps at a time through one 16-byte load per row and one 8-byte load of weights (both 4-byte aligned: a table
+        // row starts at an even number of weights), then the 1 .. 3 taps that remain one by one
+        uint32_t j = 0;
+        for (; j + 4u <= n; j += 4u) {
+            const ResampleWeights4 w4 = *reinterpret_cast<const ResampleWeights4 *>(w + j);
+            const int wj[4] = {(int)(int16_t)(w4.w[0] & 0xffffu), (int)w4.w[0] >> 16, (int)(int16_t)(w4.w[1] & 0xffffu), (int)w4.w[1] >> 16};
+#pragma unroll
+            for (uint32_t k = 0; k < kResampleBlock; ++k) {
+                const ResampleTexels4 t4 = *reinterpret_cast<const ResampleTexels4 *>(row[k] + (size_t)j * 4u);
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) resample_accumulate(acc[k], wj[i], t4.t[i]);
+            }
+        }
+        for (; j < n; ++j) {
+            const int wj = w[j];
+#pragma unroll
+            for (uint32_t k = 0; k < kResampleBlock; ++k)
+                resample_accumulate(acc[k], wj, *reinterpret_cast<const uint32_t *>(row[k] + (size_t)j * 4u));
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kResampleBlock; ++k) {
+            if (r0 + (int32_t)k >= t.rowHi) break;
+            ResampleWord h;
+            h.lo = ((uint32_t)((acc[k][0] + 128) >> 8) & 0xffffu) | ((uint32_t)((acc[k][1] + 128) >> 8) << 16);
+            h.hi = ((uint32_t)((acc[k][2] + 128) >> 8) & 0xffffu) | ((uint32_t)((acc[k][3] + 128) >> 8) << 16);
+            lds[(size_t)(r0 + (int32_t)k - t.rowLo) * kResampleColumns + c] = h;
+        }
+    }
+}
+
+// Phase 2 for thread (c, g): output rows q0 + g, q0 + g + 4, ... of column tileX * 64 + c.
+__host__ __device__ inline void resample_phase2(const ResampleArgs &a, uint32_t tileX, uint32_t tileY, uint32_t c, uint32_t g,
+                                                const ResampleWord *lds) {
+    const uint32_t p = tileX * kResampleColumns + c;
+    if (p >= a.outW) return;
+    const ResampleTile t = resample_tile(a, tileY);
+    for (uint32_t q = t.q0 + g; q < t.q1; q += kResampleGroups) {
+        const uint32_t n = a.y.count[q];
+        const int16_t *w = a.y.weights + (size_t)q * a.y.stride;
+        const ResampleWord *col = lds + (size_t)(a.y.first[q] - t.rowLo) * kResampleColumns + c;
+        int v[4] = {0, 0, 0, 0};
+        for (uint32_t j = 0; j < n; ++j) {
+            const int wj = w[j];
+            const ResampleWord h = col[(size_t)j * kResampleColumns];
+            v[0] += wj * (int)(int16_t)(h.lo & 0xffffu);
+            v[1] += wj * ((int)h.lo >> 16);
+            v[2] += wj * (int)(int16_t)(h.hi & 0xffffu);
+            v[3] += wj * ((int)h.hi >> 16);
+        }
+        const uint32_t px = (uint32_t)resample_byte(v[0]) | ((uint32_t)resample_byte(v[1]) << 8) | ((uint32_t)resample_byte(v[2]) << 16) |
+                            ((uint32_t)resample_byte(v[3]) << 24);
+        *reinterpret_cast<uint32_t *>(a.out + (size_t)q * a.outPitch + (size_t)p * 4u) = px;
+    }
+}
+
+}  // namespace lfg

@@ -42,7 +42,7 @@ struct Resources {
 }  // namespace
 
 bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeight, uint32_t outputWidth, uint32_t outputHeight,
-                   int frames, EvaluationResult& result, bool extrapolate) {
+                   int frames, EvaluationResult& result, bool extrapolate, int scaleFilter) {
     auto& fm = FrameManager::Get();
     if (!Ctx() || frames < 3) {
         LOG_ERROR("RunEvaluation: needs an initialized HipContext and at least 3 frames");
@@ -71,7 +71,8 @@ bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeigh
         if (lfg_ring_acquire(r.ring, &slotHost, &slot) != LFG_OK) { LOG_ERROR("Failed to acquire an upload slot"); return false; }
         if (!source.NextFrame(static_cast<uint8_t*>(slotHost))) { LOG_ERROR("Failed to capture frame"); return false; }
         lfg_frame in = r.input.AsAbi(), up = into.AsAbi();
-        if (lfg_ring_upload(r.ring, slot, &in) != LFG_OK || lfg_scale(Ctx(), &in, &up) != LFG_OK) {
+        if (lfg_ring_upload(r.ring, slot, &in) != LFG_OK ||
+            (scaleFilter < 0 ? lfg_scale(Ctx(), &in, &up) : lfg_resample(Ctx(), &in, &up, scaleFilter)) != LFG_OK) {
             LOG_ERROR("Failed to upload and upscale a frame: ", lfg_last_error(Ctx()));
             return false;
         }

@@ -22,5 +22,6 @@ struct EvaluationResult {
 // With `extrapolate` (the context then carries LFG_GENERATION_EXTRAPOLATE) pair k's frames 2k and 2k + 1 give the frame one interval
 // ahead, which "generated" compares with frame 2k + 2; "repeated" compares frame 2k + 1, the newest frame shown again, with it.
 // The same frames are read and the report has the same keys.
+// `scaleFilter` as ScalerConfig::scaleFilter: -1 upscales with lfg_scale, an lfg_filter with lfg_resample.
 bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeight, uint32_t outputWidth, uint32_t outputHeight,
-                   int frames, EvaluationResult& result, bool extrapolate = false);
+                   int frames, EvaluationResult& result, bool extrapolate = false, int scaleFilter = -1);

@@ -53,6 +53,10 @@ static void PrintUsage() {
               << "                           1..64: strength in 64ths of the classic 5-point kernel, each pixel kept within the range of\n"
               << "                           itself and its four neighbours).  Applied to a copy just before the read-back: motion, masks and\n"
               << "                           cut detection see the unsharpened frames.  --evaluate does not sharpen\n"
+              << "  --scale-filter F         Filter of the scale to the output size: reference (default: the reference's six Lanczos-3 taps at\n"
+              << "                           every ratio), or nearest, bilinear, catmull-rom, mitchell, lanczos2, lanczos3 -- these widen with\n"
+              << "                           the ratio where the output is smaller than the input (anti-aliased downscaling); at most 64 taps\n"
+              << "                           per sample, which Lanczos-3 reaches at 10.6 : 1\n"
               << "  --evaluate               Measure instead of presenting: source frames 0, 2, 4, ... are the stream, 1, 3, 5, ... are\n"
               << "                           held out; each pair's frame at 0.5 is generated under the options above and compared on the\n"
               << "                           GPU, at the output size, with the frame held out -- as is the pair's first frame, shown\n"
@@ -81,6 +85,9 @@ static void PrintUsage() {
               << "  --sync-present           Wait for each call's own frames (reference behaviour) instead of pipelining\n"
               << "  --quiet                  Only warnings and errors\n";
 }
+
+// --scale-filter: the names of LFG_FILTER_NEAREST .. LFG_FILTER_LANCZOS3, in the enum's order
+static const char* const kScaleFilterNames[6] = {"nearest", "bilinear", "catmull-rom", "mitchell", "lanczos2", "lanczos3"};
 
 int main(int argc, char* argv[]) {
     // (HIP's default of four hardware queues is one short of three lanes + a copy stream + a communication stream: streams that
@@ -173,6 +180,14 @@ int main(int argc, char* argv[]) {
             if (!end || end == argv[i] || *end != '\0' || v < 0 || v > 64) { LOG_ERROR("Invalid --sharpen (0 to 64)"); return 1; }
             config.sharpen = (uint32_t)v;
         }
+        else if (strcmp(argv[i], "--scale-filter") == 0 && i + 1 < argc) {
+            const char* m = argv[++i];
+            config.scaleFilter = -2;
+            if (strcmp(m, "reference") == 0) config.scaleFilter = -1;
+            for (int f = 0; f < 6; ++f)
+                if (strcmp(m, kScaleFilterNames[f]) == 0) config.scaleFilter = f;
+            if (config.scaleFilter == -2) { LOG_ERROR("Invalid --scale-filter (reference|nearest|bilinear|catmull-rom|mitchell|lanczos2|lanczos3)"); return 1; }
+        }
         else if (strcmp(argv[i], "--evaluate") == 0) evaluate = true;
         else if (strcmp(argv[i], "--frames") == 0 && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (strcmp(argv[i], "--device") == 0 && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -239,6 +254,18 @@ int main(int argc, char* argv[]) {
             return 2;
         }
     }
+    if (config.scaleFilter >= 0) {                              // before a context is made: the tables are a host function
+        for (int axis = 0; axis < 2; ++axis) {
+            const uint32_t in = axis ? config.inputHeight : config.inputWidth, out = axis ? config.outputHeight : config.outputWidth;
+            std::vector<int32_t> first(out);
+            std::vector<uint32_t> count(out);
+            std::vector<int16_t> weights((size_t)out * LFG_RESAMPLE_MAX_TAPS);
+            if (lfg_resample_taps(config.scaleFilter, in, out, first.data(), count.data(), weights.data()) != LFG_OK) {
+                LOG_ERROR("--scale-filter ", kScaleFilterNames[config.scaleFilter], " cannot scale ", in, " to ", out, " (more than 64 taps per sample)");
+                return 2;
+            }
+        }
+    }
     if (generation == LFG_GENERATION_EXTRAPOLATE) {            // before a context is made
         if (interpolator != LFG_INTERPOLATOR_COMPENSATED) { LOG_ERROR("--generation extrapolate needs --interpolator compensated"); return 2; }
         if (ranks > 0) { LOG_ERROR("--generation extrapolate cannot be combined with --ranks"); return 2; }
@@ -273,16 +300,18 @@ int main(int argc, char* argv[]) {
         else source = std::make_unique<SyntheticCapture>(stream);
         EvaluationResult result;
         const bool ok = RunEvaluation(*source, config.inputWidth, config.inputHeight, config.outputWidth, config.outputHeight, frames, result,
-                                      generation == LFG_GENERATION_EXTRAPOLATE);
+                                      generation == LFG_GENERATION_EXTRAPOLATE, config.scaleFilter);
         source.reset();
         FrameManager::Get().Cleanup();
         HipContext::Get().Cleanup();
         if (!ok) { LOG_ERROR("Evaluation failed: ", Logger::Get().GetLastError()); return 1; }
+        char filterField[48] = "";
+        if (config.scaleFilter >= 0) snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
         printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
                "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
-               "\"input_format\": \"rgba\", \"output_format\": \"rgba\", \"protect_static\": %d, "
+               "\"input_format\": \"rgba\", \"output_format\": \"rgba\", \"protect_static\": %d, %s"
                "\"note\": \"nothing is presented: every second source frame is held out and compared on the GPU\", \"evaluation\": %s}\n",
-               frames, (unsigned long long)result.pairs, result.seconds, presentNull ? "true" : "false", staticTolerance, result.json.c_str());
+               frames, (unsigned long long)result.pairs, result.seconds, presentNull ? "true" : "false", staticTolerance, filterField, result.json.c_str());
         return 0;
     }
     if (ranks > 0) {
@@ -348,13 +377,15 @@ int main(int argc, char* argv[]) {
     if (rawOut && rawOut != stdout) fclose(rawOut);
     char sharpenField[32] = "";
     if (config.sharpen > 0) snprintf(sharpenField, sizeof sharpenField, "\"sharpen\": %u, ", config.sharpen);
+    char filterField[48] = "";
+    if (config.scaleFilter >= 0) snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
-           "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, %s"
+           "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, %s%s"
            "\"note\": \"includes %s, PCIe upload and readback\"}\n",
            frames, (unsigned long long)presented, (unsigned long long)generated, (unsigned long long)cuts, sec, presented / sec,
            (unsigned long long)checksum, syncPresent ? "false" : "true", replay, presentNull ? "true" : "false", inFlight,
-           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance, sharpenField,
+           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance, sharpenField, filterField,
            replay > 0 ? "one memcpy per input frame into the staging slot" : "host frame synthesis");
     return 0;
 }

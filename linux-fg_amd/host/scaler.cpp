@@ -215,7 +215,8 @@ bool Scaler::ScaleFrame(const Frame& input, Frame& output) {
     LOG_DEBUG("ScaleFrame - Input: ", input.width, "x", input.height, " Output: ", output.width, "x", output.height);
     const lfg_frame in = input.AsAbi();
     lfg_frame out = output.AsAbi();
-    if (lfg_scale(Ctx(), &in, &out) != LFG_OK) {
+    const int rc = m_config.scaleFilter < 0 ? lfg_scale(Ctx(), &in, &out) : lfg_resample(Ctx(), &in, &out, m_config.scaleFilter);
+    if (rc != LFG_OK) {
         LOG_ERROR("Failed to submit scale kernel: ", lfg_last_error(Ctx()));
         return false;
     }
