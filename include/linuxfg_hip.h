@@ -465,6 +465,66 @@ int  lfg_extrapolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, 
 typedef enum lfg_generation { LFG_GENERATION_INTERPOLATE = 0, LFG_GENERATION_EXTRAPOLATE = 1 } lfg_generation;
 int  lfg_set_generation(lfg_context *ctx, int generation);
 
+/* Bidirectional motion-compensated interpolation, opt-in: lfg_interpolate_compensated with a second vector field, measured the
+ * other way, that checks the first and projects from prev's grid as well.  No reference counterpart.  Always in pixels and with
+ * the vectors' own signs: it does not depend on lfg_set_semantics.  All float arithmetic is fp32 without contraction; the
+ * predicates are integer arithmetic.
+ *   Fields: fwd is LFG_FORMAT_MV_S8X2 on curr's grid, as lfg_motion(prev, curr) writes it: prev(q + f) ~ curr(q).  bwd is on
+ *   prev's grid, as lfg_motion(curr, prev) writes it: curr(p + b) ~ prev(p).  Any byte values; components in [-128, 127].
+ *   confirmed_f(q), f = fwd(q): lfg_interpolate_compensated's match gate holds (sum over c of |curr(q)_c - prev(q + f)_c| <=
+ *   match_sad, prev outside the image read as 0); p = q + f lies inside the image; and with b = bwd(p), |f.x + b.x| + |f.y + b.y|
+ *   <= tolerance.
+ *   confirmed_b(p), b = bwd(p): the mirror image: sum over c of |prev(p)_c - curr(p + b)_c| <= match_sad, curr outside read as
+ *   0; q = p + b lies inside; |b.x + fwd(q).x| + |b.y + fwd(q).y| <= tolerance; and neither component of b is -128 (its negation
+ *   does not fit the vector word).
+ * lfg_motion_consistency is the vector half of the two predicates on its own, with no frames and no gate: out(q) = 255 when r = q
+ * + a(q) lies inside the image and |a(q).x + b(r).x| + |a(q).y + b(r).y| <= tolerance, otherwise 0; called with (fwd, bwd) it
+ * answers for curr's grid, with (bwd, fwd) for prev's: the occlusion map of a pair.  a, b MV_S8X2 of one size, 2-byte aligned; 0
+ * <= tolerance <= 64; out of the fields' size with pitch >= width, overlapping neither field (lfg_static_mask's rules); only
+ * the W bytes of each row are written.  One launch on the selected lane, no device memory kept, outside the stage timers.
+ *
+ * lfg_interpolate_compensated_bidirectional is lfg_interpolate_compensated's definition word for word, with these changes:
+ *   Forward projection: every q with confirmed_f(q) (not merely matched) projects as there: d = q + (floorf((float)f.x * s +
+ *   0.5f), likewise y), s = 1.0f - t; outside the image dropped, otherwise atomicMin of the key of (f.x, f.y) into K(d).
+ *   Backward projection, into the same K: every p with confirmed_b(p) projects to d = p + (floorf((float)b.x * t + 0.5f),
+ *   likewise y); outside dropped, otherwise atomicMin of the key of (-b.x, -b.y): the content of p moves by +b per interval, so
+ *   in fwd's convention it carries u = -b.  Near t = 0, where the forward displacement is nearly the whole vector and its
+ *   rounding leaves cracks between regions, the backward one is small, and the other way round.  The key order is total, so K
+ *   does not depend on scheduling or on which projection ran first.
+ *   Sampling at a non-hole: unchanged (u decoded from K(d), P, C, the taps, the inside rule, the mix, the store).
+ *   Holes: the walk, its 16-pixel reach, its direction order and the choice of u are unchanged.  With c = clamp(floor(C)) and p
+ *   = clamp(floor(P)): Cbad = confirmed_f(c) && fwd(c) != u (curr shows other, confirmed content there); Pbad = confirmed_b(p)
+ *   && -bwd(p) != u (prev does).  Cbad && !Pbad: the prev sample alone (the content is covered in curr).  Pbad && !Cbad: the curr
+ *   sample alone (revealed in curr).  In every other case the pixel goes on as a projected pixel: the inside rule, then the mix.
+ *   Hence t = 1 gives curr exactly and t = 0 gives prev exactly, for any fields, match_sad and tolerance: at t = 0 every
+ *   confirmed_b pixel projects onto itself, so a hole at d is not confirmed_b, Pbad is false, P = d and mixf(x, y, 0) is x; at t
+ *   = 1 the same holds with the roles exchanged.  (lfg_interpolate_compensated promises only the second.)
+ * Frames and errors: lfg_interpolate_compensated's rules, bwd held to fwd's (MV_S8X2 of the frames' size, 2-byte aligned, no
+ * output overlapping it); 0 <= tolerance <= 64.  Any violation returns LFG_ERR_INVALID before anything is enqueued, with a
+ * message latched.  Uses the lane's key image of lfg_interpolate_compensated and keeps no other device memory.  Enqueued on the
+ * selected lane (clear K, project forward, project backward, sample, per factor); timed under LFG_STAGE_INTERPOLATE.  _multi: 1
+ * <= count <= LFG_MAX_FACTORS, outs[i] for factors[i], each identical to the single call.  Not built: a masked
+ * (overlay-protected) variant, an extrapolating variant, both fields estimated in one pass over the pair. */
+int  lfg_motion_consistency(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, int tolerance, const lfg_mask *out);
+int  lfg_interpolate_compensated_bidirectional(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *fwd,
+                                               const lfg_frame *bwd, lfg_frame *out, float factor, int match_sad, int tolerance);
+int  lfg_interpolate_compensated_bidirectional_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
+                                                     const lfg_frame *fwd, const lfg_frame *bwd, lfg_frame *const *outs,
+                                                     const float *factors, uint32_t count, int match_sad, int tolerance);
+/* The bidirectional route of lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else).  -1 (default): off, every
+ * path enqueues what it did.  0 .. 64 takes effect when LFG_INTERPOLATOR_COMPENSATED and LFG_GENERATION_INTERPOLATE are selected
+ * and static protection is off: the selected estimator runs twice, (prev, curr) into the lane's vector temporary as before and
+ * (curr, prev) into a further temporary of the lane, made on demand and freed with the lane; with lfg_set_vector_refinement on,
+ * lfg_motion_refine runs on each, (prev, curr, fwd) and (curr, prev, bwd); cut detection runs on fwd as before; then
+ * lfg_interpolate_compensated_bidirectional[_multi] runs with this tolerance in the compensated interpolator's place.  This
+ * doubles the motion stage, the dominant cost: about 4.5 ms more per 4K pair with the pyramid.
+ * The setting is stored and has no effect
+ *   with LFG_INTERPOLATOR_SHADER selected;
+ *   with LFG_GENERATION_EXTRAPOLATE selected (an extrapolating variant is not built);
+ *   with lfg_set_static_protection on (a masked bidirectional route is not built: the masked interpolation runs as before).
+ * Any other value: LFG_ERR_INVALID and no change. */
+int  lfg_set_bidirectional(lfg_context *ctx, int tolerance);
+
 /* Per-pixel vector refinement, opt-in, between motion estimation and interpolation.  No reference counterpart.  Both
  * estimators give each pixel the vector of the 8 x 8 block around it, so near a moving edge a band of up to ~4 px takes the
  * other side's vector; this picks, for each pixel, the nearby vector that fits a small window around that pixel best.

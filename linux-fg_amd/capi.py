@@ -149,6 +149,11 @@ SIGNATURES = {
     "lfg_extrapolate_compensated": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
     "lfg_extrapolate_compensated_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
     "lfg_set_generation": (_i, [_vp, _i]),
+    "lfg_motion_consistency": (_i, [_vp, _FP, _FP, _i, ctypes.POINTER(Mask)]),
+    "lfg_interpolate_compensated_bidirectional": (_i, [_vp, _FP, _FP, _FP, _FP, _FP, ctypes.c_float, _i, _i]),
+    "lfg_interpolate_compensated_bidirectional_multi": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.POINTER(_FP),
+                                                             ctypes.POINTER(ctypes.c_float), _u32, _i, _i]),
+    "lfg_set_bidirectional": (_i, [_vp, _i]),
     "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_vector_refinement": (_i, [_vp, _i]),
     "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
@@ -578,6 +583,33 @@ class Context:
         """GENERATION_INTERPOLATE (default) or GENERATION_EXTRAPOLATE: with INTERPOLATOR_COMPENSATED, interpolate_frames[_multi]
         read each factor as an `ahead` and run the extrapolation in the compensated interpolation's place."""
         self._check(self.lib.lfg_set_generation(self.h, int(generation)), "lfg_set_generation")
+
+    def motion_consistency(self, a: Frame, b: Frame, tolerance: int, out: Mask):
+        """The forward-backward check (lfg_motion_consistency): out(q) = 255 where q + a(q) is inside and b there is -a(q)
+        within `tolerance` in L1, else 0.  (fwd, bwd) answers for curr's grid, (bwd, fwd) for prev's."""
+        self._check(self.lib.lfg_motion_consistency(self.h, ctypes.byref(a), ctypes.byref(b), int(tolerance), ctypes.byref(out)),
+                    "lfg_motion_consistency")
+
+    def interpolate_compensated_bidirectional(self, prev: Frame, curr: Frame, fwd: Frame, bwd: Frame, out: Frame, factor: float = 0.5,
+                                              match_sad: int = DEFAULT_MATCH_SAD, tolerance: int = 1):
+        """Bidirectional compensated interpolation (lfg_interpolate_compensated_bidirectional): fwd as motion(prev, curr) and
+        bwd as motion(curr, prev) write them; a vector projects only where the other field confirms it, from both grids."""
+        self._check(self.lib.lfg_interpolate_compensated_bidirectional(
+            self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(fwd), ctypes.byref(bwd), ctypes.byref(out), factor,
+            int(match_sad), int(tolerance)), "lfg_interpolate_compensated_bidirectional")
+
+    def interpolate_compensated_bidirectional_multi(self, prev: Frame, curr: Frame, fwd: Frame, bwd: Frame, outs, factors,
+                                                    match_sad: int = DEFAULT_MATCH_SAD, tolerance: int = 1):
+        """lfg_interpolate_compensated_bidirectional_multi: one generated frame per factor, each equal to the single call."""
+        po, pf, n = self._multi_args(outs, factors)
+        self._check(self.lib.lfg_interpolate_compensated_bidirectional_multi(
+            self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(fwd), ctypes.byref(bwd), po, pf, n, int(match_sad),
+            int(tolerance)), "lfg_interpolate_compensated_bidirectional_multi")
+
+    def set_bidirectional(self, tolerance: int):
+        """-1 (default): off.  0 .. 64: with INTERPOLATOR_COMPENSATED, GENERATION_INTERPOLATE and static protection off,
+        interpolate_frames[_multi] measure the pair both ways and run the bidirectional interpolation with this tolerance."""
+        self._check(self.lib.lfg_set_bidirectional(self.h, int(tolerance)), "lfg_set_bidirectional")
 
     def motion_refine(self, prev: Frame, curr: Frame, mv_in: Frame, mv_out: Frame, radius: int = 1):
         """Per-pixel vector refinement (lfg_motion_refine): each pixel takes, of the vectors of mv_in at it and 4 or 8 px

@@ -136,7 +136,7 @@ hipError_t sync_lanes(lfg_context *ctx) {
     return e;
 }
 
-// A frame the selected lane owns (mv_tmp, mv_refined, mid_tmp), at this size: kept while the size stays, made again when it
+// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, mid_tmp), at this size: kept while the size stays, made again when it
 // changes.  The test comes first because lfg_frame_destroy waits for every lane.  (frame_manager.cpp:226-230)
 int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, uint32_t format) {
     if (f.data && f.width == width && f.height == height) return LFG_OK;
@@ -479,7 +479,7 @@ namespace {
 void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
-    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mid_tmp})      // (lane_frame)
+    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.mid_tmp})      // (lane_frame)
         if (f->data && f->owned) (void)hipFree(f->data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
@@ -1129,19 +1129,31 @@ constexpr float kFramesSearchRadius = 16.0f;
 // The vectors the generated frames are made from, on the selected lane: the selected estimator's in mv_tmp, and with
 // lfg_set_vector_refinement their refinement in mv_refined.  The estimator is enqueued before mv_refined is made: making
 // a frame can wait for every lane.
+int frame_vectors_into(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame &estimated, lfg_frame &refined,
+                       const lfg_frame **vectors) {
+    int rc = lane_frame(ctx, estimated, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
+    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
+    rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &estimated, 2, 16, 2)
+                                                 : lfg_motion(ctx, prev, curr, &estimated, kFramesBlockSize, kFramesSearchRadius);
+    if (rc != LFG_OK) return rc;
+    *vectors = &estimated;
+    if (ctx->refine_radius < 0) return LFG_OK;
+    rc = lane_frame(ctx, refined, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
+    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create refined motion vectors frame");
+    *vectors = &refined;
+    return lfg_motion_refine(ctx, prev, curr, &estimated, &refined, ctx->refine_radius);
+}
+
 int frame_vectors(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame **vectors) {
     lfg_lane_state &cur = ctx->cur();
-    int rc = lane_frame(ctx, cur.mv_tmp, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
-    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
-    rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &cur.mv_tmp, 2, 16, 2)
-                                                 : lfg_motion(ctx, prev, curr, &cur.mv_tmp, kFramesBlockSize, kFramesSearchRadius);
-    if (rc != LFG_OK) return rc;
-    *vectors = &cur.mv_tmp;
-    if (ctx->refine_radius < 0) return LFG_OK;
-    rc = lane_frame(ctx, cur.mv_refined, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
-    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create refined motion vectors frame");
-    *vectors = &cur.mv_refined;
-    return lfg_motion_refine(ctx, prev, curr, &cur.mv_tmp, &cur.mv_refined, ctx->refine_radius);
+    return frame_vectors_into(ctx, prev, curr, cur.mv_tmp, cur.mv_refined, vectors);
+}
+
+// lfg_set_bidirectional's conditions: where they hold, compensated_frames measures the pair the other way too and runs the
+// bidirectional call in the compensated interpolator's place.
+bool bidirectional_applies(const lfg_context *ctx) {
+    return ctx->bidir_tolerance >= 0 && ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED &&
+           ctx->generation == LFG_GENERATION_INTERPOLATE && ctx->static_tolerance < 0;
 }
 
 int cut_fallback_check(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
@@ -1291,13 +1303,15 @@ bool mask_ok(const lfg_mask *m, const lfg_frame *like) {
     return m && m->data && m->width == like->width && m->height == like->height && m->pitch >= m->width;
 }
 
-// The three stages that project the vectors into the lane's key image: lfg_interpolate_compensated[_multi], with a mask
-// lfg_interpolate_compensated_masked[_multi], and lfg_extrapolate_compensated[_multi], whose factors are its `aheads`.
-enum class McKind { Plain, Masked, Extrapolate };
+// The four stages that project the vectors into the lane's key image: lfg_interpolate_compensated[_multi], with a mask
+// lfg_interpolate_compensated_masked[_multi], lfg_extrapolate_compensated[_multi], whose factors are its `aheads`, and
+// lfg_interpolate_compensated_bidirectional[_multi], whose mv is `fwd` and which alone takes `bwd` and `tolerance`.
+enum class McKind { Plain, Masked, Extrapolate, Bidirectional };
 
 int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_mask *mask, McKind kind,
-                    lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name) {
-    const bool masked = kind == McKind::Masked;
+                    lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name,
+                    const lfg_frame *bwd = nullptr, int tolerance = 0) {
+    const bool masked = kind == McKind::Masked, bidir = kind == McKind::Bidirectional;
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     const std::string n(name);
@@ -1312,13 +1326,17 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, n + ": match_sad must be in [0, 1020]");
     if (masked && !mask_ok(mask, curr))
         return fail(ctx, LFG_ERR_INVALID, n + ": mask must be non-NULL, of the frames' size, with pitch >= width");
+    if (bidir && (!frame_ok(bwd, LFG_FORMAT_MV_S8X2) || !same_size(curr, bwd) || bwd->pitch % 2u || (uintptr_t)bwd->data % 2u))
+        return fail(ctx, LFG_ERR_INVALID, n + ": bwd must be a non-empty, 2-byte aligned MV_S8X2 frame of the frames' size");
+    if (bidir && (tolerance < 0 || tolerance > 64)) return fail(ctx, LFG_ERR_INVALID, n + ": tolerance must be in [0, 64]");
     for (uint32_t i = 0; i < count; ++i) {
         const lfg_frame *o = outs[i];
         if (!frame_ok(o, LFG_FORMAT_RGBA8_UNORM) || !same_size(curr, o) || o->pitch % 4u || (uintptr_t)o->data % 4u)
             return fail(ctx, LFG_ERR_INVALID, n + ": bad output frame (NULL, empty, wrong format, size or alignment)");
         if (!std::isfinite(factors[i]) || factors[i] < 0.0f || factors[i] > 1.0f)
             return fail(ctx, LFG_ERR_INVALID, n + ": every factor must be a finite number in [0, 1]");
-        if (frames_overlap(o, prev) || frames_overlap(o, curr) || frames_overlap(o, mv) || (masked && mask_overlaps(mask, o)))
+        if (frames_overlap(o, prev) || frames_overlap(o, curr) || frames_overlap(o, mv) || (masked && mask_overlaps(mask, o)) ||
+            (bidir && frames_overlap(o, bwd)))
             return fail(ctx, LFG_ERR_INVALID, n + ": an output aliases an input");
         for (uint32_t j = 0; j < i; ++j)
             if (frames_overlap(outs[j], o)) return fail(ctx, LFG_ERR_INVALID, n + ": two outputs alias each other");
@@ -1332,6 +1350,8 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
         hipError_t e = masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys)
                        : kind == McKind::Extrapolate
                               ? lfg::launch_extrapolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys)
+                       : bidir ? lfg::launch_interpolate_compensated_bidirectional(cur.stream, *prev, *curr, *mv, *bwd, *outs[i], factors[i],
+                                                                                   match_sad, tolerance, cur.mc_keys)
                               : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
         if (e != hipSuccess) return fail_hip(ctx, e, kind == McKind::Extrapolate ? "compensated extrapolate kernel launch" : "compensated interpolate kernel launch");
     }
@@ -1340,12 +1360,22 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
 
 // The compensated interpolation of lfg_interpolate_frames[_multi]: as it is, or with lfg_set_static_protection on the pair's
 // static mask into the lane's temporary and the masked call in its place; under LFG_GENERATION_EXTRAPOLATE the extrapolation
-// in the place of both.
+// in the place of both.  Where lfg_set_bidirectional applies: the pair measured the other way as `vectors` were measured, into the
+// lane's backward temporaries, and the bidirectional call in the compensated one's place.
 int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *vectors,
                        lfg_frame *const *outs, const float *factors, uint32_t count, bool multi) {
     if (ctx->generation == LFG_GENERATION_EXTRAPOLATE)             // each factor is an `ahead`; static protection does not apply
         return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Extrapolate, outs, factors, count, ctx->match_sad,
                                multi ? "lfg_extrapolate_compensated_multi" : "lfg_extrapolate_compensated");
+    if (bidirectional_applies(ctx)) {
+        lfg_lane_state &cur = ctx->cur();
+        const lfg_frame *backward = nullptr;
+        const int rc = frame_vectors_into(ctx, curr, prev, cur.mv_bwd, cur.mv_bwd_refined, &backward);
+        if (rc != LFG_OK) return rc;
+        return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Bidirectional, outs, factors, count, ctx->match_sad,
+                               multi ? "lfg_interpolate_compensated_bidirectional_multi" : "lfg_interpolate_compensated_bidirectional",
+                               backward, ctx->bidir_tolerance);
+    }
     if (ctx->static_tolerance < 0)
         return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Plain, outs, factors, count, ctx->match_sad,
                                multi ? "lfg_interpolate_compensated_multi" : "lfg_interpolate_compensated");
@@ -1392,6 +1422,49 @@ LFG_EXPORT int lfg_set_generation(lfg_context *ctx, int generation) {
     if (generation != LFG_GENERATION_INTERPOLATE && generation != LFG_GENERATION_EXTRAPOLATE)
         return fail(ctx, LFG_ERR_INVALID, "lfg_set_generation: unknown generation");
     ctx->generation = generation;
+    return LFG_OK;
+}
+
+// ---- bidirectional compensated interpolation (interpolate_bidir.hip)
+
+LFG_EXPORT int lfg_interpolate_compensated_bidirectional(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
+                                                         const lfg_frame *fwd, const lfg_frame *bwd, lfg_frame *out, float factor,
+                                                         int match_sad, int tolerance) {
+    lfg_frame *const outs[1] = {out};
+    return compensated_run(ctx, prev, curr, fwd, nullptr, McKind::Bidirectional, outs, &factor, 1, match_sad,
+                           "lfg_interpolate_compensated_bidirectional", bwd, tolerance);
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_bidirectional_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
+                                                               const lfg_frame *fwd, const lfg_frame *bwd, lfg_frame *const *outs,
+                                                               const float *factors, uint32_t count, int match_sad, int tolerance) {
+    return compensated_run(ctx, prev, curr, fwd, nullptr, McKind::Bidirectional, outs, factors, count, match_sad,
+                           "lfg_interpolate_compensated_bidirectional_multi", bwd, tolerance);
+}
+
+LFG_EXPORT int lfg_motion_consistency(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, int tolerance, const lfg_mask *out) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(a, LFG_FORMAT_MV_S8X2) || !frame_ok(b, LFG_FORMAT_MV_S8X2))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_consistency: a and b must be non-empty MV_S8X2");
+    if (!same_size(a, b)) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_consistency: a and b differ in size");
+    if ((a->pitch | b->pitch) % 2u || ((uintptr_t)a->data | (uintptr_t)b->data) % 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_consistency: MV_S8X2 frames must be 2-byte aligned");
+    if (tolerance < 0 || tolerance > 64) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_consistency: tolerance must be in [0, 64]");
+    if (!mask_ok(out, a))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_consistency: out must be non-NULL, of the fields' size, with pitch >= width");
+    if (mask_overlaps(out, a) || mask_overlaps(out, b))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_consistency: out overlaps an input");
+    hipError_t e = lfg::launch_motion_consistency(ctx->cur().stream, *a, *b, tolerance, *out);
+    if (e != hipSuccess) return fail_hip(ctx, e, "motion consistency kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_set_bidirectional(lfg_context *ctx, int tolerance) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (tolerance < -1 || tolerance > 64)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_bidirectional: tolerance must be -1 (off) or in [0, 64]");
+    ctx->bidir_tolerance = tolerance;
     return LFG_OK;
 }
 

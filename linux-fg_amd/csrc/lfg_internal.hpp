@@ -176,6 +176,7 @@ struct lfg_lane_state {
     hipStream_t own_stream = nullptr, stream = nullptr;
     lfg_frame mv_tmp{};                        // temporary of lfg_interpolate_frames
     lfg_frame mv_refined{};                    // ... and its refined vectors (lfg_set_vector_refinement), made on demand
+    lfg_frame mv_bwd{}, mv_bwd_refined{};      // ... and the same two measured from curr to prev (lfg_set_bidirectional), made on demand
     lfg_frame mid_tmp{};                       // temporary of lfg_interpolate_scale where the fused kernel does not apply
     // prefiltered motion path: scratch for one frame size, grown on demand
     uint8_t *motion_ws = nullptr;
@@ -224,6 +225,7 @@ struct lfg_context {
     int cut_permille = -1;                     // lfg_interpolate_frames[_multi]: lfg_cut_fallback's threshold, -1 = off (lfg_set_cut_detection)
     int static_tolerance = -1;                 // lfg_interpolate_frames[_multi]: lfg_static_mask's tolerance, -1 = off (lfg_set_static_protection)
     int generation = 0;                        // lfg_interpolate_frames[_multi]: LFG_GENERATION_INTERPOLATE / _EXTRAPOLATE (lfg_set_generation)
+    int bidir_tolerance = -1;                  // lfg_interpolate_frames[_multi]: the bidirectional route's tolerance, -1 = off (lfg_set_bidirectional)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -333,6 +335,12 @@ hipError_t launch_static_mask(hipStream_t s, const lfg_frame &prev, const lfg_fr
 // Motion-compensated extrapolation (extrapolate_mc.hip): clears `keys` (W * H words), projects past time 1, samples curr; one factor.
 hipError_t launch_extrapolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                           const lfg_frame &out, float ahead, int matchSad, uint32_t *keys);
+// Bidirectional compensated interpolation (interpolate_bidir.hip): clears `keys` (W * H words), projects both fields, samples; one
+// factor.  And the forward-backward check of field `a` against field `b` on its own: one launch.
+hipError_t launch_interpolate_compensated_bidirectional(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &fwd,
+                                                        const lfg_frame &bwd, const lfg_frame &out, float factor, int matchSad,
+                                                        int tolerance, uint32_t *keys);
+hipError_t launch_motion_consistency(hipStream_t s, const lfg_frame &a, const lfg_frame &b, int tolerance, const lfg_mask &out);
 // Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
                                 const lfg_frame &mvOut, int radius);

@@ -29,6 +29,14 @@ bool FrameManager::SetGeneration(int generation) {
     return true;
 }
 
+bool FrameManager::SetBidirectional(int tolerance) {
+    if (lfg_set_bidirectional(Ctx(), tolerance) != LFG_OK) {
+        LOG_ERROR("Failed to set the bidirectional tolerance: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
+        return false;
+    }
+    return true;
+}
+
 bool FrameManager::CreateFrame(Frame& frame, uint32_t width, uint32_t height) {
     lfg_frame f{};
     const uint32_t format = frame.format;                    // RGBA8 unless the caller asked otherwise

@@ -71,6 +71,11 @@ public:
     // interpolator selected on the device context; the reference has no such mode).
     bool SetGeneration(int generation);
 
+    // The bidirectional route of the four calls above (lfg_set_bidirectional): -1 (default) off; 0 .. 64, with the compensated
+    // interpolator, interpolation and no static protection selected on the device context, the pair is measured both ways and a
+    // vector projects only where the two fields agree within `tolerance` (the reference has no such mode).
+    bool SetBidirectional(int tolerance);
+
     // The one exchange of the multi-GPU path: broadcast a frame from rank `root` to every rank (asynchronous, on the
     // device context's communication stream) and make later work on the compute queue wait for it.
     bool BroadcastFrame(Frame& frame, int root);
