@@ -1,6 +1,8 @@
 /* CPU model of lfg_interpolate_compensated_bidirectional and lfg_motion_consistency (include/linuxfg_hip.h): the two
  * `confirmed` predicates, both projections, the hole fill, the symmetric hole rule and the sampling, in the header's fp32
- * operation order.  Built with the system C compiler and -ffp-contract=off by tests/bidir_model.py.
+ * operation order.  Built with the system C compiler and -ffp-contract=off by tests/bidir_model.py.  The library's helpers,
+ * the gate, the key, the hole walk and the end of the sampling are tests/compensated_model.h's, shared with the family's
+ * other models; this file holds the predicates, the two projections and the symmetric hole rule.
  *
  * Frames are tight: prev / curr / out RGBA8 rows of W * 4 bytes, fwd / bwd int8 (x, y) pairs in rows of W * 2 bytes, masks rows
  * of W bytes.
@@ -13,38 +15,7 @@
  *   BIDIR_MUTANT_NEG128_AS_127  a backward vector with a component of -128 is not refused: the component is carried as 127;
  *   BIDIR_MUTANT_CHEBYSHEV      the tolerance bounds max(|dx|, |dy|) instead of |dx| + |dy|;
  *   BIDIR_MUTANT_STRICT         `<` for `<=` in the tolerance. */
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#define HOLE 0xFFFFFFFFu
-#define WALK 16
-
-typedef struct { float x, y, z, w; } vec4;
-
-/* the library's own helpers, restated as tests/mc_model.c restates them */
-static inline float unorm(uint8_t b) { return (float)b / 255.0f; }
-
-static inline uint8_t pack_unorm(float v) {
-    float x = v * 255.0f;
-    if (!(x > 0.0f)) x = 0.0f;
-    if (x > 255.0f) x = 255.0f;
-    return (uint8_t)lrintf(x);
-}
-
-static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-static inline float mixf(float x, float y, float a) { return x * (1.0f - a) + y * a; }
-
-static inline uint32_t texel_sad(const uint8_t *a, const uint8_t *b) {
-    uint32_t s = 0;
-    for (int c = 0; c < 4; ++c) s += (uint32_t)abs((int)a[c] - (int)b[c]);
-    return s;
-}
-
-static inline uint32_t key_of(int vx, int vy) {
-    return ((uint32_t)(65535 - (vx * vx + vy * vy)) << 16) | ((uint32_t)(vy + 128) << 8) | (uint32_t)(vx + 128);
-}
+#include "compensated_model.h"
 
 /* r = q + a(q) inside the image and the other field there within the tolerance of -a(q) */
 static int consistent(const int8_t *a, const int8_t *b, int W, int H, int qx, int qy, int tolerance) {
@@ -59,14 +30,6 @@ static int consistent(const int8_t *a, const int8_t *b, int W, int H, int qx, in
 #else
     return ex + ey <= tolerance;
 #endif
-}
-
-/* the gate of `own`'s pixel q against `far` at q + a(q), far outside the image read as 0 */
-static int gate(const uint8_t *own, const uint8_t *far, const int8_t *a, int W, int H, int qx, int qy, int match_sad) {
-    static const uint8_t zero[4] = {0, 0, 0, 0};
-    const int sx = qx + a[((size_t)qy * W + qx) * 2], sy = qy + a[((size_t)qy * W + qx) * 2 + 1];
-    const uint8_t *p = (sx >= 0 && sx < W && sy >= 0 && sy < H) ? far + ((size_t)sy * W + sx) * 4 : zero;
-    return texel_sad(own + ((size_t)qy * W + qx) * 4, p) <= (uint32_t)match_sad;
 }
 
 static int confirmed_f(const uint8_t *prev, const uint8_t *curr, const int8_t *fwd, const int8_t *bwd, int W, int H, int qx, int qy,
@@ -118,53 +81,6 @@ void bidir_project(const uint8_t *prev, const uint8_t *curr, const int8_t *fwd, 
         }
 }
 
-/* texture() with CLAMP_TO_EDGE, in pixel units: (px, py) is a position with texel centres at i + 0.5 */
-static vec4 bilinear_px(const uint8_t *img, int W, int H, float px, float py) {
-    const float u = px - 0.5f, v = py - 0.5f;
-    const float fu = floorf(u), fv = floorf(v);
-    const float a = u - fu, b = v - fv;
-    const int i0 = clampi((int)fu, 0, W - 1), i1 = clampi((int)fu + 1, 0, W - 1);
-    const int j0 = clampi((int)fv, 0, H - 1), j1 = clampi((int)fv + 1, 0, H - 1);
-    const float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
-    const uint8_t *t00 = img + ((size_t)j0 * W + i0) * 4, *t10 = img + ((size_t)j0 * W + i1) * 4;
-    const uint8_t *t01 = img + ((size_t)j1 * W + i0) * 4, *t11 = img + ((size_t)j1 * W + i1) * 4;
-    float r[4];
-    for (int c = 0; c < 4; ++c)
-        r[c] = ((w00 * unorm(t00[c]) + w10 * unorm(t10[c])) + w01 * unorm(t01[c])) + w11 * unorm(t11[c]);
-    vec4 o = {r[0], r[1], r[2], r[3]};
-    return o;
-}
-
-static inline int inside(float x, float y, int W, int H) { return x >= 0.0f && x <= (float)W && y >= 0.0f && y <= (float)H; }
-
-static inline void store(uint8_t *o, vec4 v) {
-    o[0] = pack_unorm(v.x); o[1] = pack_unorm(v.y); o[2] = pack_unorm(v.z); o[3] = pack_unorm(v.w);
-}
-
-static inline void decode(uint32_t key, int *ux, int *uy) {
-    *ux = (int)(key & 0xffu) - 128;
-    *uy = (int)((key >> 8) & 0xffu) - 128;
-}
-
-/* The fill vector of hole (x, y): of the first non-hole pixel in each axis direction within WALK, the smallest
- * (|v|^2, vy, vx); (0, 0) if there is none. */
-static void fill_vector(const uint32_t *K, int W, int H, int x, int y, int *ux, int *uy) {
-    static const int dir[4][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}};
-    uint32_t best = HOLE;                                      /* (|v|^2 << 16) | (vy + 128) << 8 | (vx + 128) */
-    for (int k = 0; k < 4; ++k)
-        for (int j = 1; j <= WALK; ++j) {
-            const int nx = x + dir[k][0] * j, ny = y + dir[k][1] * j;
-            if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
-            const uint32_t key = K[(size_t)ny * W + nx];
-            if (key == HOLE) continue;
-            const uint32_t order = ((65535u - (key >> 16)) << 16) | (key & 0xffffu);
-            if (order < best) best = order;
-            break;
-        }
-    if (best == HOLE) { *ux = 0; *uy = 0; return; }
-    decode(best, ux, uy);
-}
-
 void bidir_sample(const uint8_t *prev, const uint8_t *curr, const int8_t *fwd, const int8_t *bwd, const uint32_t *K, int W, int H,
                   float t, int match_sad, int tolerance, int x0, int y0, int x1, int y1, uint8_t *out) {
     const float s = 1.0f - t;
@@ -189,12 +105,6 @@ void bidir_sample(const uint8_t *prev, const uint8_t *curr, const int8_t *fwd, c
                 if (cbad && !pbad) { store(o, Pv); continue; }                                        /* covered in curr */
                 if (pbad && !cbad) { store(o, Cv); continue; }                                        /* revealed in curr */
             }
-            const int pin = inside(Px, Py, W, H), cin = inside(Cx, Cy, W, H);
-            if (pin && !cin) store(o, Pv);
-            else if (cin && !pin) store(o, Cv);
-            else {
-                const vec4 m = {mixf(Pv.x, Cv.x, t), mixf(Pv.y, Cv.y, t), mixf(Pv.z, Cv.z, t), mixf(Pv.w, Cv.w, t)};
-                store(o, m);
-            }
+            store_inside_or_blend(o, Pv, Cv, Px, Py, Cx, Cy, W, H, t);
         }
 }

@@ -1,7 +1,7 @@
 """CPU model of lfg_interpolate_compensated_bidirectional and lfg_motion_consistency (include/linuxfg_hip.h): the forward-backward
 check, the two `confirmed` predicates, both projections, the hole fill with its symmetric revealed / covered rule and the
 sampling, in the header's fp32 operation order.  The loops are C (tests/bidir_model.c, built here with the system C compiler and
--ffp-contract=off on first use).
+-ffp-contract=off on first use); what this wrapper shares with the family's other three is in tests/c_model.py.
 
 ``consistency(a, b, tolerance)`` is lfg_motion_consistency's mask.  ``keys(prev, curr, fwd, bwd, t, ...)`` is the key image of
 both projections (``which`` = "forward" / "backward" for one alone), ``sample(..., K, ...)`` the sampling step from any key
@@ -9,32 +9,21 @@ image, and ``interpolate_bidirectional(...)`` the whole frame, or with ``roi=(x,
 projections still cover the whole frame)."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
-from tests.c_model import frames_and_vectors as _inputs, load, ptr as _ptr
+from tests.c_model import DEFAULT_MATCH_SAD, HOLE          # public names of this module too
+from tests.c_model import F, I, VP, frames_and_vectors as _inputs, mutant_loader, plane as _plane, ptr as _ptr
+from tests.c_model import sampling as _sampling
 
-_VP, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_SIGNATURES = {"bidir_consistency": [_VP, _VP, _I, _I, _I, _VP],
-               "bidir_project": [_VP, _VP, _VP, _VP, _I, _I, _F, _I, _I, _I, _VP],
-               "bidir_sample": [_VP, _VP, _VP, _VP, _VP, _I, _I, _F, _I, _I, _I, _I, _I, _I, _VP]}
-
-HOLE = 0xFFFFFFFF
-DEFAULT_MATCH_SAD = 48
 MUTANTS = ("NEG128_AS_127", "CHEBYSHEV", "STRICT")   # bidir_model.c: what a case of test_bidir_model.py must tell from the model
 _WHICH = {"forward": 1, "backward": 2, "both": 3}
-
-
-def _load(mutant=None):
-    assert mutant is None or mutant in MUTANTS, mutant
-    return load("bidir_model", _SIGNATURES, ["-ffp-contract=off"] + ([f"-DBIDIR_MUTANT_{mutant}"] if mutant else []), ["-lm"])
+_load = mutant_loader("bidir_model", {"bidir_consistency": [VP, VP, I, I, I, VP],
+                                      "bidir_project": [VP, VP, VP, VP, I, I, F, I, I, I, VP],
+                                      "bidir_sample": [VP, VP, VP, VP, VP, I, I, F, I, I, I, I, I, I, VP]}, "BIDIR_MUTANT_", MUTANTS)
 
 
 def _field(v, shape):
-    v = np.ascontiguousarray(np.asarray(v).astype(np.int8, copy=False))
-    assert v.shape == shape + (2,), (v.shape, shape)
-    return v
+    return _plane(v, np.int8, tuple(shape) + (2,))
 
 
 def consistency(a: np.ndarray, b: np.ndarray, tolerance: int, mutant=None) -> np.ndarray:
@@ -65,12 +54,9 @@ def sample(prev, curr, fwd, bwd, K, t: float, match_sad: int = DEFAULT_MATCH_SAD
     prev, curr, fwd = _inputs(prev, curr, fwd)
     bwd = _field(bwd, prev.shape[:2])
     H, W = prev.shape[:2]
-    K = np.ascontiguousarray(K, np.uint32)
-    assert K.shape == (H, W)
-    x, y, w, h = roi if roi is not None else (0, 0, W, H)
-    out = np.empty((h, w, 4), np.uint8)
+    K, rect, out = _sampling(K, H, W, roi)
     _load(mutant).bidir_sample(_ptr(prev), _ptr(curr), _ptr(fwd), _ptr(bwd), _ptr(K), W, H, float(t), int(match_sad),
-                               int(tolerance), x, y, x + w, y + h, _ptr(out))
+                               int(tolerance), *rect, _ptr(out))
     return out
 
 

@@ -1,38 +1,23 @@
 """CPU model of lfg_extrapolate_compensated (include/linuxfg_hip.h): the match gate, the projection of curr's vectors past
 time 1, the hole walk with its donor rule and the sampling of curr, in the header's fp32 operation order.  The loops are C
-(tests/extrapolate_model.c, built here with the system C compiler and -ffp-contract=off on first use).
+(tests/extrapolate_model.c, built here with the system C compiler and -ffp-contract=off on first use); what this wrapper
+shares with the family's other three is in tests/c_model.py.
 
 ``extrapolate(prev, curr, mv, a, match_sad)`` gives the whole frame; ``..., roi=(x, y, w, h)`` only the ROI's pixels (the
 projection still covers the whole frame: any source pixel may land in the ROI).  ``keys(...)`` is the projected key image
 itself, ``sample(..., K, ...)`` the sampling step from any key image, and ``branches(...)`` says how each pixel was made."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
-from tests.c_model import frames_and_vectors as _inputs, load, ptr as _ptr
+from tests.c_model import DEFAULT_MATCH_SAD, HOLE, key     # public names of this module too
+from tests.c_model import F, I, VP, frames_and_vectors as _inputs, mutant_loader, ptr as _ptr, sampling as _sampling
 
-_VP, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_SIGNATURES = {"ex_project": [_VP, _VP, _VP, _I, _I, _F, _I, _VP],
-               "ex_sample": [_VP, _VP, _VP, _VP, _I, _I, _F, _I, _I, _I, _I, _I, _VP, _VP]}
-
-HOLE = 0xFFFFFFFF
-DEFAULT_MATCH_SAD = 48
 PROJECTED, NO_DONOR, DONOR_KEPT, DONOR_TAKEN = 0, 1, 2, 3      # branches(): how a pixel was made
 # extrapolate_model.c: what the shared cases (tests/extrapolate_cases.py) must tell from the model
 MUTANTS = ("PLUS_V", "CEIL_PROJECT", "ONE_MINUS_A", "NO_DONOR", "LATER_TIE")
-
-
-def _load(mutant=None):
-    """The model, or with mutant = one of MUTANTS the model built with -DEX_MUTANT_<mutant>, under a cache name of its own."""
-    assert mutant is None or mutant in MUTANTS, mutant
-    return load("extrapolate_model", _SIGNATURES, ["-ffp-contract=off"] + ([f"-DEX_MUTANT_{mutant}"] if mutant else []), ["-lm"])
-
-
-def key(vx: int, vy: int) -> int:
-    """A vector's projection key: the smallest key wins (longest vector, then smallest vy, then smallest vx)."""
-    return ((65535 - (vx * vx + vy * vy)) << 16) | ((vy + 128) << 8) | (vx + 128)
+_load = mutant_loader("extrapolate_model", {"ex_project": [VP, VP, VP, I, I, F, I, VP],
+                                            "ex_sample": [VP, VP, VP, VP, I, I, F, I, I, I, I, I, VP, VP]}, "EX_MUTANT_", MUTANTS)
 
 
 def keys(prev, curr, mv, a: float, match_sad: int = DEFAULT_MATCH_SAD, mutant=None) -> np.ndarray:
@@ -47,12 +32,9 @@ def keys(prev, curr, mv, a: float, match_sad: int = DEFAULT_MATCH_SAD, mutant=No
 def _sample(prev, curr, mv, K, a, match_sad, roi, mutant):
     prev, curr, mv = _inputs(prev, curr, mv)
     H, W = prev.shape[:2]
-    K = np.ascontiguousarray(K, np.uint32)
-    assert K.shape == (H, W)
-    x, y, w, h = roi if roi is not None else (0, 0, W, H)
-    out, how = np.empty((h, w, 4), np.uint8), np.empty((h, w), np.uint8)
-    _load(mutant).ex_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(a), int(match_sad), x, y, x + w, y + h,
-                            _ptr(out), _ptr(how))
+    K, rect, out = _sampling(K, H, W, roi)
+    how = np.empty(out.shape[:2], np.uint8)
+    _load(mutant).ex_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(a), int(match_sad), *rect, _ptr(out), _ptr(how))
     return out, how
 
 

@@ -1,36 +1,21 @@
 """CPU model of lfg_interpolate_compensated (include/linuxfg_hip.h): the match gate, the projection of the vectors to time t,
 the hole fill and the sampling, in the header's fp32 operation order.  The loops are C (tests/mc_model.c, built here with
-the system C compiler and -ffp-contract=off on first use).
+the system C compiler and -ffp-contract=off on first use); what this wrapper shares with the family's other three is in
+tests/c_model.py.
 
 ``interpolate_compensated(prev, curr, mv, t, match_sad)`` gives the whole frame; ``..., roi=(x, y, w, h)`` only the ROI's
 pixels (the projection still covers the whole frame: any source pixel may land in the ROI), so ROIs of a 4K or 8K frame are
 cheap.  ``keys(...)`` is the projected key image itself, and ``sample(..., K, ...)`` the sampling step from any key image."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
-from tests.c_model import frames_and_vectors as _inputs, load, ptr as _ptr
+from tests.c_model import DEFAULT_MATCH_SAD, HOLE, key     # public names of this module too
+from tests.c_model import F, I, VP, frames_and_vectors as _inputs, mutant_loader, ptr as _ptr, sampling as _sampling
 
-_VP, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_SIGNATURES = {"mc_project": [_VP, _VP, _VP, _I, _I, _F, _I, _VP],
-               "mc_sample": [_VP, _VP, _VP, _VP, _I, _I, _F, _I, _I, _I, _I, _I, _VP]}
-
-HOLE = 0xFFFFFFFF
-DEFAULT_MATCH_SAD = 48
 MUTANTS = ("C_FROM_P", "CEIL_PROJECT", "HALF_LAST")     # mc_model.c: rewrites that a test's factors must tell from the model
-
-
-def _load(mutant=None):
-    """The model, or with mutant = one of MUTANTS the model built with -DMC_MUTANT_<mutant>, under a cache name of its own."""
-    assert mutant is None or mutant in MUTANTS, mutant
-    return load("mc_model", _SIGNATURES, ["-ffp-contract=off"] + ([f"-DMC_MUTANT_{mutant}"] if mutant else []), ["-lm"])
-
-
-def key(vx: int, vy: int) -> int:
-    """A vector's projection key: the smallest key wins (longest vector, then smallest vy, then smallest vx)."""
-    return ((65535 - (vx * vx + vy * vy)) << 16) | ((vy + 128) << 8) | (vx + 128)
+_load = mutant_loader("mc_model", {"mc_project": [VP, VP, VP, I, I, F, I, VP],
+                                   "mc_sample": [VP, VP, VP, VP, I, I, F, I, I, I, I, I, VP]}, "MC_MUTANT_", MUTANTS)
 
 
 def keys(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, t: float, match_sad: int = DEFAULT_MATCH_SAD,
@@ -54,11 +39,8 @@ def sample(prev: np.ndarray, curr: np.ndarray, mv: np.ndarray, K: np.ndarray, t:
     """The sampling step alone, from a key image K (H, W) uint32 given by the caller: lets a test place keys and holes."""
     prev, curr, mv = _inputs(prev, curr, mv)
     H, W = prev.shape[:2]
-    K = np.ascontiguousarray(K, np.uint32)
-    assert K.shape == (H, W)
-    x, y, w, h = roi if roi is not None else (0, 0, W, H)
-    out = np.empty((h, w, 4), np.uint8)
-    _load(mutant).mc_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(t), int(match_sad), x, y, x + w, y + h, _ptr(out))
+    K, rect, out = _sampling(K, H, W, roi)
+    _load(mutant).mc_sample(_ptr(prev), _ptr(curr), _ptr(mv), _ptr(K), W, H, float(t), int(match_sad), *rect, _ptr(out))
     return out
 
 

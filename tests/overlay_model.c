@@ -1,6 +1,8 @@
 /* CPU model of lfg_interpolate_compensated_masked (include/linuxfg_hip.h): lfg_interpolate_compensated with a static mask,
- * in the header's fp32 operation order and in mc_model.c's style.  Built with the system C compiler and -ffp-contract=off by
- * tests/overlay_model.py.  With an all-zero mask every step below is mc_model.c's (tests/test_overlay_model.py holds the two
+ * in the header's fp32 operation order.  Built with the system C compiler and -ffp-contract=off by tests/overlay_model.py.
+ * The library's helpers, the gate, the key and the end of the sampling are tests/compensated_model.h's, shared with the
+ * family's other models; this file holds the projection with its static key, the walk that passes static pixels, the fetch
+ * rule and the hole rule.  With an all-zero mask every step below is mc_model.c's (tests/test_overlay_model.py holds the two
  * to each other byte for byte).
  *
  * Frames are tight: prev / curr / out RGBA8 rows of W * 4 bytes, mv int8 (x, y) pairs in rows of W * 2 bytes, mask rows of W
@@ -16,43 +18,9 @@
  *   OV_MUTANT_RULE_AFTER_HOLE  the fetch rule tested after the hole's revealed / covered test instead of before it;
  *   OV_MUTANT_RULE_LRINT       the fetch rule's p and c from lrintf instead of floorf;
  *   OV_MUTANT_STATIC_CURR      a static location's output as curr(d) instead of mix(prev(d), curr(d), t). */
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
+#include "compensated_model.h"
 
-#define HOLE 0xFFFFFFFFu
 #define STATIC 0u
-#define WALK 16
-
-typedef struct { float x, y, z, w; } vec4;
-
-static inline float unorm(uint8_t b) { return (float)b / 255.0f; }
-
-static inline uint8_t pack_unorm(float v) {
-    float x = v * 255.0f;
-    if (!(x > 0.0f)) x = 0.0f;
-    if (x > 255.0f) x = 255.0f;
-    return (uint8_t)lrintf(x);
-}
-
-static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-static inline float mixf(float x, float y, float a) { return x * (1.0f - a) + y * a; }
-
-static inline uint32_t texel_sad(const uint8_t *a, const uint8_t *b) {
-    uint32_t s = 0;
-    for (int c = 0; c < 4; ++c) s += (uint32_t)abs((int)a[c] - (int)b[c]);
-    return s;
-}
-
-/* the gate: curr(q) against prev(q + mv(q)), prev outside the image read as 0 */
-static int matched(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, int W, int H, int qx, int qy, int match_sad) {
-    static const uint8_t zero[4] = {0, 0, 0, 0};
-    const int8_t *v = mv + ((size_t)qy * W + qx) * 2;
-    const int sx = qx + v[0], sy = qy + v[1];
-    const uint8_t *p = (sx >= 0 && sx < W && sy >= 0 && sy < H) ? prev + ((size_t)sy * W + sx) * 4 : zero;
-    return texel_sad(curr + ((size_t)qy * W + qx) * 4, p) <= (uint32_t)match_sad;
-}
 
 void ov_project(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, const uint8_t *mask, int W, int H, float t,
                 int match_sad, uint32_t *K) {
@@ -71,44 +39,16 @@ void ov_project(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, cons
             const int dx = (int)floorf((float)vx * s + 0.5f), dy = (int)floorf((float)vy * s + 0.5f);
             const int x = qx + dx, y = qy + dy;
             if (x < 0 || x >= W || y < 0 || y >= H) continue;
-            const uint32_t key = ((uint32_t)(65535 - (vx * vx + vy * vy)) << 16) | ((uint32_t)(vy + 128) << 8) | (uint32_t)(vx + 128);
-            if (key < K[(size_t)y * W + x]) K[(size_t)y * W + x] = key;
+            if (key_of(vx, vy) < K[(size_t)y * W + x]) K[(size_t)y * W + x] = key_of(vx, vy);
         }
 }
 
-/* texture() with CLAMP_TO_EDGE, in pixel units: (px, py) is a position with texel centres at i + 0.5 */
-static vec4 bilinear_px(const uint8_t *img, int W, int H, float px, float py) {
-    const float u = px - 0.5f, v = py - 0.5f;
-    const float fu = floorf(u), fv = floorf(v);
-    const float a = u - fu, b = v - fv;
-    const int i0 = clampi((int)fu, 0, W - 1), i1 = clampi((int)fu + 1, 0, W - 1);
-    const int j0 = clampi((int)fv, 0, H - 1), j1 = clampi((int)fv + 1, 0, H - 1);
-    const float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
-    const uint8_t *t00 = img + ((size_t)j0 * W + i0) * 4, *t10 = img + ((size_t)j0 * W + i1) * 4;
-    const uint8_t *t01 = img + ((size_t)j1 * W + i0) * 4, *t11 = img + ((size_t)j1 * W + i1) * 4;
-    float r[4];
-    for (int c = 0; c < 4; ++c)
-        r[c] = ((w00 * unorm(t00[c]) + w10 * unorm(t10[c])) + w01 * unorm(t01[c])) + w11 * unorm(t11[c]);
-    vec4 o = {r[0], r[1], r[2], r[3]};
-    return o;
-}
-
-static inline int inside(float x, float y, int W, int H) { return x >= 0.0f && x <= (float)W && y >= 0.0f && y <= (float)H; }
-
-static inline void store(uint8_t *o, vec4 v) {
-    o[0] = pack_unorm(v.x); o[1] = pack_unorm(v.y); o[2] = pack_unorm(v.z); o[3] = pack_unorm(v.w);
-}
-
-static inline void decode(uint32_t key, int *ux, int *uy) {
-    *ux = (int)(key & 0xffu) - 128;
-    *uy = (int)((key >> 8) & 0xffu) - 128;
-}
-
 /* The fill vector of hole (x, y): of the first pixel that is neither a hole nor static in each axis direction within WALK,
- * the smallest (|v|^2, vy, vx); (0, 0) if there is none.  An overlay is not the surface behind it. */
-static void fill_vector(const uint32_t *K, int W, int H, int x, int y, int *ux, int *uy) {
+ * the smallest (|v|^2, vy, vx); (0, 0) if there is none.  An overlay is not the surface behind it, so this is not the
+ * shared header's fill_vector, which knows no static pixel. */
+static void fill_vector_past_static(const uint32_t *K, int W, int H, int x, int y, int *ux, int *uy) {
     static const int dir[4][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}};
-    uint32_t best = HOLE;                                      /* (|v|^2 << 16) | (vy + 128) << 8 | (vx + 128) */
+    uint32_t best = HOLE;
     for (int k = 0; k < 4; ++k)
         for (int j = 1; j <= WALK; ++j) {
             const int nx = x + dir[k][0] * j, ny = y + dir[k][1] * j;
@@ -120,8 +60,7 @@ static void fill_vector(const uint32_t *K, int W, int H, int x, int y, int *ux, 
 #else
             if (key == STATIC) continue;
 #endif
-            const uint32_t order = ((65535u - (key >> 16)) << 16) | (key & 0xffffu);
-            if (order < best) best = order;
+            if (walk_order(key) < best) best = walk_order(key);
             break;
         }
     if (best == HOLE) { *ux = 0; *uy = 0; return; }
@@ -164,7 +103,7 @@ void ov_sample(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, const
             }
             int ux, uy;
             const int hole = key == HOLE;
-            if (hole) fill_vector(K, W, H, x, y, &ux, &uy);
+            if (hole) fill_vector_past_static(K, W, H, x, y, &ux, &uy);
             else decode(key, &ux, &uy);
             const float Px = ((float)x + 0.5f) + (float)ux * t, Py = ((float)y + 0.5f) + (float)uy * t;
             const float Cx = ((float)x + 0.5f) - (float)ux * s, Cy = ((float)y + 0.5f) - (float)uy * s;
@@ -185,12 +124,6 @@ void ov_sample(const uint8_t *prev, const uint8_t *curr, const int8_t *mv, const
             if (rule == 2) { store(o, Cv); continue; }
             if (rule == 1) { store(o, Pv); continue; }
 #endif
-            const int pin = inside(Px, Py, W, H), cin = inside(Cx, Cy, W, H);
-            if (pin && !cin) store(o, Pv);
-            else if (cin && !pin) store(o, Cv);
-            else {
-                const vec4 m = {mixf(Pv.x, Cv.x, t), mixf(Pv.y, Cv.y, t), mixf(Pv.z, Cv.z, t), mixf(Pv.w, Cv.w, t)};
-                store(o, m);
-            }
+            store_inside_or_blend(o, Pv, Cv, Px, Py, Cx, Cy, W, H, t);
         }
 }
