@@ -1,7 +1,7 @@
 // extrapolate_mc.hip -- motion-compensated extrapolation (lfg_extrapolate_compensated, include/linuxfg_hip.h): curr's content is
 // projected past time 1 along the vectors just measured, and curr alone is fetched along the projected vectors.  No reference
-// counterpart; opt-in, next to interpolate_mc.hip, with which it shares the hole word, the reads, the match gate and the
-// launcher's start (lfg_mc.hpp) and the key with its decode (lfg_vector_word.hpp); the batched hole walk is its own.
+// counterpart; opt-in, next to interpolate_mc.hip, with which it shares the hole word, the walk's reach, the reads, the match
+// gate and the launcher's steps (lfg_mc.hpp) and the key with its decode (lfg_vector_word.hpp); the batched hole walk is its own.
 // tests/extrapolate_model.c restates every step below on the CPU.
 //
 // Two launches per factor, after the key image K (W * H words, the lane's scratch, interpolate_mc.hip's) has been set to 0xFF
@@ -13,13 +13,11 @@
 // Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 4
 // (one fetch, mostly cached neighbours) + 4 (out) in the sampling: 30 bytes, 249 MB at 4K.
 #include "lfg_mc.hpp"
-#include "lfg_interp.hpp"
 
 namespace lfg {
 
 namespace {
 
-constexpr int kExWalk = 16;                    // the hole walk's reach, per axis direction
 constexpr int kExBatch = 4;                    // words of each direction loaded ahead of their comparison
 
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void ex_project_kernel(
@@ -47,14 +45,14 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void ex_sample_kernel(
     bool donor = false;
     int nx = x, ny = y;
     if (hole) {
-        // Each direction's first non-hole word within kExWalk.  The words of all four directions are loaded kExBatch steps
+        // Each direction's first non-hole word within kMcWalk.  The words of all four directions are loaded kExBatch steps
         // ahead of their comparison: a round is 16 independent loads, and a hole next to projected pixels is done after one.
         // A step past the image edge reads as a hole (its address is clamped into the image): every later step of that
         // direction is past the edge too, so the direction keeps nothing, as when the walk stops there.
         const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
         uint32_t first[4] = {kMcHole, kMcHole, kMcHole, kMcHole};
         int firstK[4] = {0, 0, 0, 0};
-        for (int base = 1; base <= kExWalk; base += kExBatch) {
+        for (int base = 1; base <= kMcWalk; base += kExBatch) {
             uint32_t n[4][kExBatch];
 #pragma unroll
             for (int d = 0; d < 4; ++d)
@@ -118,16 +116,14 @@ hipError_t launch_extrapolate_compensated(hipStream_t s, const lfg_frame &prev, 
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ex_project_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
-                       (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, ahead,
-                       matchSad, keys);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ex_sample_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
-                       (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
-                       (const uint32_t *)keys, W, H, ahead, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
-    return hipGetLastError();
+    if (e == hipSuccess)
+        e = mc_launch(ex_project_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
+                      (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, ahead, matchSad, keys);
+    if (e == hipSuccess)
+        e = mc_launch(ex_sample_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
+                      (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint32_t *)keys, W, H, ahead, matchSad,
+                      (uint8_t *)out.data, (size_t)out.pitch);
+    return e;
 }
 
 }  // namespace lfg

@@ -2,7 +2,8 @@
 // include/linuxfg_hip.h) and the forward-backward check on its own (lfg_motion_consistency).  No reference counterpart;
 // opt-in, next to interpolate_mc.hip, whose definition it keeps but for three things: a vector projects only when the field
 // measured the other way confirms it, prev's grid projects too, and a hole's revealed / covered decision asks both frames.
-// The predicates are lfg_mc_bidir.hpp's; the hole word, the reads, the match gate and the launcher's start lfg_mc.hpp's; the
+// The predicates are lfg_mc_bidir.hpp's; the hole word, the reads, the match gate, the hole walk (mc_fill_vector), the end of
+// a pixel (mc_store_inside_or_blend) and the launchers' steps lfg_mc.hpp's, the same functions interpolate_mc.hip calls; the
 // key, its decode and the hole walk's order lfg_vector_word.hpp's; the taps lfg_interp.hpp's.  tests/bidir_model.c restates
 // every step below on the CPU.
 //
@@ -20,13 +21,10 @@
 // vector) + 4 (atomic)) in the projections, 4 (K) + 8 (two fetches, mostly cached neighbours) + 4 (out) in the sampling:
 // 52 bytes, 431 MB at 4K, against interpolate_mc.hip's 34.
 #include "lfg_mc_bidir.hpp"
-#include "lfg_interp.hpp"
 
 namespace lfg {
 
 namespace {
-
-constexpr int kBidirWalk = 16;                 // the hole walk's reach, per axis direction: interpolate_mc.hip's
 
 // Forward: own = curr, far = prev, mine = fwd, other = bwd.  Backward: own = prev, far = curr, mine = bwd, other = fwd.
 template <bool Backward>
@@ -57,25 +55,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_sample_kernel(
     const float s = 1.0f - t;
     uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
     const bool hole = key == kMcHole;
-    if (hole) {
-        // mc_interpolate_kernel's walk: of the first non-hole word in each axis direction within kBidirWalk, the smallest
-        // (|v|^2, vy, vx); (0, 0) when every direction runs out.
-        uint32_t best = kMcHole;
-        const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            for (int k = 1; k <= kBidirWalk; ++k) {
-                const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
-                if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
-                const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
-                if (n == kMcHole) continue;
-                const uint32_t order = mv_key_flip_length(n);
-                best = order < best ? order : best;
-                break;
-            }
-        }
-        key = best == kMcHole ? mv_order_key(0, 0) : best;     // only the low 16 bits are decoded
-    }
+    if (hole) key = mc_fill_vector<false>(keys, W, H, x, y);
     const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
@@ -97,10 +77,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_sample_kernel(
                           bidir_confirmed<true>(curr, (size_t)currPitch, pTexel, fwd, fwdPitch, W, H, qx, qy, bp, matchSad, tolerance);
         only = cBad && !pBad ? 1 : (pBad && !cBad ? 2 : 0);
     }
-    if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
-    const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
-    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
-    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+    mc_store_inside_or_blend(sp, tp, sc, tc, only, t, out, outPitch, x, y);
 }
 
 // out(q) = 255 where a(q) is consistent with b, 0 elsewhere: one byte per thread, the W bytes of each row and no more.
@@ -121,30 +98,25 @@ hipError_t launch_interpolate_compensated_bidirectional(hipStream_t s, const lfg
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bidir_project_kernel<false>, grid, mc_block(), 0, s, (const uint8_t *)curr.data, (size_t)curr.pitch,
-                       (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch,
-                       (const uint8_t *)bwd.data, (size_t)bwd.pitch, W, H, factor, matchSad, tolerance, keys);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bidir_project_kernel<true>, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
-                       (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch,
-                       (const uint8_t *)fwd.data, (size_t)fwd.pitch, W, H, factor, matchSad, tolerance, keys);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bidir_sample_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
-                       (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch,
-                       (const uint8_t *)bwd.data, (size_t)bwd.pitch, (const uint32_t *)keys, W, H, factor, matchSad, tolerance,
-                       (uint8_t *)out.data, (size_t)out.pitch);
-    return hipGetLastError();
+    if (e == hipSuccess)
+        e = mc_launch(bidir_project_kernel<false>, grid, s, (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)prev.data,
+                      (size_t)prev.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch,
+                      W, H, factor, matchSad, tolerance, keys);
+    if (e == hipSuccess)
+        e = mc_launch(bidir_project_kernel<true>, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
+                      (size_t)curr.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch,
+                      W, H, factor, matchSad, tolerance, keys);
+    if (e == hipSuccess)
+        e = mc_launch(bidir_sample_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
+                      (int)curr.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch,
+                      (const uint32_t *)keys, W, H, factor, matchSad, tolerance, (uint8_t *)out.data, (size_t)out.pitch);
+    return e;
 }
 
 hipError_t launch_motion_consistency(hipStream_t s, const lfg_frame &a, const lfg_frame &b, int tolerance, const lfg_mask &out) {
     const int W = (int)a.width, H = (int)a.height;
-    const dim3 grid((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
-    hipLaunchKernelGGL(motion_consistency_kernel, grid, mc_block(), 0, s, (const uint8_t *)a.data, (size_t)a.pitch,
-                       (const uint8_t *)b.data, (size_t)b.pitch, W, H, tolerance, (uint8_t *)out.data, (size_t)out.pitch);
-    return hipGetLastError();
+    return mc_launch(motion_consistency_kernel, mc_grid(W, H), s, (const uint8_t *)a.data, (size_t)a.pitch, (const uint8_t *)b.data,
+                     (size_t)b.pitch, W, H, tolerance, (uint8_t *)out.data, (size_t)out.pitch);
 }
 
 }  // namespace lfg

@@ -9,22 +9,17 @@
 // neighbours that other workgroups also read.  lfg_interpolate_compensated_masked runs the same two launches through
 // mc_project_masked_kernel and mc_interpolate_masked_kernel (tests/overlay_model.c).  The project pair is one body,
 // mc_project<Masked>, under two wrappers that keep the kernels' names and argument lists; the interpolate pair is two kernels
-// (see there).  The hole word, the reads, the match gate and the launchers' start are lfg_mc.hpp's, shared with
-// extrapolate_mc.hip; the key, its decode and the hole walk's order are lfg_vector_word.hpp's.
+// that share their hole walk and the end of a pixel (see there).  The hole and static words, the reads, the match gate, the
+// walk (mc_fill_vector), the end of a pixel (mc_store_inside_or_blend) and the launchers' steps are lfg_mc.hpp's, shared with
+// extrapolate_mc.hip and interpolate_bidir.hip; the key, its decode and the hole walk's order are lfg_vector_word.hpp's.
 //
 // Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 8
 // (two fetches, mostly cached neighbours) + 4 (out) in the interpolation: 34 bytes, 280 MB at 4K.
 #include "lfg_mc.hpp"
-#include "lfg_interp.hpp"
 
 namespace lfg {
 
 namespace {
-
-constexpr int kMcWalk = 16;                    // the hole walk's reach, per axis direction
-// Key 0 marks a static location (the masked pair only): no vector's key is 0 (65535 - |v|^2 >= 32767), and it is the smallest
-// word, so it outlasts whatever is projected onto it.
-constexpr uint32_t kMcStatic = 0u;
 
 // Both project kernels.  Masked: one more byte of traffic per pixel, and a static pixel projects its own vector as any other.
 template <bool Masked>
@@ -52,9 +47,11 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_kernel(
     mc_project<false>(prev, prevPitch, curr, currPitch, mv, mvPitch, nullptr, 0, W, H, t, matchSad, keys);
 }
 
-// The two interpolate kernels are not one body: as wrappers around a shared one they differed from these by two swapped
-// v_mad_u64_u32 factors (the unmasked one also by a few reordered instructions), and a changed kernel has to stay inside the
-// former code's run-to-run spread on every row of the stage tools, which neither did.
+// The two interpolate kernels take their hole walk and the end of a pixel from lfg_mc.hpp (mc_fill_vector,
+// mc_store_inside_or_blend), as bidir_sample_kernel does.  They are not one body: what lies between differs in kind (the
+// static shortcut, the mask bytes and the fetch rule are the masked kernel's alone) and in place (the unmasked kernel
+// computes the clamped position inside the hole branch, the masked one for every pixel).  One template <bool Masked> body
+// had to move those, and was not kept.
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
         const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad,
@@ -64,25 +61,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
     const float s = 1.0f - t;
     uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
     const bool hole = key == kMcHole;
-    if (hole) {
-        // The fill vector: of the first non-hole word in each axis direction within kMcWalk, the smallest (|v|^2, vy, vx);
-        // (0, 0) when every direction runs out.
-        uint32_t best = kMcHole;
-        const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            for (int k = 1; k <= kMcWalk; ++k) {
-                const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
-                if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
-                const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
-                if (n == kMcHole) continue;
-                const uint32_t order = mv_key_flip_length(n);
-                best = order < best ? order : best;
-                break;
-            }
-        }
-        key = best == kMcHole ? mv_order_key(0, 0) : best;     // only the low 16 bits are decoded
-    }
+    if (hole) key = mc_fill_vector<false>(keys, W, H, x, y);
     const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
@@ -98,10 +77,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
         if (!matched(prev, (size_t)prevPitch, texel_u32(curr, (size_t)currPitch, cx, cy), W, H, cx, cy, vc, matchSad)) only = 2;
         else if (vc.x != u.x || vc.y != u.y) only = 1;
     }
-    if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
-    const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
-    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
-    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+    mc_store_inside_or_blend(sp, tp, sc, tc, only, t, out, outPitch, x, y);
 }
 
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_masked_kernel(
@@ -126,24 +102,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_k
         return;
     }
     const bool hole = key == kMcHole;
-    if (hole) {
-        // mc_interpolate_kernel's walk, which also passes over static pixels: an overlay is not the surface behind it
-        uint32_t best = kMcHole;
-        const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            for (int k = 1; k <= kMcWalk; ++k) {
-                const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
-                if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
-                const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
-                if (n == kMcHole || n == kMcStatic) continue;
-                const uint32_t order = mv_key_flip_length(n);
-                best = order < best ? order : best;
-                break;
-            }
-        }
-        key = best == kMcHole ? mv_order_key(0, 0) : best;
-    }
+    if (hole) key = mc_fill_vector<true>(keys, W, H, x, y);    // the walk also passes over static pixels
     const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
@@ -162,10 +121,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_k
         if (!matched(prev, (size_t)prevPitch, texel_u32(curr, (size_t)currPitch, cx, cy), W, H, cx, cy, vc, matchSad)) only = 2;
         else if (vc.x != u.x || vc.y != u.y) only = 1;
     }
-    if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
-    const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
-    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
-    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+    mc_store_inside_or_blend(sp, tp, sc, tc, only, t, out, outPitch, x, y);
 }
 
 }  // namespace
@@ -176,17 +132,15 @@ hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame 
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_project_masked_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
-                       (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
-                       (const uint8_t *)mask.data, (size_t)mask.pitch, W, H, factor, matchSad, keys);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_interpolate_masked_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
-                       (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
-                       (const uint8_t *)mask.data, (size_t)mask.pitch, (const uint32_t *)keys, W, H, factor, matchSad,
-                       (uint8_t *)out.data, (size_t)out.pitch);
-    return hipGetLastError();
+    if (e == hipSuccess)
+        e = mc_launch(mc_project_masked_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
+                      (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint8_t *)mask.data,
+                      (size_t)mask.pitch, W, H, factor, matchSad, keys);
+    if (e == hipSuccess)
+        e = mc_launch(mc_interpolate_masked_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
+                      (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint8_t *)mask.data, (size_t)mask.pitch,
+                      (const uint32_t *)keys, W, H, factor, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
+    return e;
 }
 
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
@@ -194,16 +148,14 @@ hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, 
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_project_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch,
-                       (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, factor,
-                       matchSad, keys);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_interpolate_kernel, grid, mc_block(), 0, s, (const uint8_t *)prev.data, (int)prev.pitch,
-                       (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
-                       (const uint32_t *)keys, W, H, factor, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
-    return hipGetLastError();
+    if (e == hipSuccess)
+        e = mc_launch(mc_project_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
+                      (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, factor, matchSad, keys);
+    if (e == hipSuccess)
+        e = mc_launch(mc_interpolate_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
+                      (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint32_t *)keys, W, H, factor, matchSad,
+                      (uint8_t *)out.data, (size_t)out.pitch);
+    return e;
 }
 
 }  // namespace lfg

@@ -1,16 +1,25 @@
-// What the compensated family shares (interpolate_mc.hip, extrapolate_mc.hip): the key image K's hole word, the packed-texel
-// read, the vector read, the match gate, and the start of every launcher.  The vector word, the longest-first key that K
-// holds (mv_longest_first_key), its decode (mv_order_decode) and the hole walks' way back to the order key
-// (mv_key_flip_length) are lfg_vector_word.hpp's.
+// What the compensated family shares (interpolate_mc.hip, extrapolate_mc.hip, interpolate_bidir.hip): the key image K's hole
+// and static words, the packed-texel read, the vector read, the match gate, the start of every launcher and its launches
+// (mc_clear_keys, mc_grid, mc_block, mc_launch), and the two halves that the three sampling kernels which blend both frames
+// have in common (mc_interpolate_kernel, mc_interpolate_masked_kernel, bidir_sample_kernel): the hole walk, mc_fill_vector,
+// and the end of a pixel, mc_store_inside_or_blend.  Both carry the names of their CPU restatements in
+// tests/compensated_model.h.  The vector word, the longest-first key that K holds (mv_longest_first_key), its decode
+// (mv_order_decode) and the hole walks' way back to the order key (mv_key_flip_length) are lfg_vector_word.hpp's; the taps
+// are lfg_interp.hpp's.
 #pragma once
 
 #include "lfg_device.hpp"
 #include "lfg_internal.hpp"
+#include "lfg_interp.hpp"
 #include "lfg_vector_word.hpp"
 
 namespace lfg {
 
 constexpr uint32_t kMcHole = 0xFFFFFFFFu;      // K where nothing was projected: what the clear leaves, above every key
+// Key 0 marks a static location (the masked pair only): no vector's key is 0 (65535 - |v|^2 >= 32767), and it is the smallest
+// word, so it outlasts whatever is projected onto it.
+constexpr uint32_t kMcStatic = 0u;
+constexpr int kMcWalk = 16;                    // every hole walk's reach, per axis direction
 constexpr int kMcBlockX = 64, kMcBlockY = 4;   // a wave is 64 pixels of one row
 
 __device__ __forceinline__ uint32_t texel_u32(const uint8_t *__restrict__ img, size_t pitch, int x, int y) {
@@ -30,12 +39,54 @@ __device__ __forceinline__ bool matched(const uint8_t *__restrict__ prev, size_t
     return __builtin_amdgcn_sad_u8(currTexel, p, 0u) <= (uint32_t)matchSad;
 }
 
-// Every launcher's start: K (W * H words) set to the hole word in stream order, and the grid of both launches, one thread
-// per pixel in blocks of kMcBlockX x kMcBlockY.
+// The fill vector of hole (x, y), as its order key: of the first non-hole word in each axis direction within kMcWalk, the
+// smallest (|v|^2, vy, vx); (0, 0) when every direction runs out.  Only the low 16 bits of the result are decoded.
+// PassStatic (the masked kernel): the walk also passes over static pixels, an overlay is not the surface behind it.
+// (ex_sample_kernel's batched walk is another algorithm: it keeps the step count for the donor.)
+template <bool PassStatic>
+__device__ __forceinline__ uint32_t mc_fill_vector(const uint32_t *__restrict__ keys, int W, int H, int x, int y) {
+    uint32_t best = kMcHole;
+    const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        for (int k = 1; k <= kMcWalk; ++k) {
+            const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
+            if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
+            const uint32_t n = keys[(size_t)ny * (size_t)W + (size_t)nx];
+            if (n == kMcHole || (PassStatic && n == kMcStatic)) continue;
+            const uint32_t order = mv_key_flip_length(n);
+            best = order < best ? order : best;
+            break;
+        }
+    }
+    return best == kMcHole ? mv_order_key(0, 0) : best;
+}
+
+// The end of an interpolated pixel.  `only` is what the caller's rules decided -- 0: nothing, 1: prev's sample alone, 2:
+// curr's alone -- and 0 falls to the inside rule: the sample whose position alone is inside the image, else the blend.
+__device__ __forceinline__ void mc_store_inside_or_blend(const SampleTaps &sp, const SampleTexels &tp, const SampleTaps &sc,
+                                                         const SampleTexels &tc, int only, float t, uint8_t *__restrict__ out,
+                                                         size_t outPitch, int x, int y) {
+    if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
+    const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
+    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
+    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+}
+
+// Every launcher's start: K (W * H words) set to the hole word in stream order, and the grid of every launch, one thread
+// per pixel in blocks of kMcBlockX x kMcBlockY.  mc_launch is one launch on that grid and its error.
 inline dim3 mc_block() { return dim3(kMcBlockX, kMcBlockY); }
+inline dim3 mc_grid(int W, int H) {
+    return dim3((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
+}
 inline hipError_t mc_clear_keys(hipStream_t s, uint32_t *keys, int W, int H, dim3 &grid) {
-    grid = dim3((unsigned)((W + kMcBlockX - 1) / kMcBlockX), (unsigned)((H + kMcBlockY - 1) / kMcBlockY));
+    grid = mc_grid(W, H);
     return hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 4u, s);
+}
+template <typename... Params, typename... Args>
+inline hipError_t mc_launch(void (*kernel)(Params...), dim3 grid, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, grid, mc_block(), 0, s, args...);
+    return hipGetLastError();
 }
 
 }  // namespace lfg

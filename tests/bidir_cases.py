@@ -121,6 +121,17 @@ def tolerance_edges():
     return prev, curr, fwd, bwd, {(1, 2): (2, 1), (5, 2): (1, 1), (9, 2): (3, 2), (13, 2): (0, 0)}
 
 
+def walk_reach():
+    """(prev, curr, fwd, bwd, blank): cases.mc_walk_reach with the field measured the other way, for match_sad 1020 and tolerance
+    0.  bwd is (127, 0) everywhere but bwd(21, 20) = (-2, 0): it confirms fwd(19, 20) = (2, 0), is confirmed by it, and lands on
+    (20, 20) as well at t = 0.5 and 0.3 (floor(-2 * 0.5 + 0.5) = floor(-2 * 0.3 + 0.5) = -1), carrying (2, 0).  No (127, 0) is
+    confirmed: its far end is outside the image.  `blank` is (127, 0) everywhere, for both fields: K all holes."""
+    prev, curr, fwd, blank = cases.mc_walk_reach()
+    bwd = blank.copy()
+    bwd[20, 21] = (-2, 0)
+    return prev, curr, fwd, bwd, blank
+
+
 def shared_cases():
     """(name, prev, curr, fwd, bwd, match_sad, tolerances): the hand-made cases through the public call, on the CPU and the GPU."""
     yield ("false_match", *false_match_on_flat(), 0, (0, 4, 5))

@@ -295,6 +295,59 @@ def mc_row_projected_to_the_top():
     return prev, curr, mv
 
 
+# ---- the hole walk's reach through the public calls (the compensated, the masked and, with tests/bidir_cases.py, the
+# bidirectional one).  40 x 40, independent random frames, match_sad 1020 (every pixel matches), every vector (127, 0): at
+# t = 0.5 and 0.3 it projects 64 and 89 columns to the right, out of the image, so K is all holes -- but for mv(19, 20) =
+# (2, 0), which lands on (20, 20) at both factors: floor(2 * 0.5 + 0.5) = floor(2 * 0.7 + 0.5) = 1.  Only holes that find
+# (20, 20) within the walk's 16 steps are filled with (2, 0) and not (0, 0): row 20 and column 20 at 4 .. 36, both included.
+
+WALK_REACH_FACTORS = (0.5, 0.3)
+WALK_REACH_MATCH_SAD = 1020
+WALK_REACH_TIPS = ((4, 20), (36, 20), (20, 4), (20, 36))           # (x, y) at distance 16: filled
+WALK_REACH_PAST = ((3, 20), (37, 20), (20, 3), (20, 37))           # at 17: not
+
+
+def mc_walk_reach():
+    """(prev, curr, mv, blank): the case above, and `blank`, the field with (127, 0) everywhere, whose K is all holes."""
+    rng = np.random.default_rng(7)
+    prev = rng.integers(0, 256, (40, 40, 4), dtype=np.uint8)
+    curr = rng.integers(0, 256, (40, 40, 4), dtype=np.uint8)
+    blank = np.zeros((40, 40, 2), np.int8)
+    blank[...] = (127, 0)
+    mv = blank.copy()
+    mv[20, 19] = (2, 0)
+    return prev, curr, mv, blank
+
+
+def walk_reach_plus():
+    """The 65 pixels of the 40 x 40 image that see (20, 20) within 16 steps along an axis, (20, 20) included, as a mask."""
+    plus = np.zeros((40, 40), bool)
+    plus[20, 4:37] = plus[4:37, 20] = True
+    return plus
+
+
+def walk_reach_static_run():
+    """The mask of the masked call's second run: (26 .. 29, 20) static, between (20, 20) and the tip (36, 20)."""
+    mask = np.zeros((40, 40), np.uint8)
+    mask[20, 26:30] = 255
+    return mask
+
+
+def check_walk_reach(frame, blank_frame, what, static_run=False):
+    """`frame` (of mv) differs from `blank_frame` (of blank) on the plus and nowhere else: the tips at distance 16 do, the
+    pixels one step further do not.  static_run: both frames are the masked call's under walk_reach_static_run() -- its four
+    pixels are the static mix in both, and the walk passes over them, so the plus loses them and nothing else: (36, 20) still
+    differs."""
+    differs = (frame != blank_frame).any(axis=-1)
+    want = walk_reach_plus()
+    if static_run:
+        want[20, 26:30] = False
+    assert differs.sum() == (61 if static_run else 65), (what, int(differs.sum()))
+    assert (differs == want).all(), (what, np.argwhere(differs != want)[:4].tolist())
+    assert all(differs[y, x] for x, y in WALK_REACH_TIPS), what
+    assert not any(differs[y, x] for x, y in WALK_REACH_PAST), what
+
+
 # ---- lfg_motion_pyramid: the tie of test_pyramid_model.py
 
 def pyramid_tie(axis: int):

@@ -1,7 +1,8 @@
 /* What the CPU models of the compensated family share (mc_model.c, overlay_model.c, extrapolate_model.c, bidir_model.c): the
  * library's own helpers restated once, in the header's fp32 operation order, for a build with -ffp-contract=off.  On the kernel
- * side each of them has one home too: the hole word and the match gate in linux-fg_amd/csrc/lfg_mc.hpp, the key, its decode and
- * the flip to the walk's order in lfg_vector_word.hpp, the taps and the UNORM8 conversions in lfg_interp.hpp.
+ * side each of them has one home too: the hole word, the match gate, the hole walk (mc_fill_vector) and the end of a pixel
+ * (mc_store_inside_or_blend) in linux-fg_amd/csrc/lfg_mc.hpp, the key, its decode and the flip to the walk's order in
+ * lfg_vector_word.hpp, the taps and the UNORM8 conversions in lfg_interp.hpp.
  *
  * Only what means the same in every model lives here.  A step that differs between two models (a projection, a walk that
  * passes static pixels or reports its donor, a hole rule) is a function of that model's own file, with its mutant macros

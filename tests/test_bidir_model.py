@@ -97,6 +97,19 @@ def test_the_backward_projection_fills_a_crack_with_the_measured_vector():
     assert not (got[:, 19] == mc.interpolate_compensated(prev, curr, fwd, t, 1020)[:, 19]).all()
 
 
+def test_the_walk_reaches_16_through_the_call():
+    """bc.walk_reach: both projections land on (20, 20), the only word of K, and change exactly the holes within 16 steps."""
+    prev, curr, fwd, bwd, blank = bc.walk_reach()
+    ms = cases.WALK_REACH_MATCH_SAD
+    for t in cases.WALK_REACH_FACTORS:
+        for direction in ("forward", "backward", "both"):
+            K = bd.keys(prev, curr, fwd, bwd, t, ms, 0, direction)
+            assert K[20, 20] == key(2, 0) and (K != HOLE).sum() == 1, (t, direction)
+        assert (bd.keys(prev, curr, blank, blank, t, ms, 0) == HOLE).all(), t
+        cases.check_walk_reach(bd.interpolate_bidirectional(prev, curr, fwd, bwd, t, ms, 0),
+                               bd.interpolate_bidirectional(prev, curr, blank, blank, t, ms, 0), t)
+
+
 def test_revealed_and_covered_through_the_call():
     prev, curr, fwd, bwd, obj = bc.revealed_and_covered()
     K = bd.keys(prev, curr, fwd, bwd, 0.5, 0, 0)

@@ -82,6 +82,20 @@ def test_shared_cases_equal_the_model(ctx):
                     assert (got == want).all(), f"{name} t={t} tolerance={tol}: {first_bad(got, want)}"
 
 
+def test_the_walk_reaches_16(ctx):
+    """bc.walk_reach at tolerance 0: both projections land on one pixel of a key image of holes.  Byte for byte the model, and
+    literally: the holes at distance 16 along an axis are filled from it, those at 17 are not."""
+    prev, curr, fwd, bwd, blank = bc.walk_reach()
+    ms = cases.WALK_REACH_MATCH_SAD
+    with Device(ctx, prev, curr, fwd, bwd) as dev, Device(ctx, prev, curr, blank, blank) as dev_blank:
+        for t in cases.WALK_REACH_FACTORS:
+            got, got_blank = dev.run(t, ms, 0), dev_blank.run(t, ms, 0)
+            for g, (f, b) in ((got, (fwd, bwd)), (got_blank, (blank, blank))):
+                want = bd.interpolate_bidirectional(prev, curr, f, b, t, ms, 0)
+                assert (g == want).all(), f"t={t}: {first_bad(g, want)}"
+            cases.check_walk_reach(got, got_blank, t)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_motion_consistency_equals_the_model(ctx, kind):
     for i, (w, h) in enumerate(SIZES):

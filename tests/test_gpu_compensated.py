@@ -171,6 +171,19 @@ def test_hand_made_cases(ctx):
             assert (run(ctx, prev, curr, mv, 1.0, ms) == curr).all(), (w, h, ms)
 
 
+def test_the_walk_reaches_16(ctx):
+    """cases.mc_walk_reach: one projected pixel in a key image of holes.  Byte for byte the model, and literally: the holes at
+    distance 16 along an axis are filled from it, those at 17 are not."""
+    prev, curr, mv, blank = cases.mc_walk_reach()
+    ms = cases.WALK_REACH_MATCH_SAD
+    for t in cases.WALK_REACH_FACTORS:
+        got, got_blank = run(ctx, prev, curr, mv, t, ms), run(ctx, prev, curr, blank, t, ms)
+        for g, field in ((got, mv), (got_blank, blank)):
+            want = mc.interpolate_compensated(prev, curr, field, t, ms)
+            assert (g == want).all(), f"t={t}: {first_bad(g, want)}"
+        cases.check_walk_reach(got, got_blank, t)
+
+
 # ---- what the shader's modes do not do: content at time t where it is
 
 def test_4k_pan_full_search(ctx):

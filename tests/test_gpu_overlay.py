@@ -192,6 +192,19 @@ def test_masked_hand_made_cases(ctx):
     assert (outs["rule on a hole, c static"][0, 8] == oc.rule_on_a_hole(False)[0][0, 6]).all()
 
 
+def test_masked_walk_reaches_16(ctx):
+    """cases.mc_walk_reach through the masked call, byte for byte the model: under an all-zero mask the holes at distance 16
+    are filled from the one projected pixel and those at 17 are not; with (26 .. 29, 20) static the walk passes over the run
+    and (36, 20) is still filled."""
+    prev, curr, mv, blank = cases.mc_walk_reach()
+    factors, ms = list(cases.WALK_REACH_FACTORS), cases.WALK_REACH_MATCH_SAD
+    for mask, static_run in ((np.zeros((40, 40), np.uint8), False), (cases.walk_reach_static_run(), True)):
+        got = check_against_model(ctx, prev, curr, mv, mask, factors, ms, f"walk reach, run {static_run}")
+        got_blank = check_against_model(ctx, prev, curr, blank, mask, factors, ms, f"walk reach, blank, run {static_run}")
+        for t, g, b in zip(factors, got, got_blank):
+            cases.check_walk_reach(g, b, (t, static_run), static_run=static_run)
+
+
 def test_masked_region_of_interest(ctx):
     prev, curr, mv, mask, ms, (x, y, w, h) = oc.region_of_interest()
     H, W = prev.shape[:2]

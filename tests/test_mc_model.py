@@ -131,6 +131,17 @@ def test_hole_with_nothing_within_16_gets_zero():
             == unorm_pack(mix(prev, curr, 0.5))).all()
 
 
+def test_the_walk_reaches_16_through_the_call():
+    """cases.mc_walk_reach: the one projected pixel, (20, 20), changes exactly the holes that find it within 16 steps."""
+    prev, curr, mv, blank = cases.mc_walk_reach()
+    for t in cases.WALK_REACH_FACTORS:
+        K = mc.keys(prev, curr, mv, t, cases.WALK_REACH_MATCH_SAD)
+        assert K[20, 20] == key(2, 0) and (K != HOLE).sum() == 1, t
+        assert (mc.keys(prev, curr, blank, t, cases.WALK_REACH_MATCH_SAD) == HOLE).all(), t
+        cases.check_walk_reach(mc.interpolate_compensated(prev, curr, mv, t, cases.WALK_REACH_MATCH_SAD),
+                               mc.interpolate_compensated(prev, curr, blank, t, cases.WALK_REACH_MATCH_SAD), t)
+
+
 def test_revealed_content_comes_from_curr_and_covered_from_prev():
     prev, curr, mv, obj = cases.mc_revealed_and_covered()    # an object moves from (4, 2) to (6, 2): v(6, 2) = (-2, 0)
     K = mc.keys(prev, curr, mv, 0.5, 0)

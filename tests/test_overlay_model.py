@@ -128,6 +128,19 @@ def test_hand_made_cases_state_the_definition():
     assert (ov.interpolate_masked(prev, curr, mv, mask, 0.5, ms)[0, 8] == prev[0, 6]).all()
 
 
+def test_the_walk_reaches_16_through_the_call():
+    """cases.mc_walk_reach under an all-zero mask: exactly the 65 pixels of the compensated model.  With (26 .. 29, 20) static
+    the walk passes over the run: 61, the 65 less the run itself, and the tip (36, 20) still finds (20, 20)."""
+    prev, curr, mv, blank = cases.mc_walk_reach()
+    ms = cases.WALK_REACH_MATCH_SAD
+    for t in cases.WALK_REACH_FACTORS:
+        for mask, run in ((np.zeros((40, 40), np.uint8), False), (cases.walk_reach_static_run(), True)):
+            K = ov.keys(prev, curr, mv, mask, t, ms)
+            assert K[20, 20] == mc.key(2, 0) and (K == ov.STATIC).sum() == (4 if run else 0) and (K == ov.HOLE).sum() == (1595 if run else 1599)
+            cases.check_walk_reach(ov.interpolate_masked(prev, curr, mv, mask, t, ms),
+                                   ov.interpolate_masked(prev, curr, blank, mask, t, ms), (t, run), static_run=run)
+
+
 def test_region_of_interest_is_the_crop():
     prev, curr, mv, mask, ms, (x, y, w, h) = oc.region_of_interest()
     crop = tuple(a[y:y + h, x:x + w] for a in (prev, curr, mv, mask))
