@@ -554,6 +554,50 @@ int  lfg_motion_refine(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
  * Any other radius: LFG_ERR_INVALID and no change. */
 int  lfg_set_vector_refinement(lfg_context *ctx, int radius);
 
+/* Half-resolution motion, opt-in.  No reference counterpart.  Motion estimation is the cost of a generated frame; both
+ * estimators take frames of any size, so the field can be estimated on frames of half the size and carried to full size.
+ * lfg_frame_halve makes the half-size frame and lfg_motion_expand the full-size field.  Integer arithmetic only; neither
+ * depends on lfg_set_semantics.
+ *
+ * lfg_frame_halve: lfg_motion_pyramid's level rule as a call.  in RGBA8 W x H, out RGBA8 ceil(W / 2) x ceil(H / 2); each channel
+ * of out(x, y) is the rounded mean (sum + 2) >> 2 of in at (2x + i, 2y + j), i, j in {0, 1}, coordinates clamped to in.
+ * Frames: 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4), W, H >= 1, out overlapping no byte of in.  Any
+ * violation, a NULL pointer, a wrong format or a wrong out size returns LFG_ERR_INVALID before anything is enqueued.  One
+ * launch on the selected lane; keeps no device memory; timed under LFG_STAGE_MOTION. */
+int  lfg_frame_halve(lfg_context *ctx, const lfg_frame *in, lfg_frame *out);
+/* lfg_motion_expand: a W x H field from a ceil(W / 2) x ceil(H / 2) one, the choice steered by the full-resolution frames.
+ *   Inputs: prev, curr RGBA8 and mv_out LFG_FORMAT_MV_S8X2, all W x H; mv_low MV_S8X2 of exactly ceil(W / 2) x ceil(H / 2), any
+ *   byte values; 0 <= radius <= 2.
+ *   dbl(v) = (clamp(2 v.x, -127, 127), clamp(2 v.y, -127, 127)).
+ *   Cost of vector v at q: lfg_motion_refine's, word for word -- the sum over texels r of the (2 radius + 1)^2 window centred
+ *   on q, and over the four channels, of |curr(r)_c - prev(r + v)_c|; texels r outside the image are skipped, prev outside the
+ *   image reads as 0.  The smallest key (cost, vx^2 + vy^2, vy, vx) wins: lfg_motion_refine's total order.
+ *   Step 1, the coarse neighbour: the candidates of q = (x, y) are dbl(mv_low(n)) for n = (x >> 1, y >> 1) + (a, b), a, b in
+ *   {-1, 0, 1}.  A position n outside mv_low gives no candidate; the centre always is one.  w = the candidate with the smallest
+ *   key.
+ *   Step 2, the parity that doubling cannot express: the candidates are (clamp(w.x + dx, -127, 127), clamp(w.y + dy, -127,
+ *   127)) for dx, dy in {-1, 0, 1}, w among them.  mv_out(q) = the one with the smallest key.
+ * Hence: the order is total, so neither the order of evaluation nor any tiling changes a result; a uniform mv_low of v gives,
+ * at every pixel, the best of dbl(v) + [-1, 1]^2; every output component lies in [-127, 127].
+ * Frames: lfg_motion_refine's rules -- 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4), 2-byte aligned vector
+ * frames -- and mv_out must not overlap any input.  Any violation, a wrong mv_low size and a radius outside [0, 2] returns
+ * LFG_ERR_INVALID before anything is enqueued.  One launch on the selected lane; keeps no device memory; timed under
+ * LFG_STAGE_MOTION.  Not built: other ratios than 2; an expansion fused into lfg_motion_refine or into the projection of the
+ * compensated interpolators. */
+int  lfg_motion_expand(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv_low,
+                       lfg_frame *mv_out, int radius);
+/* Half-resolution motion in lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   radius = -1 (default): off; every path enqueues and allocates what it did;
+ *   radius = 0 .. 2: wherever those calls run the selected estimator -- for both directions of lfg_set_bidirectional -- they
+ *       halve both frames into per-lane temporaries (lfg_frame_halve), run the estimator on the halves into a per-lane
+ *       half-size vector frame -- LFG_ESTIMATOR_FULL_SEARCH: lfg_motion(8, 16); LFG_ESTIMATOR_PYRAMID: lfg_motion_pyramid(1, 16,
+ *       2), which with the expansion reaches 2 (16 * 2 + 2) + 1 = 69 px -- and run lfg_motion_expand with this radius into the
+ *       vector temporary the estimator wrote before.  The temporaries are made on demand, follow a change of size and are
+ *       freed with the lane.  Everything downstream takes the field unchanged: refinement, cut detection, static protection,
+ *       every interpolator and generation mode.  lfg_set_fused_motion_interpolate does not apply.
+ * Any other radius: LFG_ERR_INVALID and no change.  Measured cost and quality: DESIGN.md section 4.18. */
+int  lfg_set_half_resolution_motion(lfg_context *ctx, int radius);
+
 /* Pair statistics: how well a vector field explains a pair of frames.  No reference counterpart.  A pair whose two frames do
  * not show the same scene (a cut, a cold start, a channel change) has no vectors that mean anything, and hardly any pixel
  * passes the compensated interpolator's match gate; moving content of every kind passes it almost everywhere (DESIGN.md

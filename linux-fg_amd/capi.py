@@ -156,6 +156,9 @@ SIGNATURES = {
     "lfg_set_bidirectional": (_i, [_vp, _i]),
     "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_vector_refinement": (_i, [_vp, _i]),
+    "lfg_frame_halve": (_i, [_vp, _FP, _FP]),
+    "lfg_motion_expand": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
+    "lfg_set_half_resolution_motion": (_i, [_vp, _i]),
     "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
     "lfg_cut_fallback": (_i, [_vp, _FP, _FP, _vp, _i, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
     "lfg_set_cut_detection": (_i, [_vp, _i]),
@@ -621,6 +624,21 @@ class Context:
         """-1 (default: off) or 0..2: lfg_motion_refine with that radius between the estimator and the interpolator of
         interpolate_frames[_multi]."""
         self._check(self.lib.lfg_set_vector_refinement(self.h, int(radius)), "lfg_set_vector_refinement")
+
+    def frame_halve(self, src: Frame, dst: Frame):
+        """lfg_frame_halve: dst, ceil(W / 2) x ceil(H / 2), is the rounded 2 x 2 mean of src (the pyramid's level rule)."""
+        self._check(self.lib.lfg_frame_halve(self.h, ctypes.byref(src), ctypes.byref(dst)), "lfg_frame_halve")
+
+    def motion_expand(self, prev: Frame, curr: Frame, mv_low: Frame, mv_out: Frame, radius: int = 1):
+        """lfg_motion_expand: a W x H field from the ceil(W / 2) x ceil(H / 2) field mv_low.  Each pixel takes the doubled vector
+        of the 3 x 3 coarse neighbours above it that fits its (2 radius + 1)^2 window best, then the best of its +-1 steps."""
+        self._check(self.lib.lfg_motion_expand(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv_low),
+                                               ctypes.byref(mv_out), int(radius)), "lfg_motion_expand")
+
+    def set_half_resolution_motion(self, radius: int):
+        """-1 (default: off) or 0..2: interpolate_frames[_multi] run the selected estimator on both frames halved and
+        lfg_motion_expand with that radius in its place."""
+        self._check(self.lib.lfg_set_half_resolution_motion(self.h, int(radius)), "lfg_set_half_resolution_motion")
 
     # -- scene-cut detection.  A record is 24 bytes of device memory: here a 6 x 1 RGBA8 frame, so upload() and download()
     # move it (write_pair_record / read_pair_record).

@@ -136,7 +136,7 @@ hipError_t sync_lanes(lfg_context *ctx) {
     return e;
 }
 
-// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, mid_tmp), at this size: kept while the size stays, made again when it
+// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, half_prev, half_curr, mv_half, mid_tmp), at this size: kept while the size stays, made again when it
 // changes.  The test comes first because lfg_frame_destroy waits for every lane.  (frame_manager.cpp:226-230)
 int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, uint32_t format) {
     if (f.data && f.width == width && f.height == height) return LFG_OK;
@@ -479,7 +479,7 @@ namespace {
 void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
-    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.mid_tmp})      // (lane_frame)
+    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.half_prev, &l.half_curr, &l.mv_half, &l.mid_tmp})      // (lane_frame)
         if (f->data && f->owned) (void)hipFree(f->data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
@@ -1128,13 +1128,32 @@ constexpr float kFramesSearchRadius = 16.0f;
 
 // The vectors the generated frames are made from, on the selected lane: the selected estimator's in mv_tmp, and with
 // lfg_set_vector_refinement their refinement in mv_refined.  The estimator is enqueued before mv_refined is made: making
-// a frame can wait for every lane.
+// a frame can wait for every lane.  With lfg_set_half_resolution_motion the estimator runs on both frames halved, into the
+// lane's half-size temporaries, and lfg_motion_expand writes `estimated` from its vectors.
 int frame_vectors_into(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame &estimated, lfg_frame &refined,
                        const lfg_frame **vectors) {
     int rc = lane_frame(ctx, estimated, curr->width, curr->height, LFG_FORMAT_MV_S8X2);
     if (rc != LFG_OK) return fail(ctx, rc, "Failed to create motion vectors frame");
-    rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &estimated, 2, 16, 2)
-                                                 : lfg_motion(ctx, prev, curr, &estimated, kFramesBlockSize, kFramesSearchRadius);
+    if (ctx->half_res_radius >= 0) {
+        lfg_lane_state &cur = ctx->cur();
+        const uint32_t hw = (curr->width + 1u) / 2u, hh = (curr->height + 1u) / 2u;
+        rc = lane_frame(ctx, cur.half_prev, hw, hh, LFG_FORMAT_RGBA8_UNORM);
+        if (rc == LFG_OK) rc = lane_frame(ctx, cur.half_curr, hw, hh, LFG_FORMAT_RGBA8_UNORM);
+        if (rc == LFG_OK) rc = lane_frame(ctx, cur.mv_half, hw, hh, LFG_FORMAT_MV_S8X2);
+        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create the half-resolution motion frames");
+        if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !same_size(prev, curr))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: prev and curr must be non-empty RGBA8 frames of one size");
+        rc = lfg_frame_halve(ctx, prev, &cur.half_prev);
+        if (rc == LFG_OK) rc = lfg_frame_halve(ctx, curr, &cur.half_curr);
+        if (rc == LFG_OK)
+            rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID
+                     ? lfg_motion_pyramid(ctx, &cur.half_prev, &cur.half_curr, &cur.mv_half, 1, 16, 2)
+                     : lfg_motion(ctx, &cur.half_prev, &cur.half_curr, &cur.mv_half, kFramesBlockSize, kFramesSearchRadius);
+        if (rc == LFG_OK) rc = lfg_motion_expand(ctx, prev, curr, &cur.mv_half, &estimated, ctx->half_res_radius);
+    } else {
+        rc = ctx->estimator == LFG_ESTIMATOR_PYRAMID ? lfg_motion_pyramid(ctx, prev, curr, &estimated, 2, 16, 2)
+                                                     : lfg_motion(ctx, prev, curr, &estimated, kFramesBlockSize, kFramesSearchRadius);
+    }
     if (rc != LFG_OK) return rc;
     *vectors = &estimated;
     if (ctx->refine_radius < 0) return LFG_OK;
@@ -1210,7 +1229,7 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
     }
     // The fused motion kernels are the full search's and write the shader's interpolation: every other setting takes the stages.
     if (ctx->fuse_motion_interpolate && ctx->estimator == LFG_ESTIMATOR_FULL_SEARCH && ctx->refine_radius < 0 &&
-        ctx->interpolator == LFG_INTERPOLATOR_SHADER) {
+        ctx->half_res_radius < 0 && ctx->interpolator == LFG_INTERPOLATOR_SHADER) {
         // The north-star order: the motion kernels write the generated frame from the vectors while they
         // hold them; the vector frame -- this call's temporary -- is not written at all.  `out` is checked as lfg_interpolate
         // checks it; whatever the fused path does not cover (see motion_run) goes on to lfg_interpolate.
@@ -1545,6 +1564,55 @@ LFG_EXPORT int lfg_set_vector_refinement(lfg_context *ctx, int radius) {
     if (!ctx) return LFG_ERR_INVALID;
     if (radius < -1 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_set_vector_refinement: radius must be -1 (off) or in [0, 2]");
     ctx->refine_radius = radius;
+    return LFG_OK;
+}
+
+// ---- half-resolution motion (motion_expand.hip)
+
+LFG_EXPORT int lfg_frame_halve(lfg_context *ctx, const lfg_frame *in, lfg_frame *out) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_halve: in and out must be non-empty RGBA8");
+    if (out->width != (in->width + 1u) / 2u || out->height != (in->height + 1u) / 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_halve: out must be ceil(W / 2) x ceil(H / 2)");
+    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_halve: RGBA8 frames must be 4-byte aligned");
+    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_halve: out overlaps in");
+    StageTimer timer(ctx, LFG_STAGE_MOTION);
+    hipError_t e = lfg::launch_frame_halve(ctx->cur().stream, *in, *out);
+    if (e != hipSuccess) return fail_hip(ctx, e, "frame halve kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_motion_expand(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv_low,
+                                 lfg_frame *mv_out, int radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) ||
+        !frame_ok(mv_low, LFG_FORMAT_MV_S8X2) || !frame_ok(mv_out, LFG_FORMAT_MV_S8X2))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_expand: prev/curr must be RGBA8 and mv_low/mv_out MV_S8X2, all non-empty");
+    if (!same_size(prev, curr) || !same_size(curr, mv_out))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_expand: prev, curr and mv_out differ in size");
+    if (mv_low->width != (curr->width + 1u) / 2u || mv_low->height != (curr->height + 1u) / 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_expand: mv_low must be ceil(W / 2) x ceil(H / 2)");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u ||
+        (mv_low->pitch | mv_out->pitch) % 2u || ((uintptr_t)mv_low->data | (uintptr_t)mv_out->data) % 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_expand: RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
+    if (frames_overlap(mv_out, prev) || frames_overlap(mv_out, curr) || frames_overlap(mv_out, mv_low))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_expand: mv_out overlaps an input");
+    if (radius < 0 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_expand: radius must be in [0, 2]");
+    StageTimer timer(ctx, LFG_STAGE_MOTION);
+    hipError_t e = lfg::launch_motion_expand(ctx->cur().stream, *prev, *curr, *mv_low, *mv_out, radius);
+    if (e != hipSuccess) return fail_hip(ctx, e, "motion expand kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_set_half_resolution_motion(lfg_context *ctx, int radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (radius < -1 || radius > 2)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_half_resolution_motion: radius must be -1 (off) or in [0, 2]");
+    ctx->half_res_radius = radius;
     return LFG_OK;
 }
 

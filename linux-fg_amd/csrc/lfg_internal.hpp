@@ -177,6 +177,7 @@ struct lfg_lane_state {
     lfg_frame mv_tmp{};                        // temporary of lfg_interpolate_frames
     lfg_frame mv_refined{};                    // ... and its refined vectors (lfg_set_vector_refinement), made on demand
     lfg_frame mv_bwd{}, mv_bwd_refined{};      // ... and the same two measured from curr to prev (lfg_set_bidirectional), made on demand
+    lfg_frame half_prev{}, half_curr{}, mv_half{};   // ... and both frames halved and their vectors (lfg_set_half_resolution_motion), made on demand
     lfg_frame mid_tmp{};                       // temporary of lfg_interpolate_scale where the fused kernel does not apply
     // prefiltered motion path: scratch for one frame size, grown on demand
     uint8_t *motion_ws = nullptr;
@@ -226,6 +227,7 @@ struct lfg_context {
     int static_tolerance = -1;                 // lfg_interpolate_frames[_multi]: lfg_static_mask's tolerance, -1 = off (lfg_set_static_protection)
     int generation = 0;                        // lfg_interpolate_frames[_multi]: LFG_GENERATION_INTERPOLATE / _EXTRAPOLATE (lfg_set_generation)
     int bidir_tolerance = -1;                  // lfg_interpolate_frames[_multi]: the bidirectional route's tolerance, -1 = off (lfg_set_bidirectional)
+    int half_res_radius = -1;                  // lfg_interpolate_frames[_multi]: lfg_motion_expand's radius, -1 = off (lfg_set_half_resolution_motion)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -343,6 +345,11 @@ hipError_t launch_interpolate_compensated_bidirectional(hipStream_t s, const lfg
 hipError_t launch_motion_consistency(hipStream_t s, const lfg_frame &a, const lfg_frame &b, int tolerance, const lfg_mask &out);
 // Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
+                                const lfg_frame &mvOut, int radius);
+// Half-resolution motion (motion_expand.hip): the pyramid's level rule for one frame into a pitched output, and mv_out(q) = the
+// best-fitting doubled vector of mv_low's 3 x 3 neighbours above q, then the best of its +-1 steps; one launch each.
+hipError_t launch_frame_halve(hipStream_t s, const lfg_frame &in, const lfg_frame &out);
+hipError_t launch_motion_expand(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvLow,
                                 const lfg_frame &mvOut, int radius);
 // Scene-cut detection (pair_stats.hip): launch_pair_match clears the 24-byte record `stats` and enqueues the fixed grid that
 // fills it; launch_cut_fallback enqueues the kernel that reads it and, on a cut, copies prev or curr over every output.

@@ -37,6 +37,14 @@ bool FrameManager::SetBidirectional(int tolerance) {
     return true;
 }
 
+bool FrameManager::SetHalfResolutionMotion(int radius) {
+    if (lfg_set_half_resolution_motion(Ctx(), radius) != LFG_OK) {
+        LOG_ERROR("Failed to set half-resolution motion: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
+        return false;
+    }
+    return true;
+}
+
 bool FrameManager::CreateFrame(Frame& frame, uint32_t width, uint32_t height) {
     lfg_frame f{};
     const uint32_t format = frame.format;                    // RGBA8 unless the caller asked otherwise

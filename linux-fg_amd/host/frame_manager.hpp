@@ -76,6 +76,11 @@ public:
     // vector projects only where the two fields agree within `tolerance` (the reference has no such mode).
     bool SetBidirectional(int tolerance);
 
+    // Half-resolution motion in the four calls above (lfg_set_half_resolution_motion): -1 (default) off; 0 .. 2, the selected
+    // estimator runs on both frames halved and lfg_motion_expand carries its field to full size with this window radius (the
+    // reference has no such mode).
+    bool SetHalfResolutionMotion(int radius);
+
     // The one exchange of the multi-GPU path: broadcast a frame from rank `root` to every rank (asynchronous, on the
     // device context's communication stream) and make later work on the compute queue wait for it.
     bool BroadcastFrame(Frame& frame, int root);

@@ -53,6 +53,9 @@ static void PrintUsage() {
               << "                           a vector projects only where the two fields agree within T in L1, and both frames' grids\n"
               << "                           project; doubles the motion stage.  No effect with --interpolator shader, --generation\n"
               << "                           extrapolate or --protect-static)\n"
+              << "  --half-res-motion R      Half-resolution motion (default -1: off; 0..2: the estimator runs on both frames halved and\n"
+              << "                           each pixel takes the doubled vector of the 3 x 3 coarse neighbours that fits its (2R+1)^2\n"
+              << "                           window best, then the best of its +-1 steps; --motion pyramid then searches one level less)\n"
               << "  --sharpen S              Contrast-limited sharpening of every presented frame, real and generated alike (default 0: off;\n"
               << "                           1..64: strength in 64ths of the classic 5-point kernel, each pixel kept within the range of\n"
               << "                           itself and its four neighbours).  Applied to a copy just before the read-back: motion, masks and\n"
@@ -106,7 +109,7 @@ int main(int argc, char* argv[]) {
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
     int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1, staticTolerance = -1,
-        generation = LFG_GENERATION_INTERPOLATE, bidirectional = -1;
+        generation = LFG_GENERATION_INTERPOLATE, bidirectional = -1, halfResMotion = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false, evaluate = false, inputNv12 = false, outputNv12 = false;
@@ -183,6 +186,12 @@ int main(int argc, char* argv[]) {
             const long t = strtol(argv[++i], &end, 10);
             if (!end || end == argv[i] || *end != '\0' || t < -1 || t > 64) { LOG_ERROR("Invalid --bidirectional (-1, or 0 to 64)"); return 1; }
             bidirectional = (int)t;
+        }
+        else if (strcmp(argv[i], "--half-res-motion") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long r = strtol(argv[++i], &end, 10);
+            if (!end || end == argv[i] || *end != '\0' || r < -1 || r > 2) { LOG_ERROR("Invalid --half-res-motion (-1, 0, 1 or 2)"); return 1; }
+            halfResMotion = (int)r;
         }
         else if (strcmp(argv[i], "--sharpen") == 0 && i + 1 < argc) {
             char* end = nullptr;
@@ -300,7 +309,7 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     if (!FrameManager::Get().Initialize(config.outputWidth, config.outputHeight) || !FrameManager::Get().SetGeneration(generation) ||
-        !FrameManager::Get().SetBidirectional(bidirectional)) {
+        !FrameManager::Get().SetBidirectional(bidirectional) || !FrameManager::Get().SetHalfResolutionMotion(halfResMotion)) {
         LOG_ERROR("Failed to initialize frame manager");
         HipContext::Get().Cleanup();
         return 1;
@@ -316,10 +325,11 @@ int main(int argc, char* argv[]) {
         FrameManager::Get().Cleanup();
         HipContext::Get().Cleanup();
         if (!ok) { LOG_ERROR("Evaluation failed: ", Logger::Get().GetLastError()); return 1; }
-        char filterField[80] = "";
+        char filterField[112] = "";
         int used = 0;
         if (config.scaleFilter >= 0) used = snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
-        if (bidirectional >= 0) snprintf(filterField + used, sizeof filterField - (size_t)used, "\"bidirectional\": %d, ", bidirectional);
+        if (bidirectional >= 0) used += snprintf(filterField + used, sizeof filterField - (size_t)used, "\"bidirectional\": %d, ", bidirectional);
+        if (halfResMotion >= 0) snprintf(filterField + used, sizeof filterField - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
         printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
                "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
                "\"input_format\": \"rgba\", \"output_format\": \"rgba\", \"protect_static\": %d, %s"
@@ -392,15 +402,17 @@ int main(int argc, char* argv[]) {
     if (config.sharpen > 0) snprintf(sharpenField, sizeof sharpenField, "\"sharpen\": %u, ", config.sharpen);
     char filterField[48] = "";
     if (config.scaleFilter >= 0) snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
-    char bidirectionalField[32] = "";
-    if (bidirectional >= 0) snprintf(bidirectionalField, sizeof bidirectionalField, "\"bidirectional\": %d, ", bidirectional);
+    char routeFields[64] = "";
+    int used = 0;
+    if (bidirectional >= 0) used = snprintf(routeFields, sizeof routeFields, "\"bidirectional\": %d, ", bidirectional);
+    if (halfResMotion >= 0) snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
            "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, %s%s%s"
            "\"note\": \"includes %s, PCIe upload and readback\"}\n",
            frames, (unsigned long long)presented, (unsigned long long)generated, (unsigned long long)cuts, sec, presented / sec,
            (unsigned long long)checksum, syncPresent ? "false" : "true", replay, presentNull ? "true" : "false", inFlight,
-           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance, sharpenField, filterField, bidirectionalField,
+           inputNv12 ? "nv12" : "rgba", outputNv12 ? "nv12" : "rgba", staticTolerance, sharpenField, filterField, routeFields,
            replay > 0 ? "one memcpy per input frame into the staging slot" : "host frame synthesis");
     return 0;
 }
