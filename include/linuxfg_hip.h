@@ -525,6 +525,34 @@ int  lfg_interpolate_compensated_bidirectional_multi(lfg_context *ctx, const lfg
  * Any other value: LFG_ERR_INVALID and no change. */
 int  lfg_set_bidirectional(lfg_context *ctx, int tolerance);
 
+/* Hole-fill reach beyond 16 px, opt-in: the fill plane.  No reference counterpart.  The hole walk of the three interpolating
+ * calls above stops after 16 pixels and then fills with (0, 0); vectors of up to 127 px open holes wider than 32 px, whose
+ * middle then shows doubled or misplaced background.  The fill plane gives every pixel its fill key
+ * from two scan passes over K whose cost does not depend on how deep a hole is.  Integer arithmetic only.
+ *   fill(x, y; reach, pass_static): in each of the directions +x, -x, +y, -y take the nearest pixel at distance 1 .. reach
+ *   inside the image whose word in K is a donor.  A word is a donor if it is not the hole word 0xFFFFFFFF; with pass_static it
+ *   must also not be the static word 0.  Of the donors found, at most four, the result is the smallest walk-order key
+ *   ((vx^2 + vy^2) << 16) | ((vy + 128) << 8) | (vx + 128) -- the stored key with its high half replaced by 65535 minus it.
+ *   If no direction has a donor the result is the hole word, which the sampling kernels read as the vector (0, 0).  The pixel
+ *   itself is never its own donor, and the plane is defined at every pixel, holes or not.  At reach 16, and at every hole, this
+ *   is the hole walk of lfg_interpolate_compensated (pass_static = 0) and of lfg_interpolate_compensated_masked (1), exactly.
+ * lfg_hole_fill_plane: the two passes alone.  keys and plane are RGBA8 frames used as one 32-bit word per pixel, pitch
+ * honoured, as lfg_frame_diff uses a frame for its record: the same size, 4-byte aligned (data and pitch), not overlapping;
+ * 1 <= reach <= LFG_HOLE_REACH_MAX (twice the longest vector the word holds); pass_static 0 or 1.  Any violation or a NULL
+ * pointer returns LFG_ERR_INVALID before anything is enqueued.  Two launches on the selected lane (row pass, column pass); keys
+ * is only read; keeps no device memory; outside the stage timers.
+ * lfg_set_hole_reach: -1 (default): off; every path enqueues and allocates what it did.  1 .. LFG_HOLE_REACH_MAX:
+ * lfg_interpolate_compensated[_multi], lfg_interpolate_compensated_masked[_multi] (pass_static = 1) and
+ * lfg_interpolate_compensated_bidirectional[_multi] -- called directly or by lfg_interpolate_frames[_multi] -- run, per factor,
+ * clear K, project, fill plane, and a sampling kernel that takes a hole's vector from the plane: their definitions word for
+ * word with "k = 1 .. 16" read as "k = 1 .. reach".  The plane is one more per-lane buffer of 4 * W * H bytes, grown on
+ * demand and freed with the lane.  Any other value: LFG_ERR_INVALID and no change.  The shader interpolator ignores the
+ * setting, and so does extrapolation (lfg_extrapolate_compensated[_multi], LFG_GENERATION_EXTRAPOLATE): its walk keeps the
+ * step count for the donor and is another algorithm, which stays at 16. */
+#define LFG_HOLE_REACH_MAX 255
+int  lfg_hole_fill_plane(lfg_context *ctx, const lfg_frame *keys, int reach, int pass_static, lfg_frame *plane);
+int  lfg_set_hole_reach(lfg_context *ctx, int reach);
+
 /* Per-pixel vector refinement, opt-in, between motion estimation and interpolation.  No reference counterpart.  Both
  * estimators give each pixel the vector of the 8 x 8 block around it, so near a moving edge a band of up to ~4 px takes the
  * other side's vector; this picks, for each pixel, the nearby vector that fits a small window around that pixel best.

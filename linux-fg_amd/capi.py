@@ -24,6 +24,7 @@ ESTIMATOR_FULL_SEARCH, ESTIMATOR_PYRAMID = 0, 1
 INTERPOLATOR_SHADER, INTERPOLATOR_COMPENSATED = 0, 1
 GENERATION_INTERPOLATE, GENERATION_EXTRAPOLATE = 0, 1
 DEFAULT_MATCH_SAD = 48
+HOLE_REACH_MAX = 255
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
 CHROMA_REPLICATE, CHROMA_LEFT = 0, 1
@@ -154,6 +155,8 @@ SIGNATURES = {
     "lfg_interpolate_compensated_bidirectional_multi": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.POINTER(_FP),
                                                              ctypes.POINTER(ctypes.c_float), _u32, _i, _i]),
     "lfg_set_bidirectional": (_i, [_vp, _i]),
+    "lfg_hole_fill_plane": (_i, [_vp, _FP, _i, _i, _FP]),
+    "lfg_set_hole_reach": (_i, [_vp, _i]),
     "lfg_motion_refine": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_vector_refinement": (_i, [_vp, _i]),
     "lfg_frame_halve": (_i, [_vp, _FP, _FP]),
@@ -613,6 +616,18 @@ class Context:
         """-1 (default): off.  0 .. 64: with INTERPOLATOR_COMPENSATED, GENERATION_INTERPOLATE and static protection off,
         interpolate_frames[_multi] measure the pair both ways and run the bidirectional interpolation with this tolerance."""
         self._check(self.lib.lfg_set_bidirectional(self.h, int(tolerance)), "lfg_set_bidirectional")
+
+    def hole_fill_plane(self, keys: Frame, plane: Frame, reach: int, pass_static: bool = False):
+        """The fill plane of a key image (lfg_hole_fill_plane): both RGBA8 frames hold one 32-bit word per pixel (upload and
+        download them as (H, W, 4) uint8 views of uint32 arrays).  plane(x, y) = the smallest walk-order key of the nearest
+        donors within `reach` in the four axis directions, the hole word where there is none."""
+        self._check(self.lib.lfg_hole_fill_plane(self.h, ctypes.byref(keys), int(reach), int(bool(pass_static)), ctypes.byref(plane)),
+                    "lfg_hole_fill_plane")
+
+    def set_hole_reach(self, reach: int):
+        """-1 (default): off, the 16-pixel hole walk.  1 .. HOLE_REACH_MAX: the compensated, masked and bidirectional
+        interpolations fill their holes from a fill plane of this reach; extrapolation and the shader interpolator ignore it."""
+        self._check(self.lib.lfg_set_hole_reach(self.h, int(reach)), "lfg_set_hole_reach")
 
     def motion_refine(self, prev: Frame, curr: Frame, mv_in: Frame, mv_out: Frame, radius: int = 1):
         """Per-pixel vector refinement (lfg_motion_refine): each pixel takes, of the vectors of mv_in at it and 4 or 8 px

@@ -16,6 +16,8 @@
 //                                give the same K in either order;
 //   bidir_sample_kernel          one thread per output pixel: K, the hole walk where K is a hole, both bilinear fetches, the
 //                                symmetric hole rule, the blend.  It never writes K.
+// Under lfg_set_hole_reach hole_fill.hip's two passes run before the third launch, which is then bidir_sample_plane_kernel: the
+// same body with one load of the fill plane where the walk was.
 //
 // Traffic per pixel and factor: 4 (clear) + 2 x (2 (own vector) + 4 (own texel) + 4 (gathered far texel) + 2 (gathered other
 // vector) + 4 (atomic)) in the projections, 4 (K) + 8 (two fetches, mostly cached neighbours) + 4 (out) in the sampling:
@@ -45,17 +47,19 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_project_kernel(
     atomicMin(keys + (size_t)dy * (size_t)W + (size_t)dx, key);       // result unused: one global_atomic_umin
 }
 
-__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_sample_kernel(
+// Plane: a hole takes its vector from the fill plane `fill` (hole_fill.hip), one load, instead of walking K.
+template <bool Plane>
+__device__ __forceinline__ void bidir_sample(
         const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
         const uint8_t *__restrict__ fwd, size_t fwdPitch, const uint8_t *__restrict__ bwd, size_t bwdPitch,
-        const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad, int tolerance, uint8_t *__restrict__ out,
-        size_t outPitch) {
+        const uint32_t *__restrict__ keys, const uint32_t *__restrict__ fill, int W, int H, float t, int matchSad, int tolerance,
+        uint8_t *__restrict__ out, size_t outPitch) {
     const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
     if (x >= W || y >= H) return;
     const float s = 1.0f - t;
     uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
     const bool hole = key == kMcHole;
-    if (hole) key = mc_fill_vector<false>(keys, W, H, x, y);
+    if (hole) key = Plane ? mc_fill_from_plane(fill, W, x, y) : mc_fill_vector<false>(keys, W, H, x, y);
     const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
@@ -80,6 +84,24 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_sample_kernel(
     mc_store_inside_or_blend(sp, tp, sc, tc, only, t, out, outPitch, x, y);
 }
 
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_sample_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ fwd, size_t fwdPitch, const uint8_t *__restrict__ bwd, size_t bwdPitch,
+        const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad, int tolerance, uint8_t *__restrict__ out,
+        size_t outPitch) {
+    bidir_sample<false>(prev, prevPitch, curr, currPitch, fwd, fwdPitch, bwd, bwdPitch, keys, nullptr, W, H, t, matchSad, tolerance, out,
+                        outPitch);
+}
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void bidir_sample_plane_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ fwd, size_t fwdPitch, const uint8_t *__restrict__ bwd, size_t bwdPitch,
+        const uint32_t *__restrict__ keys, const uint32_t *__restrict__ fill, int W, int H, float t, int matchSad, int tolerance,
+        uint8_t *__restrict__ out, size_t outPitch) {
+    bidir_sample<true>(prev, prevPitch, curr, currPitch, fwd, fwdPitch, bwd, bwdPitch, keys, fill, W, H, t, matchSad, tolerance, out,
+                       outPitch);
+}
+
 // out(q) = 255 where a(q) is consistent with b, 0 elsewhere: one byte per thread, the W bytes of each row and no more.
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void motion_consistency_kernel(
         const uint8_t *__restrict__ a, size_t aPitch, const uint8_t *__restrict__ b, size_t bPitch, int W, int H, int tolerance,
@@ -91,10 +113,11 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void motion_consistency_kern
 
 }  // namespace
 
-// Clear K, project forward, project backward, sample.
+// Clear K, project forward, project backward, sample.  With `fill` (lfg_set_hole_reach): the fill plane of `reach` into `fill`
+// (W * H words, hole_fill.hip) before the sampling, and the kernel that reads it at holes.
 hipError_t launch_interpolate_compensated_bidirectional(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &fwd,
                                                         const lfg_frame &bwd, const lfg_frame &out, float factor, int matchSad,
-                                                        int tolerance, uint32_t *keys) {
+                                                        int tolerance, uint32_t *keys, uint32_t *fill, int reach) {
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
@@ -106,6 +129,15 @@ hipError_t launch_interpolate_compensated_bidirectional(hipStream_t s, const lfg
         e = mc_launch(bidir_project_kernel<true>, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
                       (size_t)curr.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch,
                       W, H, factor, matchSad, tolerance, keys);
+    if (e == hipSuccess && fill) {
+        e = launch_hole_fill_plane(s, keys, (size_t)W, fill, (size_t)W, W, H, reach, false);
+        if (e == hipSuccess)
+            e = mc_launch(bidir_sample_plane_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
+                          (int)curr.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch,
+                          (const uint32_t *)keys, (const uint32_t *)fill, W, H, factor, matchSad, tolerance, (uint8_t *)out.data,
+                          (size_t)out.pitch);
+        return e;
+    }
     if (e == hipSuccess)
         e = mc_launch(bidir_sample_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
                       (int)curr.pitch, (const uint8_t *)fwd.data, (size_t)fwd.pitch, (const uint8_t *)bwd.data, (size_t)bwd.pitch,

@@ -12,6 +12,8 @@
 // that share their hole walk and the end of a pixel (see there).  The hole and static words, the reads, the match gate, the
 // walk (mc_fill_vector), the end of a pixel (mc_store_inside_or_blend) and the launchers' steps are lfg_mc.hpp's, shared with
 // extrapolate_mc.hip and interpolate_bidir.hip; the key, its decode and the hole walk's order are lfg_vector_word.hpp's.
+// Under lfg_set_hole_reach the launchers put hole_fill.hip's two passes between the launches and run mc_interpolate_plane_kernel
+// or mc_interpolate_masked_plane_kernel: the same bodies with one load of the fill plane where the walk was.
 //
 // Traffic per pixel and factor: 4 (clear) + 2 (mv) + 4 (curr) + 4 (gathered prev) + 4 (atomic) in the projection, 4 (K) + 8
 // (two fetches, mostly cached neighbours) + 4 (out) in the interpolation: 34 bytes, 280 MB at 4K.
@@ -51,17 +53,20 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_kernel(
 // mc_store_inside_or_blend), as bidir_sample_kernel does.  They are not one body: what lies between differs in kind (the
 // static shortcut, the mask bytes and the fetch rule are the masked kernel's alone) and in place (the unmasked kernel
 // computes the clamped position inside the hole branch, the masked one for every pixel).  One template <bool Masked> body
-// had to move those, and was not kept.
-__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
+// had to move those, and was not kept.  Each of the two is a body over <bool Plane> under two wrappers:
+// the kernel of before, whose machine code the template leaves as it was, and the one that reads the fill plane.
+// Plane: a hole takes its vector from the fill plane `fill` (hole_fill.hip), one load, instead of walking K.
+template <bool Plane>
+__device__ __forceinline__ void mc_interpolate(
         const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
-        const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad,
-        uint8_t *__restrict__ out, size_t outPitch) {
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ fill, int W,
+        int H, float t, int matchSad, uint8_t *__restrict__ out, size_t outPitch) {
     const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
     if (x >= W || y >= H) return;
     const float s = 1.0f - t;
     uint32_t key = keys[(size_t)y * (size_t)W + (size_t)x];
     const bool hole = key == kMcHole;
-    if (hole) key = mc_fill_vector<false>(keys, W, H, x, y);
+    if (hole) key = Plane ? mc_fill_from_plane(fill, W, x, y) : mc_fill_vector<false>(keys, W, H, x, y);
     const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
@@ -80,6 +85,20 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
     mc_store_inside_or_blend(sp, tp, sc, tc, only, t, out, outPitch, x, y);
 }
 
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad,
+        uint8_t *__restrict__ out, size_t outPitch) {
+    mc_interpolate<false>(prev, prevPitch, curr, currPitch, mv, mvPitch, keys, nullptr, W, H, t, matchSad, out, outPitch);
+}
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_plane_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ fill, int W,
+        int H, float t, int matchSad, uint8_t *__restrict__ out, size_t outPitch) {
+    mc_interpolate<true>(prev, prevPitch, curr, currPitch, mv, mvPitch, keys, fill, W, H, t, matchSad, out, outPitch);
+}
+
 __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_masked_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch, int W, int H, float t,
@@ -87,10 +106,12 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_project_masked_kerne
     mc_project<true>(prev, prevPitch, curr, currPitch, mv, mvPitch, mask, maskPitch, W, H, t, matchSad, keys);
 }
 
-__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_kernel(
+template <bool Plane>
+__device__ __forceinline__ void mc_interpolate_masked(
         const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
         const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch,
-        const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad, uint8_t *__restrict__ out, size_t outPitch) {
+        const uint32_t *__restrict__ keys, const uint32_t *__restrict__ fill, int W, int H, float t, int matchSad,
+        uint8_t *__restrict__ out, size_t outPitch) {
     const int x = (int)(blockIdx.x * kMcBlockX + threadIdx.x), y = (int)(blockIdx.y * kMcBlockY + threadIdx.y);
     if (x >= W || y >= H) return;
     const float s = 1.0f - t;
@@ -102,7 +123,7 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_k
         return;
     }
     const bool hole = key == kMcHole;
-    if (hole) key = mc_fill_vector<true>(keys, W, H, x, y);    // the walk also passes over static pixels
+    if (hole) key = Plane ? mc_fill_from_plane(fill, W, x, y) : mc_fill_vector<true>(keys, W, H, x, y);    // the walk also passes over static pixels
     const Mv u = mv_order_decode(key);
     const float px = (float)x + 0.5f, py = (float)y + 0.5f;
     const float Px = px + (float)u.x * t, Py = py + (float)u.y * t;
@@ -124,11 +145,30 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_k
     mc_store_inside_or_blend(sp, tp, sc, tc, only, t, out, outPitch, x, y);
 }
 
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch,
+        const uint32_t *__restrict__ keys, int W, int H, float t, int matchSad, uint8_t *__restrict__ out, size_t outPitch) {
+    mc_interpolate_masked<false>(prev, prevPitch, curr, currPitch, mv, mvPitch, mask, maskPitch, keys, nullptr, W, H, t, matchSad, out,
+                                 outPitch);
+}
+
+__global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mc_interpolate_masked_plane_kernel(
+        const uint8_t *__restrict__ prev, int prevPitch, const uint8_t *__restrict__ curr, int currPitch,
+        const uint8_t *__restrict__ mv, size_t mvPitch, const uint8_t *__restrict__ mask, size_t maskPitch,
+        const uint32_t *__restrict__ keys, const uint32_t *__restrict__ fill, int W, int H, float t, int matchSad,
+        uint8_t *__restrict__ out, size_t outPitch) {
+    mc_interpolate_masked<true>(prev, prevPitch, curr, currPitch, mv, mvPitch, mask, maskPitch, keys, fill, W, H, t, matchSad, out,
+                                outPitch);
+}
+
 }  // namespace
 
-// Each launcher: clear K, project, interpolate.
+// Each launcher: clear K, project, interpolate.  With `fill` (lfg_set_hole_reach): clear K, project, the fill plane of `reach`
+// into `fill` (W * H words, hole_fill.hip), the interpolate kernel that reads it at holes.
 hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
-                                                 const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {
+                                                 const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys,
+                                                 uint32_t *fill, int reach) {
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
@@ -136,6 +176,15 @@ hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame 
         e = mc_launch(mc_project_masked_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
                       (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint8_t *)mask.data,
                       (size_t)mask.pitch, W, H, factor, matchSad, keys);
+    if (e == hipSuccess && fill) {
+        e = launch_hole_fill_plane(s, keys, (size_t)W, fill, (size_t)W, W, H, reach, true);
+        if (e == hipSuccess)
+            e = mc_launch(mc_interpolate_masked_plane_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch,
+                          (const uint8_t *)curr.data, (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
+                          (const uint8_t *)mask.data, (size_t)mask.pitch, (const uint32_t *)keys, (const uint32_t *)fill, W, H, factor,
+                          matchSad, (uint8_t *)out.data, (size_t)out.pitch);
+        return e;
+    }
     if (e == hipSuccess)
         e = mc_launch(mc_interpolate_masked_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
                       (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint8_t *)mask.data, (size_t)mask.pitch,
@@ -144,13 +193,21 @@ hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame 
 }
 
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
-                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys) {
+                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys, uint32_t *fill, int reach) {
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
     if (e == hipSuccess)
         e = mc_launch(mc_project_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
                       (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, factor, matchSad, keys);
+    if (e == hipSuccess && fill) {
+        e = launch_hole_fill_plane(s, keys, (size_t)W, fill, (size_t)W, W, H, reach, false);
+        if (e == hipSuccess)
+            e = mc_launch(mc_interpolate_plane_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
+                          (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint32_t *)keys, (const uint32_t *)fill, W, H,
+                          factor, matchSad, (uint8_t *)out.data, (size_t)out.pitch);
+        return e;
+    }
     if (e == hipSuccess)
         e = mc_launch(mc_interpolate_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
                       (int)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, (const uint32_t *)keys, W, H, factor, matchSad,

@@ -144,7 +144,7 @@ int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, 
     return lfg_frame_create(ctx, width, height, format, &f);
 }
 
-// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys, static_mask).  `what` names the allocation in the error.
+// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys, mc_fill, static_mask).  `what` names the allocation in the error.
 template <typename T>
 int lane_buffer_grow(lfg_context *ctx, T *&buf, size_t &have, size_t need, const char *what) {
     if (need <= have) return LFG_OK;
@@ -470,6 +470,7 @@ LFG_EXPORT int lfg_context_create(int device_ordinal, lfg_context **out_ctx) {
     if (getenv("LFG_DEBUG_DYN")) ctx->knobs.debugDyn = 1;
     if (const char *m = getenv("LFG_DEBUG_DYN_DEEP")) ctx->knobs.debugDynDeep = atoi(m);
     if (const char *m = getenv("LFG_TIER_FORCE")) ctx->knobs.tierForce = atoi(m) & 1;
+    if (const char *m = getenv("LFG_FILL_BAND")) { const int v = atoi(m); if (v >= 8 && v <= 1024) ctx->knobs.fillBand = v; }
     if (const char *m = getenv("LFG_COMM_CUS")) { const int v = atoi(m); if (v == 0 || v == 8 || v == 16 || v == 24 || v == 32) ctx->knobs.commCus = v; }
     *out_ctx = ctx;
     return LFG_OK;
@@ -484,6 +485,7 @@ void lane_release(lfg_lane_state &l) {
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
     if (l.mc_keys) (void)hipFree(l.mc_keys);
+    if (l.mc_fill) (void)hipFree(l.mc_fill);
     if (l.static_mask) (void)hipFree(l.static_mask);
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
@@ -1364,14 +1366,23 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     const size_t bytes = (size_t)curr->width * curr->height * 4u;
     int rc = lane_buffer_grow(ctx, cur.mc_keys, cur.mc_keys_bytes, bytes, "hipMalloc((void **)&cur.mc_keys, bytes)");
     if (rc != LFG_OK) return rc;
+    // lfg_set_hole_reach: the three interpolating kinds fill their holes from the lane's fill plane, made per factor behind K
+    const int reach = kind == McKind::Extrapolate ? -1 : ctx->hole_reach;
+    if (reach >= 1) {
+        rc = lane_buffer_grow(ctx, cur.mc_fill, cur.mc_fill_bytes, bytes, "hipMalloc((void **)&cur.mc_fill, bytes)");
+        if (rc != LFG_OK) return rc;
+    }
+    uint32_t *const fill = reach >= 1 ? cur.mc_fill : nullptr;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
-    for (uint32_t i = 0; i < count; ++i) {                       // one key image, reused in stream order
-        hipError_t e = masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys)
+    for (uint32_t i = 0; i < count; ++i) {                       // one key image (and one fill plane), reused in stream order
+        hipError_t e = masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys,
+                                                                           fill, reach)
                        : kind == McKind::Extrapolate
                               ? lfg::launch_extrapolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys)
                        : bidir ? lfg::launch_interpolate_compensated_bidirectional(cur.stream, *prev, *curr, *mv, *bwd, *outs[i], factors[i],
-                                                                                   match_sad, tolerance, cur.mc_keys)
-                              : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys);
+                                                                                   match_sad, tolerance, cur.mc_keys, fill, reach)
+                              : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys,
+                                                                    fill, reach);
         if (e != hipSuccess) return fail_hip(ctx, e, kind == McKind::Extrapolate ? "compensated extrapolate kernel launch" : "compensated interpolate kernel launch");
     }
     return LFG_OK;
@@ -1421,6 +1432,35 @@ LFG_EXPORT int lfg_interpolate_compensated(lfg_context *ctx, const lfg_frame *pr
 LFG_EXPORT int lfg_interpolate_compensated_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
                                                  lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad) {
     return compensated_run(ctx, prev, curr, mv, nullptr, McKind::Plain, outs, factors, count, match_sad, "lfg_interpolate_compensated_multi");
+}
+
+// ---- the fill plane (hole_fill.hip)
+
+LFG_EXPORT int lfg_hole_fill_plane(lfg_context *ctx, const lfg_frame *keys, int reach, int pass_static, lfg_frame *plane) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(keys, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(plane, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_hole_fill_plane: keys and plane must be non-empty RGBA8");
+    if (!same_size(keys, plane)) return fail(ctx, LFG_ERR_INVALID, "lfg_hole_fill_plane: keys and plane differ in size");
+    if ((keys->pitch | plane->pitch) % 4u || ((uintptr_t)keys->data | (uintptr_t)plane->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_hole_fill_plane: RGBA8 frames must be 4-byte aligned");
+    if (frames_overlap(keys, plane)) return fail(ctx, LFG_ERR_INVALID, "lfg_hole_fill_plane: plane overlaps keys");
+    if (reach < 1 || reach > LFG_HOLE_REACH_MAX)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_hole_fill_plane: reach must be in [1, LFG_HOLE_REACH_MAX]");
+    if (pass_static != 0 && pass_static != 1) return fail(ctx, LFG_ERR_INVALID, "lfg_hole_fill_plane: pass_static must be 0 or 1");
+    const hipError_t e = lfg::launch_hole_fill_plane(ctx->cur().stream, (const uint32_t *)keys->data, keys->pitch / 4u, (uint32_t *)plane->data,
+                                                     plane->pitch / 4u, (int)keys->width, (int)keys->height, reach, pass_static != 0,
+                                                     ctx->knobs.fillBand);
+    if (e != hipSuccess) return fail_hip(ctx, e, "fill plane kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_set_hole_reach(lfg_context *ctx, int reach) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (reach != -1 && (reach < 1 || reach > LFG_HOLE_REACH_MAX))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_hole_reach: reach must be -1 (off) or in [1, LFG_HOLE_REACH_MAX]");
+    ctx->hole_reach = reach;
+    return LFG_OK;
 }
 
 // ---- motion-compensated extrapolation (extrapolate_mc.hip)

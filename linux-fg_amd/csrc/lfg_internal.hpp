@@ -191,6 +191,9 @@ struct lfg_lane_state {
     // lfg_interpolate_compensated: the key image K of one factor (W * H words), grown on demand
     uint32_t *mc_keys = nullptr;
     size_t mc_keys_bytes = 0;
+    // lfg_set_hole_reach: the fill plane of that key image (W * H words), grown on demand
+    uint32_t *mc_fill = nullptr;
+    size_t mc_fill_bytes = 0;
     // lfg_set_static_protection: the pair's static mask (W * H bytes), grown on demand
     uint8_t *static_mask = nullptr;
     size_t static_mask_bytes = 0;
@@ -227,6 +230,7 @@ struct lfg_context {
     int static_tolerance = -1;                 // lfg_interpolate_frames[_multi]: lfg_static_mask's tolerance, -1 = off (lfg_set_static_protection)
     int generation = 0;                        // lfg_interpolate_frames[_multi]: LFG_GENERATION_INTERPOLATE / _EXTRAPOLATE (lfg_set_generation)
     int bidir_tolerance = -1;                  // lfg_interpolate_frames[_multi]: the bidirectional route's tolerance, -1 = off (lfg_set_bidirectional)
+    int hole_reach = -1;                       // the compensated, masked and bidirectional calls: the fill plane's reach, -1 = off: the walk (lfg_set_hole_reach)
     int half_res_radius = -1;                  // lfg_interpolate_frames[_multi]: lfg_motion_expand's radius, -1 = off (lfg_set_half_resolution_motion)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
@@ -327,12 +331,20 @@ hipError_t launch_interpolate_multi(hipStream_t s, const lfg_frame &prev, const 
 size_t pyramid_workspace_bytes(uint32_t width, uint32_t height, int levels, PyramidLayout *layout);
 hipError_t launch_motion_pyramid(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
                                  int levels, int coarseRadius, int refineRadius, uint8_t *workspace, const PyramidLayout &layout);
+// The fill plane of a key image (hole_fill.hip): the row pass and the column pass, which read `keys` and write `plane`; pitches
+// in words, reach in [1, LFG_HOLE_REACH_MAX], band = rows per workgroup of the column pass (0: kFillBand, lfg_mc.hpp).
+hipError_t launch_hole_fill_plane(hipStream_t s, const uint32_t *keys, size_t keysPitchWords, uint32_t *plane, size_t planePitchWords,
+                                  int W, int H, int reach, bool passStatic, int band = 0);
 // Motion-compensated interpolation (interpolate_mc.hip): clears `keys` (W * H words), projects, interpolates; one factor.
+// The three interpolating launchers with `fill` (W * H words; lfg_set_hole_reach): the fill plane of `reach` after the
+// projection, and the sampling kernel that reads it where K is a hole.  fill == nullptr: the launches of before.
 hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
-                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
+                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys, uint32_t *fill = nullptr,
+                                          int reach = 0);
 // The same with a static mask (interpolate_mc.hip), and the mask of a pair (static_mask.hip): one launch.
 hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
-                                                 const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
+                                                 const lfg_mask &mask, const lfg_frame &out, float factor, int matchSad, uint32_t *keys,
+                                                 uint32_t *fill = nullptr, int reach = 0);
 hipError_t launch_static_mask(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, int tolerance, const lfg_mask &out);
 // Motion-compensated extrapolation (extrapolate_mc.hip): clears `keys` (W * H words), projects past time 1, samples curr; one factor.
 hipError_t launch_extrapolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
@@ -341,7 +353,7 @@ hipError_t launch_extrapolate_compensated(hipStream_t s, const lfg_frame &prev, 
 // factor.  And the forward-backward check of field `a` against field `b` on its own: one launch.
 hipError_t launch_interpolate_compensated_bidirectional(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &fwd,
                                                         const lfg_frame &bwd, const lfg_frame &out, float factor, int matchSad,
-                                                        int tolerance, uint32_t *keys);
+                                                        int tolerance, uint32_t *keys, uint32_t *fill = nullptr, int reach = 0);
 hipError_t launch_motion_consistency(hipStream_t s, const lfg_frame &a, const lfg_frame &b, int tolerance, const lfg_mask &out);
 // Per-pixel vector refinement (motion_refine.hip): mv_out(q) = the best-fitting of mv_in's 17 candidates around q; one launch.
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,

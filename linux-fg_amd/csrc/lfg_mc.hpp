@@ -3,7 +3,8 @@
 // (mc_clear_keys, mc_grid, mc_block, mc_launch), and the two halves that the three sampling kernels which blend both frames
 // have in common (mc_interpolate_kernel, mc_interpolate_masked_kernel, bidir_sample_kernel): the hole walk, mc_fill_vector,
 // and the end of a pixel, mc_store_inside_or_blend.  Both carry the names of their CPU restatements in
-// tests/compensated_model.h.  The vector word, the longest-first key that K holds (mv_longest_first_key), its decode
+// tests/compensated_model.h.  mc_fill_from_plane is what stands in the walk's place under lfg_set_hole_reach (hole_fill.hip
+// makes the plane, tests/fill_model.c restates it), and kFillBand is that file's band height.  The vector word, the longest-first key that K holds (mv_longest_first_key), its decode
 // (mv_order_decode) and the hole walks' way back to the order key (mv_key_flip_length) are lfg_vector_word.hpp's; the taps
 // are lfg_interp.hpp's.
 #pragma once
@@ -61,6 +62,14 @@ __device__ __forceinline__ uint32_t mc_fill_vector(const uint32_t *__restrict__ 
     }
     return best == kMcHole ? mv_order_key(0, 0) : best;
 }
+
+// The same from the fill plane (hole_fill.hip; lfg_set_hole_reach): the plane holds the order key already, and the hole word
+// where no direction has a donor within the reach.  One load in the walk's place.
+__device__ __forceinline__ uint32_t mc_fill_from_plane(const uint32_t *__restrict__ fill, int W, int x, int y) {
+    const uint32_t best = fill[(size_t)y * (size_t)W + (size_t)x];
+    return best == kMcHole ? mv_order_key(0, 0) : best;
+}
+constexpr int kFillBand = 64;                  // rows per workgroup of the plane's column pass
 
 // The end of an interpolated pixel.  `only` is what the caller's rules decided -- 0: nothing, 1: prev's sample alone, 2:
 // curr's alone -- and 0 falls to the inside rule: the sample whose position alone is inside the image, else the blend.

@@ -57,6 +57,7 @@ struct MotionKnobs {
     int debugDyn = 0;         // LFG_DEBUG_DYN: lfg_motion_last_stats prints the deepest private lists of the handed-over segments,
     int debugDynDeep = 14;    // LFG_DEBUG_DYN_DEEP: ... deeper than this
     int tierForce = -1;       // LFG_TIER_FORCE = 0 | 1: the persistent kernel's variant whatever the verdict (-1: by the verdict)
+    int fillBand = 0;         // LFG_FILL_BAND = 8 .. 1024: rows per workgroup of lfg_hole_fill_plane's column pass (0: kFillBand; tools/fill_bench.py's band sweep)
     int commCus = 8;          // LFG_COMM_CUS = 0 | 8 | 16 | 24 | 32: CUs a communicator keeps free of the library's own kernels (lfg_comm.cpp)
 };
 

@@ -45,6 +45,14 @@ bool FrameManager::SetHalfResolutionMotion(int radius) {
     return true;
 }
 
+bool FrameManager::SetHoleReach(int reach) {
+    if (lfg_set_hole_reach(Ctx(), reach) != LFG_OK) {
+        LOG_ERROR("Failed to set the hole reach: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
+        return false;
+    }
+    return true;
+}
+
 bool FrameManager::CreateFrame(Frame& frame, uint32_t width, uint32_t height) {
     lfg_frame f{};
     const uint32_t format = frame.format;                    // RGBA8 unless the caller asked otherwise

@@ -81,6 +81,11 @@ public:
     // reference has no such mode).
     bool SetHalfResolutionMotion(int radius);
 
+    // The hole fill's reach in the four calls above where they take the compensated, masked or bidirectional route
+    // (lfg_set_hole_reach): -1 (default) the 16 px walk; 1 .. LFG_HOLE_REACH_MAX, the fill plane of that reach (the reference
+    // has no such mode).  Extrapolated frames keep the walk.
+    bool SetHoleReach(int reach);
+
     // The one exchange of the multi-GPU path: broadcast a frame from rank `root` to every rank (asynchronous, on the
     // device context's communication stream) and make later work on the compute queue wait for it.
     bool BroadcastFrame(Frame& frame, int root);

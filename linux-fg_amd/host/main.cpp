@@ -56,6 +56,10 @@ static void PrintUsage() {
               << "  --half-res-motion R      Half-resolution motion (default -1: off; 0..2: the estimator runs on both frames halved and\n"
               << "                           each pixel takes the doubled vector of the 3 x 3 coarse neighbours that fits its (2R+1)^2\n"
               << "                           window best, then the best of its +-1 steps; --motion pyramid then searches one level less)\n"
+              << "  --hole-reach N           Reach of the compensated interpolator's hole fill (default: the 16 px walk; 1..255: a fill plane\n"
+              << "                           of two scans gives every hole the nearest vector within N px along each axis, at a cost\n"
+              << "                           that does not grow with N -- for the wide holes behind fast objects).  Needs --interpolator\n"
+              << "                           compensated; not with --generation extrapolate\n"
               << "  --sharpen S              Contrast-limited sharpening of every presented frame, real and generated alike (default 0: off;\n"
               << "                           1..64: strength in 64ths of the classic 5-point kernel, each pixel kept within the range of\n"
               << "                           itself and its four neighbours).  Applied to a copy just before the read-back: motion, masks and\n"
@@ -109,7 +113,7 @@ int main(int argc, char* argv[]) {
     std::string dumpDir, inputRaw, outputRaw, commFile;
     int ranks = 0, rank = 0, inFlight = 2;
     int estimator = LFG_ESTIMATOR_FULL_SEARCH, semantics = LFG_SEMANTICS_REFERENCE, interpolator = LFG_INTERPOLATOR_SHADER, refineRadius = -1, cutThreshold = -1, staticTolerance = -1,
-        generation = LFG_GENERATION_INTERPOLATE, bidirectional = -1, halfResMotion = -1;
+        generation = LFG_GENERATION_INTERPOLATE, bidirectional = -1, halfResMotion = -1, holeReach = -1;
     unsigned long long commNonce = getenv("LFG_COMM_NONCE") ? strtoull(getenv("LFG_COMM_NONCE"), nullptr, 0) : 0ull;
     std::vector<float> factors;
     bool syncPresent = false, presentNull = false, evaluate = false, inputNv12 = false, outputNv12 = false;
@@ -192,6 +196,12 @@ int main(int argc, char* argv[]) {
             const long r = strtol(argv[++i], &end, 10);
             if (!end || end == argv[i] || *end != '\0' || r < -1 || r > 2) { LOG_ERROR("Invalid --half-res-motion (-1, 0, 1 or 2)"); return 1; }
             halfResMotion = (int)r;
+        }
+        else if (strcmp(argv[i], "--hole-reach") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long n = strtol(argv[++i], &end, 10);
+            if (!end || end == argv[i] || *end != '\0' || n < 1 || n > LFG_HOLE_REACH_MAX) { LOG_ERROR("Invalid --hole-reach (1 to 255)"); return 1; }
+            holeReach = (int)n;
         }
         else if (strcmp(argv[i], "--sharpen") == 0 && i + 1 < argc) {
             char* end = nullptr;
@@ -289,6 +299,10 @@ int main(int argc, char* argv[]) {
         if (interpolator != LFG_INTERPOLATOR_COMPENSATED) { LOG_ERROR("--generation extrapolate needs --interpolator compensated"); return 2; }
         if (ranks > 0) { LOG_ERROR("--generation extrapolate cannot be combined with --ranks"); return 2; }
     }
+    if (holeReach >= 1) {                                       // before a context is made
+        if (interpolator != LFG_INTERPOLATOR_COMPENSATED) { LOG_ERROR("--hole-reach needs --interpolator compensated"); return 2; }
+        if (generation == LFG_GENERATION_EXTRAPOLATE) { LOG_ERROR("--hole-reach cannot be combined with --generation extrapolate"); return 2; }
+    }
     if (evaluate) {                                             // before a context is made
         const char* clash = ranks > 0 ? "--ranks" : !factors.empty() ? "--factors" : !config.enableInterpolation ? "--no-interpolation"
                           : !outputRaw.empty() ? "--output-raw" : !dumpDir.empty() ? "--dump-dir" : replay > 0 ? "--replay" : nullptr;
@@ -309,7 +323,8 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     if (!FrameManager::Get().Initialize(config.outputWidth, config.outputHeight) || !FrameManager::Get().SetGeneration(generation) ||
-        !FrameManager::Get().SetBidirectional(bidirectional) || !FrameManager::Get().SetHalfResolutionMotion(halfResMotion)) {
+        !FrameManager::Get().SetBidirectional(bidirectional) || !FrameManager::Get().SetHalfResolutionMotion(halfResMotion) ||
+        !FrameManager::Get().SetHoleReach(holeReach)) {
         LOG_ERROR("Failed to initialize frame manager");
         HipContext::Get().Cleanup();
         return 1;
@@ -329,7 +344,8 @@ int main(int argc, char* argv[]) {
         int used = 0;
         if (config.scaleFilter >= 0) used = snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
         if (bidirectional >= 0) used += snprintf(filterField + used, sizeof filterField - (size_t)used, "\"bidirectional\": %d, ", bidirectional);
-        if (halfResMotion >= 0) snprintf(filterField + used, sizeof filterField - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
+        if (halfResMotion >= 0) used += snprintf(filterField + used, sizeof filterField - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
+        if (holeReach >= 1) snprintf(filterField + used, sizeof filterField - (size_t)used, "\"hole_reach\": %d, ", holeReach);
         printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
                "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
                "\"input_format\": \"rgba\", \"output_format\": \"rgba\", \"protect_static\": %d, %s"
@@ -402,10 +418,11 @@ int main(int argc, char* argv[]) {
     if (config.sharpen > 0) snprintf(sharpenField, sizeof sharpenField, "\"sharpen\": %u, ", config.sharpen);
     char filterField[48] = "";
     if (config.scaleFilter >= 0) snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
-    char routeFields[64] = "";
+    char routeFields[96] = "";
     int used = 0;
     if (bidirectional >= 0) used = snprintf(routeFields, sizeof routeFields, "\"bidirectional\": %d, ", bidirectional);
-    if (halfResMotion >= 0) snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
+    if (halfResMotion >= 0) used += snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
+    if (holeReach >= 1) snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"hole_reach\": %d, ", holeReach);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
            "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, %s%s%s"
