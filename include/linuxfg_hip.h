@@ -52,7 +52,12 @@ typedef enum lfg_format {
      * vec4(best, 0, 1) (:56); best is always integer-valued for the integer search radii
      * the host pushes (src/frame_manager.cpp:333), so two int8 hold it losslessly at 1/8
      * of the bytes.  lfg_mv_export_rgba32f() reproduces the reference's image verbatim. */
-    LFG_FORMAT_MV_S8X2 = 1
+    LFG_FORMAT_MV_S8X2 = 1,
+    /* Motion vectors in quarter pixels, four bytes per pixel: int16 x in the low half, int16 y in the high half.  Rows are
+     * 4-byte aligned and the pitch is a multiple of 4.  A frame may hold any 16-bit values; every reader clamps each component
+     * to [-508, 508] (= 4 * 127) before use.  Written by lfg_motion_subpel, read by lfg_interpolate_compensated_subpel.  No
+     * reference counterpart. */
+    LFG_FORMAT_MV_S16X2_Q2 = 2
 } lfg_format;
 
 /* Replaces `struct Frame` {VkImage, VkDeviceMemory, VkImageView, width, height, format}
@@ -625,6 +630,70 @@ int  lfg_motion_expand(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
  *       every interpolator and generation mode.  lfg_set_fused_motion_interpolate does not apply.
  * Any other radius: LFG_ERR_INVALID and no change.  Measured cost and quality: DESIGN.md section 4.18. */
 int  lfg_set_half_resolution_motion(lfg_context *ctx, int radius);
+
+/* Quarter-pixel vectors, opt-in.  No reference counterpart.  Every other vector in the library is a whole number of pixels;
+ * content that moves by 2.5 px per frame then fails the compensated interpolator's match gate where nothing is wrong, and the
+ * two fetches of a projected pixel land half a pixel apart.  lfg_motion_subpel refines an integer field to quarter pixels and
+ * lfg_interpolate_compensated_subpel is the compensated interpolation that carries the fraction.
+ *
+ * lfg_motion_subpel: mvq_out(q) = the quarter-pixel vector near 4 mv_in(q) that fits q's window best.  Integer arithmetic
+ * only; it does not depend on lfg_set_semantics.
+ *   Inputs: prev, curr RGBA8, mv_in LFG_FORMAT_MV_S8X2 and mvq_out LFG_FORMAT_MV_S16X2_Q2, all W x H; 0 <= radius <= 2.
+ *   v = mv_in(q), a byte of -128 read as -127.
+ *   The fractional sample prevq(r, w) of a quarter-pixel vector w: i = (w.x >> 2, w.y >> 2) (arithmetic shift: the floor),
+ *   f = (w.x & 3, w.y & 3), T00 = prev(r + i), T10 = prev(r + i + (1, 0)), T01 = prev(r + i + (0, 1)), T11 = prev(r + i + (1, 1)),
+ *   a texel outside the image read as 0 in all channels; per channel
+ *       ((4 - fx)(4 - fy) T00 + fx (4 - fy) T10 + (4 - fx) fy T01 + fx fy T11 + 8) >> 4.
+ *   With f = (0, 0) this is prev(r + i) exactly.
+ *   Cost of w at q: the sum over texels r of the (2 radius + 1)^2 window centred on q, and over the four channels, of
+ *   |curr(r)_c - prevq(r, w)_c|; texels r outside the image are skipped (lfg_motion_refine's conventions).
+ *   Order: with d = w - 4v the smallest key (cost, dx^2 + dy^2, dy, dx) wins.  The integer vector wins every tie -- a fraction
+ *   has to earn its place with a strictly lower cost -- and the order is total, so neither the order of evaluation nor any
+ *   tiling changes a result.
+ *   Stage 1, half pixel: the candidates 4v + (2a, 2b), a, b in {-1, 0, 1}; the winner is h.
+ *   Stage 2, quarter pixel: the candidates h + (a, b), a, b in {-1, 0, 1}; the winner is mvq_out(q).
+ *   A candidate with a component outside [-508, 508] is dropped; 4v is always in range.
+ * Hence: every output lies within 3 quarter pixels (Chebyshev distance) of 4v; where the windows are flat the output is
+ * 4 mv_in; all texels needed lie in the (2 radius + 3)^2 block of prev around q + v.
+ * Frames: lfg_motion_refine's rules -- 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4), mv_in 2-byte aligned,
+ * mvq_out 4-byte aligned with a pitch that is a multiple of 4 -- and mvq_out must not overlap any input.  Any violation, a
+ * NULL pointer, a wrong format or size and a radius outside [0, 2] returns LFG_ERR_INVALID before anything is enqueued.  One
+ * launch on the selected lane; keeps no device memory; timed under LFG_STAGE_MOTION. */
+int  lfg_motion_subpel(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv_in,
+                       lfg_frame *mvq_out, int radius);
+/* lfg_interpolate_compensated_subpel[_multi]: lfg_interpolate_compensated[_multi] with mvq (LFG_FORMAT_MV_S16X2_Q2, any
+ * 16-bit values) in mv's place.  The definition is lfg_interpolate_compensated's word for word, with five changes:
+ *   Gate: q is matched when sum over c of |curr(q)_c - prevq(q, w)_c| <= match_sad, w = mvq(q) clamped to [-508, 508].
+ *   Projection: d = q + (dx, dy), dx = (int)floorf(((float)w.x * 0.25f) * s + 0.5f), s = 1 - t, dy likewise; a landing outside
+ *   the image is dropped.
+ *   Key order: where several pixels land on one destination the largest wx^2 + wy^2 wins, then the smallest wy, then the
+ *   smallest wx (20 + 10 + 10 bits: the key image K holds 64 bits per pixel, all ones where nothing landed).
+ *   Sampling: P.x = ((float)d.x + 0.5f) + ((float)u.x * 0.25f) * t, C.x = ((float)d.x + 0.5f) - ((float)u.x * 0.25f) * s, y
+ *   likewise; the same bilinear fetch, inside rule, blend and store.
+ *   Holes: the same four 16 px walks, each direction keeping its first non-hole; u is the smallest (|w|^2, wy, wx) of the kept
+ *   vectors, (0, 0) if none; c as in lfg_interpolate_compensated; c unmatched under the fractional gate: Cv alone; c matched
+ *   with mvq(c) != u (clamped): Pv alone; otherwise as a projected pixel.
+ * Hence: with mvq = 4 mv (components in [-127, 127]) the output equals lfg_interpolate_compensated(mv) byte for byte, for
+ * every input, factor and match_sad; t = 1 gives curr exactly.
+ * Frames and checks: lfg_interpolate_compensated[_multi]'s, with mvq 4-byte aligned and its pitch a multiple of 4.  The lane
+ * keeps the route's key image, 8 W H bytes, grown on demand and freed with the lane; _multi repeats the single call per
+ * factor with one K.  Timed under LFG_STAGE_INTERPOLATE.
+ * Not built, on purpose: masked (static protection), bidirectional, extrapolating and fill-plane (lfg_set_hole_reach)
+ * variants of this route. */
+int  lfg_interpolate_compensated_subpel(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mvq,
+                                        lfg_frame *out, float factor, int match_sad);
+int  lfg_interpolate_compensated_subpel_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mvq,
+                                              lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad);
+/* Quarter-pixel vectors in lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   radius = -1 (default): off; every path enqueues and allocates what it did;
+ *   radius = 0 .. 2: exactly where those calls would run lfg_interpolate_compensated[_multi] with the 16 px walk -- the
+ *       compensated interpolator, LFG_GENERATION_INTERPOLATE, and lfg_set_bidirectional, lfg_set_static_protection and
+ *       lfg_set_hole_reach all off -- the final integer field (after half-resolution expansion and refinement) goes through
+ *       lfg_motion_subpel with this radius into a per-lane MV_S16X2_Q2 temporary (made on demand, follows a change of size,
+ *       freed with the lane), and lfg_interpolate_compensated_subpel[_multi] runs in the compensated call's place.
+ * Under every other setting it has no effect.  Cut detection and everything else keep reading the integer field.
+ * Any other radius: LFG_ERR_INVALID and no change.  Measured cost and quality: DESIGN.md section 4.20. */
+int  lfg_set_subpixel_vectors(lfg_context *ctx, int radius);
 
 /* Pair statistics: how well a vector field explains a pair of frames.  No reference counterpart.  A pair whose two frames do
  * not show the same scene (a cut, a cold start, a channel change) has no vectors that mean anything, and hardly any pixel

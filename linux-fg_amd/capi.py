@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("LFG_LIB") or os.path.join(_HERE, "liblinuxfg_hip.so")
 
 FORMAT_RGBA8 = 0
 FORMAT_MV_S8X2 = 1
+FORMAT_MV_S16X2_Q2 = 2
 STAGE_SCALE, STAGE_MOTION, STAGE_INTERPOLATE = 0, 1, 2
 MOTION_PREFILTERED, MOTION_EXACT_ONLY = 0, 1
 SEMANTICS_REFERENCE, SEMANTICS_INTENDED = 0, 1
@@ -28,7 +29,7 @@ HOLE_REACH_MAX = 255
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
 CHROMA_REPLICATE, CHROMA_LEFT = 0, 1
-_BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2}
+_BPP = {FORMAT_RGBA8: 4, FORMAT_MV_S8X2: 2, FORMAT_MV_S16X2_Q2: 4}
 COMM_ID_BYTES = 128
 MAX_LANES = 4
 MAX_SHARPEN = 64
@@ -162,6 +163,10 @@ SIGNATURES = {
     "lfg_frame_halve": (_i, [_vp, _FP, _FP]),
     "lfg_motion_expand": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
     "lfg_set_half_resolution_motion": (_i, [_vp, _i]),
+    "lfg_motion_subpel": (_i, [_vp, _FP, _FP, _FP, _FP, _i]),
+    "lfg_interpolate_compensated_subpel": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
+    "lfg_interpolate_compensated_subpel_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
+    "lfg_set_subpixel_vectors": (_i, [_vp, _i]),
     "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
     "lfg_cut_fallback": (_i, [_vp, _FP, _FP, _vp, _i, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
     "lfg_set_cut_detection": (_i, [_vp, _i]),
@@ -356,6 +361,8 @@ class Context:
     def download(self, f: Frame) -> np.ndarray:
         if f.format == FORMAT_RGBA8:
             out = np.empty((f.height, f.width, 4), np.uint8)
+        elif f.format == FORMAT_MV_S16X2_Q2:
+            out = np.empty((f.height, f.width, 2), np.int16)
         else:
             out = np.empty((f.height, f.width, 2), np.int8)
         self._check(self.lib.lfg_frame_download(self.h, ctypes.byref(f), out.ctypes.data_as(_vp), out.nbytes), "lfg_frame_download")
@@ -363,6 +370,10 @@ class Context:
         return out
 
     def frame_from(self, host: np.ndarray, fmt: int = FORMAT_RGBA8) -> Frame:
+        """A new frame holding `host`: (H, W, 4) uint8, (H, W, 2) int8 for FORMAT_MV_S8X2 or (H, W, 2) int16 for
+        FORMAT_MV_S16X2_Q2."""
+        if fmt == FORMAT_MV_S16X2_Q2 and (host.dtype != np.int16 or host.shape[2:] != (2,)):
+            raise LfgError(f"frame_from: FORMAT_MV_S16X2_Q2 takes (H, W, 2) int16, not {host.shape} {host.dtype}")
         f = self.create_frame(host.shape[1], host.shape[0], fmt)
         self.upload(f, host)
         return f
@@ -649,6 +660,29 @@ class Context:
         of the 3 x 3 coarse neighbours above it that fits its (2 radius + 1)^2 window best, then the best of its +-1 steps."""
         self._check(self.lib.lfg_motion_expand(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv_low),
                                                ctypes.byref(mv_out), int(radius)), "lfg_motion_expand")
+
+    def motion_subpel(self, prev: Frame, curr: Frame, mv_in: Frame, mvq_out: Frame, radius: int = 1):
+        """lfg_motion_subpel: the FORMAT_MV_S16X2_Q2 field mvq_out from the integer field mv_in.  Each pixel takes the best of the
+        nine half-pixel steps around 4 * mv_in, then of the nine quarter-pixel steps around that, by its (2 radius + 1)^2 window."""
+        self._check(self.lib.lfg_motion_subpel(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv_in),
+                                               ctypes.byref(mvq_out), int(radius)), "lfg_motion_subpel")
+
+    def interpolate_compensated_subpel(self, prev: Frame, curr: Frame, mvq: Frame, out: Frame, factor: float = 0.5,
+                                       match_sad: int = DEFAULT_MATCH_SAD):
+        """lfg_interpolate_compensated_subpel: interpolate_compensated along quarter-pixel vectors (FORMAT_MV_S16X2_Q2)."""
+        self._check(self.lib.lfg_interpolate_compensated_subpel(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mvq),
+                                                                ctypes.byref(out), factor, int(match_sad)), "lfg_interpolate_compensated_subpel")
+
+    def interpolate_compensated_subpel_multi(self, prev: Frame, curr: Frame, mvq: Frame, outs, factors, match_sad: int = DEFAULT_MATCH_SAD):
+        """lfg_interpolate_compensated_subpel_multi: one generated frame per factor, each equal to the single call."""
+        po, pf, n = self._multi_args(outs, factors)
+        self._check(self.lib.lfg_interpolate_compensated_subpel_multi(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mvq),
+                                                                      po, pf, n, int(match_sad)), "lfg_interpolate_compensated_subpel_multi")
+
+    def set_subpixel_vectors(self, radius: int):
+        """lfg_set_subpixel_vectors: -1 (default) off; 0 .. 2, where interpolate_frames[_multi] would run the plain compensated
+        call with the walk they run motion_subpel with that radius and interpolate_compensated_subpel[_multi] in its place."""
+        self._check(self.lib.lfg_set_subpixel_vectors(self.h, int(radius)), "lfg_set_subpixel_vectors")
 
     def set_half_resolution_motion(self, radius: int):
         """-1 (default: off) or 0..2: interpolate_frames[_multi] run the selected estimator on both frames halved and

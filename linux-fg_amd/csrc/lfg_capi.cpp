@@ -36,6 +36,7 @@ uint32_t bytes_per_pixel(uint32_t format) {
     switch (format) {
         case LFG_FORMAT_RGBA8_UNORM: return 4;
         case LFG_FORMAT_MV_S8X2: return 2;
+        case LFG_FORMAT_MV_S16X2_Q2: return 4;
         default: return 0;
     }
 }
@@ -136,7 +137,7 @@ hipError_t sync_lanes(lfg_context *ctx) {
     return e;
 }
 
-// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, half_prev, half_curr, mv_half, mid_tmp), at this size: kept while the size stays, made again when it
+// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, half_prev, half_curr, mv_half, mvq_tmp, mid_tmp), at this size: kept while the size stays, made again when it
 // changes.  The test comes first because lfg_frame_destroy waits for every lane.  (frame_manager.cpp:226-230)
 int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, uint32_t format) {
     if (f.data && f.width == width && f.height == height) return LFG_OK;
@@ -144,7 +145,7 @@ int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, 
     return lfg_frame_create(ctx, width, height, format, &f);
 }
 
-// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys, mc_fill, static_mask).  `what` names the allocation in the error.
+// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys, mc_fill, static_mask, mcq_keys).  `what` names the allocation in the error.
 template <typename T>
 int lane_buffer_grow(lfg_context *ctx, T *&buf, size_t &have, size_t need, const char *what) {
     if (need <= have) return LFG_OK;
@@ -480,13 +481,14 @@ namespace {
 void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
-    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.half_prev, &l.half_curr, &l.mv_half, &l.mid_tmp})      // (lane_frame)
+    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.half_prev, &l.half_curr, &l.mv_half, &l.mvq_tmp, &l.mid_tmp})      // (lane_frame)
         if (f->data && f->owned) (void)hipFree(f->data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
     if (l.mc_keys) (void)hipFree(l.mc_keys);
     if (l.mc_fill) (void)hipFree(l.mc_fill);
     if (l.static_mask) (void)hipFree(l.static_mask);
+    if (l.mcq_keys) (void)hipFree(l.mcq_keys);
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
     if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
@@ -1326,24 +1328,29 @@ bool mask_ok(const lfg_mask *m, const lfg_frame *like) {
 
 // The four stages that project the vectors into the lane's key image: lfg_interpolate_compensated[_multi], with a mask
 // lfg_interpolate_compensated_masked[_multi], lfg_extrapolate_compensated[_multi], whose factors are its `aheads`, and
-// lfg_interpolate_compensated_bidirectional[_multi], whose mv is `fwd` and which alone takes `bwd` and `tolerance`.
-enum class McKind { Plain, Masked, Extrapolate, Bidirectional };
+// lfg_interpolate_compensated_bidirectional[_multi], whose mv is `fwd` and which alone takes `bwd` and `tolerance`.  And
+// lfg_interpolate_compensated_subpel[_multi], whose mv is the quarter-pixel `mvq`: another format and alignment, a key image of
+// its own with 64-bit words, and no fill plane.
+enum class McKind { Plain, Masked, Extrapolate, Bidirectional, Subpel };
 
 int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_mask *mask, McKind kind,
                     lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name,
                     const lfg_frame *bwd = nullptr, int tolerance = 0) {
-    const bool masked = kind == McKind::Masked, bidir = kind == McKind::Bidirectional;
+    const bool masked = kind == McKind::Masked, bidir = kind == McKind::Bidirectional, subpel = kind == McKind::Subpel;
+    const uint32_t mvFormat = subpel ? LFG_FORMAT_MV_S16X2_Q2 : LFG_FORMAT_MV_S8X2, mvAlign = subpel ? 4u : 2u;
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     const std::string n(name);
     if (!outs || !factors || count == 0 || count > LFG_MAX_FACTORS)
         return fail(ctx, LFG_ERR_INVALID, n + ": count must be in [1, LFG_MAX_FACTORS] and outs/factors non-NULL");
-    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(mv, LFG_FORMAT_MV_S8X2))
-        return fail(ctx, LFG_ERR_INVALID, n + ": prev/curr must be RGBA8 and mv MV_S8X2, all non-empty");
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(mv, mvFormat))
+        return fail(ctx, LFG_ERR_INVALID, n + (subpel ? ": prev/curr must be RGBA8 and mvq MV_S16X2_Q2, all non-empty"
+                                                      : ": prev/curr must be RGBA8 and mv MV_S8X2, all non-empty"));
     if (!same_size(prev, curr) || !same_size(curr, mv))
         return fail(ctx, LFG_ERR_INVALID, n + ": prev, curr and mv differ in size");
-    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u || mv->pitch % 2u || (uintptr_t)mv->data % 2u)
-        return fail(ctx, LFG_ERR_INVALID, n + ": RGBA8 frames must be 4-byte aligned and mv 2-byte aligned");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u || mv->pitch % mvAlign || (uintptr_t)mv->data % mvAlign)
+        return fail(ctx, LFG_ERR_INVALID, n + (subpel ? ": RGBA8 frames and mvq must be 4-byte aligned"
+                                                      : ": RGBA8 frames must be 4-byte aligned and mv 2-byte aligned"));
     if (match_sad < 0 || match_sad > 1020) return fail(ctx, LFG_ERR_INVALID, n + ": match_sad must be in [0, 1020]");
     if (masked && !mask_ok(mask, curr))
         return fail(ctx, LFG_ERR_INVALID, n + ": mask must be non-NULL, of the frames' size, with pitch >= width");
@@ -1364,10 +1371,12 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     }
     lfg_lane_state &cur = ctx->cur();
     const size_t bytes = (size_t)curr->width * curr->height * 4u;
-    int rc = lane_buffer_grow(ctx, cur.mc_keys, cur.mc_keys_bytes, bytes, "hipMalloc((void **)&cur.mc_keys, bytes)");
+    int rc = subpel ? lane_buffer_grow(ctx, cur.mcq_keys, cur.mcq_keys_bytes, 2u * bytes, "hipMalloc((void **)&cur.mcq_keys, 2 * bytes)")
+                    : lane_buffer_grow(ctx, cur.mc_keys, cur.mc_keys_bytes, bytes, "hipMalloc((void **)&cur.mc_keys, bytes)");
     if (rc != LFG_OK) return rc;
-    // lfg_set_hole_reach: the three interpolating kinds fill their holes from the lane's fill plane, made per factor behind K
-    const int reach = kind == McKind::Extrapolate ? -1 : ctx->hole_reach;
+    // lfg_set_hole_reach: the three interpolating kinds of whole-pixel vectors fill their holes from the lane's fill plane, made
+    // per factor behind K
+    const int reach = kind == McKind::Extrapolate || subpel ? -1 : ctx->hole_reach;
     if (reach >= 1) {
         rc = lane_buffer_grow(ctx, cur.mc_fill, cur.mc_fill_bytes, bytes, "hipMalloc((void **)&cur.mc_fill, bytes)");
         if (rc != LFG_OK) return rc;
@@ -1375,7 +1384,8 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     uint32_t *const fill = reach >= 1 ? cur.mc_fill : nullptr;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
     for (uint32_t i = 0; i < count; ++i) {                       // one key image (and one fill plane), reused in stream order
-        hipError_t e = masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys,
+        hipError_t e = subpel ? lfg::launch_interpolate_compensated_subpel(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mcq_keys)
+                       : masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys,
                                                                            fill, reach)
                        : kind == McKind::Extrapolate
                               ? lfg::launch_extrapolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys)
@@ -1386,6 +1396,12 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
         if (e != hipSuccess) return fail_hip(ctx, e, kind == McKind::Extrapolate ? "compensated extrapolate kernel launch" : "compensated interpolate kernel launch");
     }
     return LFG_OK;
+}
+
+// lfg_set_subpixel_vectors' conditions: exactly where compensated_frames would run the plain kind with the walk.
+bool subpixel_applies(const lfg_context *ctx) {
+    return ctx->subpel_radius >= 0 && ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED && ctx->generation == LFG_GENERATION_INTERPOLATE &&
+           ctx->bidir_tolerance < 0 && ctx->static_tolerance < 0 && ctx->hole_reach < 0;
 }
 
 // The compensated interpolation of lfg_interpolate_frames[_multi]: as it is, or with lfg_set_static_protection on the pair's
@@ -1405,6 +1421,15 @@ int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
         return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Bidirectional, outs, factors, count, ctx->match_sad,
                                multi ? "lfg_interpolate_compensated_bidirectional_multi" : "lfg_interpolate_compensated_bidirectional",
                                backward, ctx->bidir_tolerance);
+    }
+    if (subpixel_applies(ctx)) {                                   // the final integer field to quarter pixels, then the route that carries them
+        lfg_lane_state &cur = ctx->cur();
+        int rc = lane_frame(ctx, cur.mvq_tmp, curr->width, curr->height, LFG_FORMAT_MV_S16X2_Q2);
+        if (rc != LFG_OK) return fail(ctx, rc, "Failed to create the quarter-pixel motion vectors frame");
+        rc = lfg_motion_subpel(ctx, prev, curr, vectors, &cur.mvq_tmp, ctx->subpel_radius);
+        if (rc != LFG_OK) return rc;
+        return compensated_run(ctx, prev, curr, &cur.mvq_tmp, nullptr, McKind::Subpel, outs, factors, count, ctx->match_sad,
+                               multi ? "lfg_interpolate_compensated_subpel_multi" : "lfg_interpolate_compensated_subpel");
     }
     if (ctx->static_tolerance < 0)
         return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Plain, outs, factors, count, ctx->match_sad,
@@ -1653,6 +1678,47 @@ LFG_EXPORT int lfg_set_half_resolution_motion(lfg_context *ctx, int radius) {
     if (radius < -1 || radius > 2)
         return fail(ctx, LFG_ERR_INVALID, "lfg_set_half_resolution_motion: radius must be -1 (off) or in [0, 2]");
     ctx->half_res_radius = radius;
+    return LFG_OK;
+}
+
+// ---- quarter-pixel vectors (motion_subpel.hip, interpolate_subpel.hip)
+
+LFG_EXPORT int lfg_motion_subpel(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv_in,
+                                 lfg_frame *mvq_out, int radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) ||
+        !frame_ok(mv_in, LFG_FORMAT_MV_S8X2) || !frame_ok(mvq_out, LFG_FORMAT_MV_S16X2_Q2))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_subpel: prev/curr must be RGBA8, mv_in MV_S8X2 and mvq_out MV_S16X2_Q2, all non-empty");
+    if (!same_size(prev, curr) || !same_size(curr, mv_in) || !same_size(curr, mvq_out))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_subpel: prev, curr, mv_in and mvq_out differ in size");
+    if ((prev->pitch | curr->pitch | mvq_out->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data | (uintptr_t)mvq_out->data) % 4u ||
+        mv_in->pitch % 2u || (uintptr_t)mv_in->data % 2u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_subpel: RGBA8 frames and mvq_out must be 4-byte aligned and mv_in 2-byte aligned");
+    if (frames_overlap(mvq_out, prev) || frames_overlap(mvq_out, curr) || frames_overlap(mvq_out, mv_in))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_motion_subpel: mvq_out overlaps an input");
+    if (radius < 0 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_subpel: radius must be in [0, 2]");
+    StageTimer timer(ctx, LFG_STAGE_MOTION);
+    hipError_t e = lfg::launch_motion_subpel(ctx->cur().stream, *prev, *curr, *mv_in, *mvq_out, radius);
+    if (e != hipSuccess) return fail_hip(ctx, e, "motion subpel kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_subpel(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mvq,
+                                                  lfg_frame *out, float factor, int match_sad) {
+    lfg_frame *const outs[1] = {out};
+    return compensated_run(ctx, prev, curr, mvq, nullptr, McKind::Subpel, outs, &factor, 1, match_sad, "lfg_interpolate_compensated_subpel");
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_subpel_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mvq,
+                                                        lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad) {
+    return compensated_run(ctx, prev, curr, mvq, nullptr, McKind::Subpel, outs, factors, count, match_sad, "lfg_interpolate_compensated_subpel_multi");
+}
+
+LFG_EXPORT int lfg_set_subpixel_vectors(lfg_context *ctx, int radius) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (radius < -1 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_set_subpixel_vectors: radius must be -1 (off) or in [0, 2]");
+    ctx->subpel_radius = radius;
     return LFG_OK;
 }
 

@@ -197,6 +197,11 @@ struct lfg_lane_state {
     // lfg_set_static_protection: the pair's static mask (W * H bytes), grown on demand
     uint8_t *static_mask = nullptr;
     size_t static_mask_bytes = 0;
+    // lfg_set_subpixel_vectors: the quarter-pixel field of the pair (W x H MV_S16X2_Q2), made on demand, and
+    // lfg_interpolate_compensated_subpel: the key image of that route (W * H 64-bit words), grown on demand
+    lfg_frame mvq_tmp{};
+    unsigned long long *mcq_keys = nullptr;
+    size_t mcq_keys_bytes = 0;
     hipEvent_t mark = nullptr;                 // lfg_lane_mark
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
@@ -232,6 +237,7 @@ struct lfg_context {
     int bidir_tolerance = -1;                  // lfg_interpolate_frames[_multi]: the bidirectional route's tolerance, -1 = off (lfg_set_bidirectional)
     int hole_reach = -1;                       // the compensated, masked and bidirectional calls: the fill plane's reach, -1 = off: the walk (lfg_set_hole_reach)
     int half_res_radius = -1;                  // lfg_interpolate_frames[_multi]: lfg_motion_expand's radius, -1 = off (lfg_set_half_resolution_motion)
+    int subpel_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_subpel's radius, -1 = off (lfg_set_subpixel_vectors)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -363,6 +369,13 @@ hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_
 hipError_t launch_frame_halve(hipStream_t s, const lfg_frame &in, const lfg_frame &out);
 hipError_t launch_motion_expand(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvLow,
                                 const lfg_frame &mvOut, int radius);
+// Quarter-pixel vectors: mvq_out(q) = the best of the nine half-pixel steps around 4 mv_in(q), then of the nine quarter-pixel
+// steps around that (motion_subpel.hip), one launch; and the compensated interpolation along such a field
+// (interpolate_subpel.hip): clears `keys` (W * H 64-bit words), projects, samples; one factor.
+hipError_t launch_motion_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
+                                const lfg_frame &mvqOut, int radius);
+hipError_t launch_interpolate_compensated_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvq,
+                                                 const lfg_frame &out, float factor, int matchSad, unsigned long long *keys);
 // Scene-cut detection (pair_stats.hip): launch_pair_match clears the 24-byte record `stats` and enqueues the fixed grid that
 // fills it; launch_cut_fallback enqueues the kernel that reads it and, on a cut, copies prev or curr over every output.
 hipError_t launch_pair_match(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv, int matchSad,

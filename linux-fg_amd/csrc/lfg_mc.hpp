@@ -6,7 +6,7 @@
 // tests/compensated_model.h.  mc_fill_from_plane is what stands in the walk's place under lfg_set_hole_reach (hole_fill.hip
 // makes the plane, tests/fill_model.c restates it), and kFillBand is that file's band height.  The vector word, the longest-first key that K holds (mv_longest_first_key), its decode
 // (mv_order_decode) and the hole walks' way back to the order key (mv_key_flip_length) are lfg_vector_word.hpp's; the taps
-// are lfg_interp.hpp's.
+// are lfg_interp.hpp's.  The sub-pixel route's reads, gate and walk (interpolate_subpel.hip) are new functions at the end.
 #pragma once
 
 #include "lfg_device.hpp"
@@ -80,6 +80,55 @@ __device__ __forceinline__ void mc_store_inside_or_blend(const SampleTaps &sp, c
     const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
     const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
     *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+}
+
+// ---- the sub-pixel route (interpolate_subpel.hip; tests/subpel_model.c restates these): quarter-pixel vectors, a key image
+// of 64-bit words.
+constexpr unsigned long long kMcqHole = ~0ull;   // what the clear leaves, above every key (lfg_vector_word.hpp)
+
+__device__ __forceinline__ Mv mvq_at(const uint8_t *__restrict__ mvq, size_t pitch, int x, int y) {
+    return mvq_unpack(*reinterpret_cast<const uint32_t *>(mvq + (size_t)y * pitch + (size_t)x * 4u));
+}
+
+// prevq(r, w), lfg_motion_subpel's fractional sample, as a packed texel: the four texels at r + (w >> 2) and one step right
+// and down, outside the image read as 0, weighted by the quarters (w & 3); per channel (sum + 8) >> 4.  Channels 0 and 2 /
+// 1 and 3 travel in 16-bit halves: a sum stays below 255 * 16 + 8.
+__device__ __forceinline__ uint32_t prevq_texel(const uint8_t *__restrict__ prev, size_t prevPitch, int W, int H, int rx, int ry, Mv w) {
+    const int ix = rx + (w.x >> 2), iy = ry + (w.y >> 2);
+    const uint32_t fx = (uint32_t)(w.x & 3), fy = (uint32_t)(w.y & 3);
+    const uint32_t t00 = texel_or_zero(prev, prevPitch, ix, iy, W, H), t10 = texel_or_zero(prev, prevPitch, ix + 1, iy, W, H);
+    const uint32_t t01 = texel_or_zero(prev, prevPitch, ix, iy + 1, W, H), t11 = texel_or_zero(prev, prevPitch, ix + 1, iy + 1, W, H);
+    const uint32_t w00 = (4u - fx) * (4u - fy), w10 = fx * (4u - fy), w01 = (4u - fx) * fy, w11 = fx * fy;
+    const uint32_t even = (t00 & 0x00FF00FFu) * w00 + (t10 & 0x00FF00FFu) * w10 + (t01 & 0x00FF00FFu) * w01 + (t11 & 0x00FF00FFu) * w11 + 0x00080008u;
+    const uint32_t odd = ((t00 >> 8) & 0x00FF00FFu) * w00 + ((t10 >> 8) & 0x00FF00FFu) * w10 + ((t01 >> 8) & 0x00FF00FFu) * w01 +
+                         ((t11 >> 8) & 0x00FF00FFu) * w11 + 0x00080008u;
+    return ((even >> 4) & 0x00FF00FFu) | (((odd >> 4) & 0x00FF00FFu) << 8);
+}
+
+// The fractional match gate: sum over the channels of |curr(q) - prevq(q, w)| <= matchSad.
+__device__ __forceinline__ bool matched_q(const uint8_t *__restrict__ prev, size_t prevPitch, uint32_t currTexel, int W, int H, int qx,
+                                          int qy, Mv w, int matchSad) {
+    return __builtin_amdgcn_sad_u8(currTexel, prevq_texel(prev, prevPitch, W, H, qx, qy, w), 0u) <= (uint32_t)matchSad;
+}
+
+// mc_fill_vector over the 64-bit key image, as the order key: the smallest (|w|^2, wy, wx) of the first non-hole word in each
+// axis direction within kMcWalk; (0, 0) when every direction runs out.
+__device__ __forceinline__ unsigned long long mcq_fill_vector(const unsigned long long *__restrict__ keys, int W, int H, int x, int y) {
+    unsigned long long best = kMcqHole;
+    const int stepX[4] = {1, -1, 0, 0}, stepY[4] = {0, 0, 1, -1};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        for (int k = 1; k <= kMcWalk; ++k) {
+            const int nx = x + stepX[d] * k, ny = y + stepY[d] * k;
+            if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
+            const unsigned long long n = keys[(size_t)ny * (size_t)W + (size_t)nx];
+            if (n == kMcqHole) continue;
+            const unsigned long long order = mvq_key_flip_length(n);
+            best = order < best ? order : best;
+            break;
+        }
+    }
+    return best == kMcqHole ? mvq_order_key(0, 0) : best;
 }
 
 // Every launcher's start: K (W * H words) set to the hole word in stream order, and the grid of every launch, one thread

@@ -53,6 +53,14 @@ bool FrameManager::SetHoleReach(int reach) {
     return true;
 }
 
+bool FrameManager::SetSubpixelVectors(int radius) {
+    if (lfg_set_subpixel_vectors(Ctx(), radius) != LFG_OK) {
+        LOG_ERROR("Failed to set sub-pixel vectors: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
+        return false;
+    }
+    return true;
+}
+
 bool FrameManager::CreateFrame(Frame& frame, uint32_t width, uint32_t height) {
     lfg_frame f{};
     const uint32_t format = frame.format;                    // RGBA8 unless the caller asked otherwise

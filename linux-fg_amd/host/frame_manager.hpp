@@ -86,6 +86,11 @@ public:
     // has no such mode).  Extrapolated frames keep the walk.
     bool SetHoleReach(int reach);
 
+    // Quarter-pixel vectors in the four calls above where they take the plain compensated route with the walk
+    // (lfg_set_subpixel_vectors): -1 (default) off; 0 .. 2, the final integer field is refined to quarter pixels with this window
+    // radius and the sub-pixel compensated call runs (the reference has no such mode).
+    bool SetSubpixelVectors(int radius);
+
     // The one exchange of the multi-GPU path: broadcast a frame from rank `root` to every rank (asynchronous, on the
     // device context's communication stream) and make later work on the compute queue wait for it.
     bool BroadcastFrame(Frame& frame, int root);

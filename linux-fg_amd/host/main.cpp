@@ -60,6 +60,11 @@ static void PrintUsage() {
               << "                           of two scans gives every hole the nearest vector within N px along each axis, at a cost\n"
               << "                           that does not grow with N -- for the wide holes behind fast objects).  Needs --interpolator\n"
               << "                           compensated; not with --generation extrapolate\n"
+              << "  --subpel-vectors R       Quarter-pixel vectors for the compensated interpolator (default -1: off; 0..2: the final integer\n"
+              << "                           field is refined to quarter pixels over each pixel's (2R+1)^2 window and the interpolation carries\n"
+              << "                           the fraction -- for content that moves by fractions of a pixel per frame).  Needs --interpolator\n"
+              << "                           compensated; not with --generation extrapolate, --bidirectional, --protect-static, --hole-reach\n"
+              << "                           or --ranks\n"
               << "  --sharpen S              Contrast-limited sharpening of every presented frame, real and generated alike (default 0: off;\n"
               << "                           1..64: strength in 64ths of the classic 5-point kernel, each pixel kept within the range of\n"
               << "                           itself and its four neighbours).  Applied to a copy just before the read-back: motion, masks and\n"
@@ -203,6 +208,12 @@ int main(int argc, char* argv[]) {
             if (!end || end == argv[i] || *end != '\0' || n < 1 || n > LFG_HOLE_REACH_MAX) { LOG_ERROR("Invalid --hole-reach (1 to 255)"); return 1; }
             holeReach = (int)n;
         }
+        else if (strcmp(argv[i], "--subpel-vectors") == 0 && i + 1 < argc) {
+            char* end = nullptr;
+            const long r = strtol(argv[++i], &end, 10);
+            if (!end || end == argv[i] || *end != '\0' || r < -1 || r > 2) { LOG_ERROR("Invalid --subpel-vectors (-1, 0, 1 or 2)"); return 1; }
+            config.subpelVectors = (int)r;
+        }
         else if (strcmp(argv[i], "--sharpen") == 0 && i + 1 < argc) {
             char* end = nullptr;
             const long v = strtol(argv[++i], &end, 10);
@@ -303,6 +314,12 @@ int main(int argc, char* argv[]) {
         if (interpolator != LFG_INTERPOLATOR_COMPENSATED) { LOG_ERROR("--hole-reach needs --interpolator compensated"); return 2; }
         if (generation == LFG_GENERATION_EXTRAPOLATE) { LOG_ERROR("--hole-reach cannot be combined with --generation extrapolate"); return 2; }
     }
+    if (config.subpelVectors >= 0) {                            // before a context is made
+        const char* clash = interpolator != LFG_INTERPOLATOR_COMPENSATED ? "--interpolator shader"
+                          : generation == LFG_GENERATION_EXTRAPOLATE ? "--generation extrapolate" : bidirectional >= 0 ? "--bidirectional"
+                          : staticTolerance >= 0 ? "--protect-static" : holeReach >= 1 ? "--hole-reach" : ranks > 0 ? "--ranks" : nullptr;
+        if (clash) { LOG_ERROR("--subpel-vectors cannot be combined with ", clash); return 2; }
+    }
     if (evaluate) {                                             // before a context is made
         const char* clash = ranks > 0 ? "--ranks" : !factors.empty() ? "--factors" : !config.enableInterpolation ? "--no-interpolation"
                           : !outputRaw.empty() ? "--output-raw" : !dumpDir.empty() ? "--dump-dir" : replay > 0 ? "--replay" : nullptr;
@@ -324,7 +341,7 @@ int main(int argc, char* argv[]) {
     }
     if (!FrameManager::Get().Initialize(config.outputWidth, config.outputHeight) || !FrameManager::Get().SetGeneration(generation) ||
         !FrameManager::Get().SetBidirectional(bidirectional) || !FrameManager::Get().SetHalfResolutionMotion(halfResMotion) ||
-        !FrameManager::Get().SetHoleReach(holeReach)) {
+        !FrameManager::Get().SetHoleReach(holeReach) || !FrameManager::Get().SetSubpixelVectors(config.subpelVectors)) {
         LOG_ERROR("Failed to initialize frame manager");
         HipContext::Get().Cleanup();
         return 1;
@@ -340,12 +357,13 @@ int main(int argc, char* argv[]) {
         FrameManager::Get().Cleanup();
         HipContext::Get().Cleanup();
         if (!ok) { LOG_ERROR("Evaluation failed: ", Logger::Get().GetLastError()); return 1; }
-        char filterField[112] = "";
+        char filterField[136] = "";
         int used = 0;
         if (config.scaleFilter >= 0) used = snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
         if (bidirectional >= 0) used += snprintf(filterField + used, sizeof filterField - (size_t)used, "\"bidirectional\": %d, ", bidirectional);
         if (halfResMotion >= 0) used += snprintf(filterField + used, sizeof filterField - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
-        if (holeReach >= 1) snprintf(filterField + used, sizeof filterField - (size_t)used, "\"hole_reach\": %d, ", holeReach);
+        if (holeReach >= 1) used += snprintf(filterField + used, sizeof filterField - (size_t)used, "\"hole_reach\": %d, ", holeReach);
+        if (config.subpelVectors >= 0) snprintf(filterField + used, sizeof filterField - (size_t)used, "\"subpel_vectors\": %d, ", config.subpelVectors);
         printf("{\"input_frames\": %d, \"presented\": 0, \"interpolated\": %llu, \"cuts\": 0, \"seconds\": %.4f, "
                "\"presented_fps\": 0.00, \"checksum\": 0, \"pipelined\": false, \"replay\": 0, \"present_null\": %s, \"in_flight\": 1, "
                "\"input_format\": \"rgba\", \"output_format\": \"rgba\", \"protect_static\": %d, %s"
@@ -418,11 +436,12 @@ int main(int argc, char* argv[]) {
     if (config.sharpen > 0) snprintf(sharpenField, sizeof sharpenField, "\"sharpen\": %u, ", config.sharpen);
     char filterField[48] = "";
     if (config.scaleFilter >= 0) snprintf(filterField, sizeof filterField, "\"scale_filter\": \"%s\", ", kScaleFilterNames[config.scaleFilter]);
-    char routeFields[96] = "";
+    char routeFields[120] = "";
     int used = 0;
     if (bidirectional >= 0) used = snprintf(routeFields, sizeof routeFields, "\"bidirectional\": %d, ", bidirectional);
     if (halfResMotion >= 0) used += snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"half_res_motion\": %d, ", halfResMotion);
-    if (holeReach >= 1) snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"hole_reach\": %d, ", holeReach);
+    if (holeReach >= 1) used += snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"hole_reach\": %d, ", holeReach);
+    if (config.subpelVectors >= 0) snprintf(routeFields + used, sizeof routeFields - (size_t)used, "\"subpel_vectors\": %d, ", config.subpelVectors);
     fprintf(report, "{\"input_frames\": %d, \"presented\": %llu, \"interpolated\": %llu, \"cuts\": %llu, \"seconds\": %.4f, "
            "\"presented_fps\": %.2f, \"checksum\": %llu, \"pipelined\": %s, \"replay\": %d, \"present_null\": %s, \"in_flight\": %d, "
            "\"input_format\": \"%s\", \"output_format\": \"%s\", \"protect_static\": %d, %s%s%s"
