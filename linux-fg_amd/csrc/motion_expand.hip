@@ -17,18 +17,14 @@
 // those registers.  A step that leaves [-127, 127] clamps back onto a vector that another step of the same nine gives, so it
 // is left out instead of being evaluated twice.
 //
-// The key (cost, |v|^2, vy, vx) is one uint64 whose minimum wins: the order is total, so neither the order of evaluation nor
-// the tiling changes a result.  Every texel load comes unconditionally from a clamped position (lfg_device.hpp:
-// texel_or_zero).  No atomics, no scratch, no data-dependent loop bounds.
-#include "lfg_internal.hpp"
-#include "lfg_device.hpp"
-#include "lfg_vector_word.hpp"
+// The cost, the key and the 64 x 4 launch are the window-cost family's (lfg_window_cost.hpp).  No atomics, no scratch, no
+// data-dependent loop bounds.
+#include "lfg_window_cost.hpp"
 
 namespace lfg {
 namespace {
 
-constexpr int kExpBlockX = 64, kExpBlockY = 4;               // a wave is 64 pixels of one row
-constexpr int kExpTileW = kExpBlockX / 2 + 2, kExpTileH = kExpBlockY / 2 + 2;   // mv_low under the block, plus the halo
+constexpr int kExpTileW = kWinBlockX / 2 + 2, kExpTileH = kWinBlockY / 2 + 2;   // mv_low under the block, plus the halo
 constexpr int kExpCands = 9;
 
 __global__ __launch_bounds__(256) void frame_halve_kernel(const uint8_t *__restrict__ src, size_t srcPitch, int Ws, int Hs,
@@ -54,16 +50,16 @@ __device__ __forceinline__ uint32_t doubled_word(uint32_t word) {
 }
 
 template <int R>
-__global__ __launch_bounds__(kExpBlockX * kExpBlockY) void motion_expand_kernel(
+__global__ __launch_bounds__(kWinBlockX * kWinBlockY) void motion_expand_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mvLow, size_t mvLowPitch, uint8_t *__restrict__ mvOut, size_t mvOutPitch, int W, int H) {
     constexpr int D = 2 * R + 1, E = D + 2;
     __shared__ uint16_t tile[kExpTileH * kExpTileW];
-    const int x0 = (int)blockIdx.x * kExpBlockX, y0 = (int)blockIdx.y * kExpBlockY;
+    const int x0 = (int)blockIdx.x * kWinBlockX, y0 = (int)blockIdx.y * kWinBlockY;
     const int Wl = (W + 1) / 2, Hl = (H + 1) / 2;
     // one load per thread covers the tile: all of them are in flight before the first LDS write
     {
-        const int i = (int)(threadIdx.y * kExpBlockX + threadIdx.x);
+        const int i = (int)(threadIdx.y * kWinBlockX + threadIdx.x);
         const int gx = x0 / 2 - 1 + i % kExpTileW, gy = y0 / 2 - 1 + i / kExpTileW;
         const uint16_t staged = (i < kExpTileH * kExpTileW && gx >= 0 && gx < Wl && gy >= 0 && gy < Hl)
                                     ? *reinterpret_cast<const uint16_t *>(mvLow + (size_t)gy * mvLowPitch + (size_t)gx * 2u) : (uint16_t)0;
@@ -122,11 +118,8 @@ __global__ __launch_bounds__(kExpBlockX * kExpBlockY) void motion_expand_kernel(
 #pragma unroll
             for (int j = 0; j < D; ++j)
 #pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    const uint32_t p = texel_or_zero(prev, prevPitch, x + i - R + v.x, y + j - R + v.y, W, H);
-                    const uint32_t sum = __builtin_amdgcn_sad_u8(cw[j * D + i], p, cost);
-                    cost = (inWin >> (j * D + i)) & 1u ? sum : cost;
-                }
+                for (int i = 0; i < D; ++i)
+                    cost = window_add(cw, inWin, j * D + i, texel_or_zero(prev, prevPitch, x + i - R + v.x, y + j - R + v.y, W, H), cost);
             const uint64_t key = ((uint64_t)cost << 32) | mv_order_key(v.x, v.y);
             best = key < best ? key : best;
         }
@@ -148,10 +141,7 @@ __global__ __launch_bounds__(kExpBlockX * kExpBlockY) void motion_expand_kernel(
 #pragma unroll
             for (int j = 0; j < D; ++j)
 #pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    const uint32_t sum = __builtin_amdgcn_sad_u8(cw[j * D + i], pw[(j + 1 + dy) * E + i + 1 + dx], cost);
-                    cost = (inWin >> (j * D + i)) & 1u ? sum : cost;
-                }
+                for (int i = 0; i < D; ++i) cost = window_add(cw, inWin, j * D + i, pw[(j + 1 + dy) * E + i + 1 + dx], cost);
             const int vx = w.x + dx, vy = w.y + dy;
             const bool inRange = vx >= -127 && vx <= 127 && vy >= -127 && vy <= 127;      // else: a duplicate of another step
             const uint64_t key = inRange ? ((uint64_t)cost << 32) | mv_order_key(vx, vy) : ~0ull;
@@ -172,12 +162,7 @@ hipError_t launch_frame_halve(hipStream_t s, const lfg_frame &in, const lfg_fram
 
 hipError_t launch_motion_expand(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvLow,
                                 const lfg_frame &mvOut, int radius) {
-    const int W = (int)curr.width, H = (int)curr.height;
-    const dim3 block(kExpBlockX, kExpBlockY), grid((unsigned)((W + kExpBlockX - 1) / kExpBlockX), (unsigned)((H + kExpBlockY - 1) / kExpBlockY));
-    auto kernel = radius == 0 ? motion_expand_kernel<0> : radius == 1 ? motion_expand_kernel<1> : motion_expand_kernel<2>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
-                       (size_t)curr.pitch, (const uint8_t *)mvLow.data, (size_t)mvLow.pitch, (uint8_t *)mvOut.data, (size_t)mvOut.pitch, W, H);
-    return hipGetLastError();
+    return window_cost_launch(motion_expand_kernel<0>, motion_expand_kernel<1>, motion_expand_kernel<2>, radius, s, prev, curr, mvLow, mvOut);
 }
 
 }  // namespace lfg

@@ -9,22 +9,18 @@
 // Uniform lanes: when every candidate equals mv_in(q) the answer is mv_in(q) (the definition's minimum over one distinct
 // vector), stored without any cost work.  On a pan that is every lane away from the image's own edges.
 //
-// Other lanes keep the (2R + 1)^2 curr window in registers (read once), then evaluate each DISTINCT candidate once: (2R + 1)^2
-// gathered prev dwords, v_sad_u8 each, and the packed key (cost, |v|^2, vy, vx) as one uint64 whose minimum wins.  The order
-// is total, so neither the order of evaluation nor the tiling changes a result.  No atomics, no second launch.
+// Other lanes keep the (2R + 1)^2 curr window in registers (read once), then evaluate each DISTINCT candidate once by the
+// family's rule (lfg_window_cost.hpp: the cost, the key, the 64 x 4 launch).  No atomics, no second launch.
 //
 // Traffic per pixel: 2 bytes of mv_in (plus the halo, L2 hits) and 2 of mv_out on a uniform lane; a non-uniform lane adds
 // (2R + 1)^2 dwords of curr and up to 17 (2R + 1)^2 gathered dwords of prev, mostly L1/L2 hits.
-#include "lfg_internal.hpp"
-#include "lfg_device.hpp"
-#include "lfg_vector_word.hpp"
+#include "lfg_window_cost.hpp"
 
 namespace lfg {
 namespace {
 
-constexpr int kRefBlockX = 64, kRefBlockY = 4;               // a wave is 64 pixels of one row
 constexpr int kRefHalo = 8;                                  // the farthest candidate offset
-constexpr int kRefTileW = kRefBlockX + 2 * kRefHalo, kRefTileH = kRefBlockY + 2 * kRefHalo;
+constexpr int kRefTileW = kWinBlockX + 2 * kRefHalo, kRefTileH = kWinBlockY + 2 * kRefHalo;
 constexpr int kRefCands = 17;
 
 // Candidate k's offset: k = 0 is (0, 0); k = 1 .. 16 run over s = 4, 8, then b, then a, skipping (a, b) = (0, 0).
@@ -32,25 +28,25 @@ __device__ constexpr int kRefDx[kRefCands] = {0, -4, 0, 4, -4, 4, -4, 0, 4, -8, 
 __device__ constexpr int kRefDy[kRefCands] = {0, -4, -4, -4, 0, 0, 4, 4, 4, -8, -8, -8, 0, 0, 8, 8, 8};
 
 template <int R>
-__global__ __launch_bounds__(kRefBlockX * kRefBlockY) void motion_refine_kernel(
+__global__ __launch_bounds__(kWinBlockX * kWinBlockY) void motion_refine_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mvIn, size_t mvInPitch, uint8_t *__restrict__ mvOut, size_t mvOutPitch, int W, int H) {
     constexpr int D = 2 * R + 1;
     __shared__ uint16_t tile[kRefTileH * kRefTileW];
-    const int x0 = (int)blockIdx.x * kRefBlockX, y0 = (int)blockIdx.y * kRefBlockY;
+    const int x0 = (int)blockIdx.x * kWinBlockX, y0 = (int)blockIdx.y * kWinBlockY;
     // every load of the tile in flight before the first LDS write: a loop that waits for each load in turn is latency-bound
-    constexpr int kThreads = kRefBlockX * kRefBlockY, kSteps = (kRefTileH * kRefTileW + kThreads - 1) / kThreads;
+    constexpr int kThreads = kWinBlockX * kWinBlockY, kSteps = (kRefTileH * kRefTileW + kThreads - 1) / kThreads;
     uint16_t staged[kSteps];
 #pragma unroll
     for (int k = 0; k < kSteps; ++k) {
-        const int i = (int)(threadIdx.y * kRefBlockX + threadIdx.x) + k * kThreads;
+        const int i = (int)(threadIdx.y * kWinBlockX + threadIdx.x) + k * kThreads;
         const int gx = x0 - kRefHalo + i % kRefTileW, gy = y0 - kRefHalo + i / kRefTileW;
         staged[k] = (i < kRefTileH * kRefTileW && gx >= 0 && gx < W && gy >= 0 && gy < H)
                         ? *reinterpret_cast<const uint16_t *>(mvIn + (size_t)gy * mvInPitch + (size_t)gx * 2u) : (uint16_t)0;
     }
 #pragma unroll
     for (int k = 0; k < kSteps; ++k) {
-        const int i = (int)(threadIdx.y * kRefBlockX + threadIdx.x) + k * kThreads;
+        const int i = (int)(threadIdx.y * kWinBlockX + threadIdx.x) + k * kThreads;
         if (i < kRefTileH * kRefTileW) tile[i] = staged[k];
     }
     __syncthreads();
@@ -100,11 +96,8 @@ __global__ __launch_bounds__(kRefBlockX * kRefBlockY) void motion_refine_kernel(
 #pragma unroll
         for (int j = 0; j < D; ++j)
 #pragma unroll
-            for (int i = 0; i < D; ++i) {
-                const uint32_t p = texel_or_zero(prev, prevPitch, x + i - R + v.x, y + j - R + v.y, W, H);
-                const uint32_t sum = __builtin_amdgcn_sad_u8(cw[j * D + i], p, cost);
-                cost = (inWin >> (j * D + i)) & 1u ? sum : cost;
-            }
+            for (int i = 0; i < D; ++i)
+                cost = window_add(cw, inWin, j * D + i, texel_or_zero(prev, prevPitch, x + i - R + v.x, y + j - R + v.y, W, H), cost);
         const uint64_t key = ((uint64_t)cost << 32) | mv_order_key(v.x, v.y);
         best = key < best ? key : best;
     }
@@ -116,12 +109,7 @@ __global__ __launch_bounds__(kRefBlockX * kRefBlockY) void motion_refine_kernel(
 
 hipError_t launch_motion_refine(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
                                 const lfg_frame &mvOut, int radius) {
-    const int W = (int)curr.width, H = (int)curr.height;
-    const dim3 block(kRefBlockX, kRefBlockY), grid((unsigned)((W + kRefBlockX - 1) / kRefBlockX), (unsigned)((H + kRefBlockY - 1) / kRefBlockY));
-    auto kernel = radius == 0 ? motion_refine_kernel<0> : radius == 1 ? motion_refine_kernel<1> : motion_refine_kernel<2>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
-                       (size_t)curr.pitch, (const uint8_t *)mvIn.data, (size_t)mvIn.pitch, (uint8_t *)mvOut.data, (size_t)mvOut.pitch, W, H);
-    return hipGetLastError();
+    return window_cost_launch(motion_refine_kernel<0>, motion_refine_kernel<1>, motion_refine_kernel<2>, radius, s, prev, curr, mvIn, mvOut);
 }
 
 }  // namespace lfg

@@ -2,7 +2,7 @@
 // No reference counterpart; opt-in, between the last integer stage and the sub-pixel compensated route
 // (interpolate_subpel.hip).  tests/subpel_model.c restates the definition on the CPU.
 //
-// One launch, one thread per pixel; a wave is 64 pixels of one row, a workgroup 64 x 4 pixels, as motion_expand_kernel's.
+// One launch of the window-cost family's shape and its masked cost (lfg_window_cost.hpp), on a sample that is this file's own.
 // curr's (2R + 1)^2 window and the (2R + 3)^2 prev texels around q + v are read once, prev's split into its even and odd
 // channels (16-bit halves of two registers per texel).  A candidate w = 4v + d, d in [-3, 3]^2, samples prev at
 // r + v + (d >> 2) with the quarters (d & 3): per axis that is the three texels at -1, 0, +1 of the block with the weights
@@ -15,14 +15,10 @@
 // minimum wins: the order is total.  Both loops run their constant nine trips, not unrolled, so the code stays one
 // candidate long.  Every texel load comes unconditionally from a clamped position (lfg_device.hpp: texel_or_zero).  No
 // atomics, no scratch, no data-dependent loop bounds.
-#include "lfg_internal.hpp"
-#include "lfg_device.hpp"
-#include "lfg_vector_word.hpp"
+#include "lfg_window_cost.hpp"
 
 namespace lfg {
 namespace {
-
-constexpr int kSubBlockX = 64, kSubBlockY = 4;               // a wave is 64 pixels of one row
 
 // The three weights of one axis for the offset d in [-3, 3], on the texels at -1, 0, +1.
 __device__ __forceinline__ void axis_weights(int d, uint32_t (&w)[3]) {
@@ -60,9 +56,7 @@ struct SubpelWindow {
                         even += pe[(j + b) * E + i + a] * w9[b * 3 + a];
                         odd += po[(j + b) * E + i + a] * w9[b * 3 + a];
                     }
-                const uint32_t p = ((even >> 4) & 0x00FF00FFu) | (((odd >> 4) & 0x00FF00FFu) << 8);
-                const uint32_t sum = __builtin_amdgcn_sad_u8(cw[j * D + i], p, cost);
-                cost = (inWin >> (j * D + i)) & 1u ? sum : cost;
+                cost = window_add(cw, inWin, j * D + i, ((even >> 4) & 0x00FF00FFu) | (((odd >> 4) & 0x00FF00FFu) << 8), cost);
             }
         const int wqx = v4.x + dx, wqy = v4.y + dy;
         const bool inRange = wqx >= -kMvqLimit && wqx <= kMvqLimit && wqy >= -kMvqLimit && wqy <= kMvqLimit;
@@ -71,11 +65,11 @@ struct SubpelWindow {
 };
 
 template <int R>
-__global__ __launch_bounds__(kSubBlockX * kSubBlockY) void motion_subpel_kernel(
+__global__ __launch_bounds__(kWinBlockX * kWinBlockY) void motion_subpel_kernel(
         const uint8_t *__restrict__ prev, size_t prevPitch, const uint8_t *__restrict__ curr, size_t currPitch,
         const uint8_t *__restrict__ mvIn, size_t mvInPitch, uint8_t *__restrict__ mvqOut, size_t mvqOutPitch, int W, int H) {
     constexpr int D = 2 * R + 1, E = D + 2;
-    const int x = (int)blockIdx.x * kSubBlockX + (int)threadIdx.x, y = (int)blockIdx.y * kSubBlockY + (int)threadIdx.y;
+    const int x = (int)blockIdx.x * kWinBlockX + (int)threadIdx.x, y = (int)blockIdx.y * kWinBlockY + (int)threadIdx.y;
     if (x >= W || y >= H) return;
     Mv v = mv_unpack(*reinterpret_cast<const uint16_t *>(mvIn + (size_t)y * mvInPitch + (size_t)x * 2u));
     v.x = max(v.x, -127); v.y = max(v.y, -127);              // a byte of -128 is read as -127
@@ -122,12 +116,7 @@ __global__ __launch_bounds__(kSubBlockX * kSubBlockY) void motion_subpel_kernel(
 
 hipError_t launch_motion_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvIn,
                                 const lfg_frame &mvqOut, int radius) {
-    const int W = (int)curr.width, H = (int)curr.height;
-    const dim3 block(kSubBlockX, kSubBlockY), grid((unsigned)((W + kSubBlockX - 1) / kSubBlockX), (unsigned)((H + kSubBlockY - 1) / kSubBlockY));
-    auto kernel = radius == 0 ? motion_subpel_kernel<0> : radius == 1 ? motion_subpel_kernel<1> : motion_subpel_kernel<2>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
-                       (size_t)curr.pitch, (const uint8_t *)mvIn.data, (size_t)mvIn.pitch, (uint8_t *)mvqOut.data, (size_t)mvqOut.pitch, W, H);
-    return hipGetLastError();
+    return window_cost_launch(motion_subpel_kernel<0>, motion_subpel_kernel<1>, motion_subpel_kernel<2>, radius, s, prev, curr, mvIn, mvqOut);
 }
 
 }  // namespace lfg

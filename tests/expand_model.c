@@ -1,6 +1,6 @@
 /* CPU model of lfg_frame_halve and lfg_motion_expand (include/linuxfg_hip.h): the rounded 2 x 2 mean, the doubled 3 x 3
- * coarse neighbours, the +-1 parity step, the window cost and the key order, in integer arithmetic exactly as the header
- * defines them.  Built with the system C compiler by tests/expand_model.py.
+ * coarse neighbours, the +-1 parity step, with the window cost and the key order of window_model.h, in integer arithmetic
+ * exactly as the header defines them.  Built with the system C compiler by tests/expand_model.py.
  *
  * Frames are tight: prev / curr RGBA8 rows of W * 4 bytes, mv_low int8 (x, y) pairs in rows of ceil(W / 2) * 2 bytes.
  *
@@ -13,8 +13,7 @@
  *   NEIGHBOURS_2X2  the neighbours (a, b) in {0, 1}^2 instead of {-1, 0, 1}^2
  *   ROUND_UP        the centre neighbour at ((x + 1) >> 1, (y + 1) >> 1)
  *   TIE_VX_FIRST    the key (cost, |v|^2, vx, vy) */
-#include <stdint.h>
-#include <stdlib.h>
+#include "window_model.h"
 
 static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
@@ -31,29 +30,13 @@ void expand_halve(const uint8_t *in, int W, int H, uint8_t *out) {
             }
 }
 
-static inline uint64_t key_of(uint32_t cost, int vx, int vy) {
+/* this model's key: window_model.h's, or TIE_VX_FIRST's (cost, |v|^2, vx, vy), which is that key of the transposed vector */
+static inline uint64_t expand_key(uint32_t cost, int vx, int vy) {
 #ifdef EXPAND_MUTANT_TIE_VX_FIRST
-    return ((uint64_t)cost << 32) | ((uint64_t)(vx * vx + vy * vy) << 16) | ((uint64_t)(vx + 128) << 8) | (uint64_t)(vy + 128);
+    return key_of(cost, vy, vx);
 #else
-    return ((uint64_t)cost << 32) | ((uint64_t)(vx * vx + vy * vy) << 16) | ((uint64_t)(vy + 128) << 8) | (uint64_t)(vx + 128);
+    return key_of(cost, vx, vy);
 #endif
-}
-
-/* sum over the window texels r inside the image of sum_c |curr(r)_c - prev(r + v)_c|, prev outside the image read as 0 */
-static uint32_t cost_at(const uint8_t *prev, const uint8_t *curr, int W, int H, int qx, int qy, int vx, int vy, int radius) {
-    uint32_t s = 0;
-    for (int ry = qy - radius; ry <= qy + radius; ++ry)
-        for (int rx = qx - radius; rx <= qx + radius; ++rx) {
-            if (rx < 0 || rx >= W || ry < 0 || ry >= H) continue;
-            const uint8_t *c = curr + ((size_t)ry * W + rx) * 4;
-            const int sx = rx + vx, sy = ry + vy;
-            const int in = sx >= 0 && sx < W && sy >= 0 && sy < H;
-            for (int ch = 0; ch < 4; ++ch) {
-                const int p = in ? prev[((size_t)sy * W + sx) * 4 + ch] : 0;
-                s += (uint32_t)abs((int)c[ch] - p);
-            }
-        }
-    return s;
 }
 
 static inline int dbl(int v) {
@@ -86,13 +69,13 @@ void expand_roi(const uint8_t *prev, const uint8_t *curr, const int8_t *mv_low, 
                     const int nx = cx + a, ny = cy + b;
                     if (nx < 0 || nx >= Wl || ny < 0 || ny >= Hl) continue;
                     const int vx = dbl(mv_low[((size_t)ny * Wl + nx) * 2]), vy = dbl(mv_low[((size_t)ny * Wl + nx) * 2 + 1]);
-                    const uint64_t key = key_of(cost_at(prev, curr, W, H, qx, qy, vx, vy, radius), vx, vy);
+                    const uint64_t key = expand_key(cost_at(prev, curr, W, H, qx, qy, vx, vy, radius), vx, vy);
                     if (key < best) best = key;
                 }
 #ifdef EXPAND_MUTANT_TIE_VX_FIRST
-            const int wx = (int)((best >> 8) & 0xff) - 128, wy = (int)(best & 0xff) - 128;
+            const int wx = key_vy(best), wy = key_vx(best);
 #else
-            const int wx = (int)(best & 0xff) - 128, wy = (int)((best >> 8) & 0xff) - 128;
+            const int wx = key_vx(best), wy = key_vy(best);
 #endif
             int ox = wx, oy = wy;
 #ifndef EXPAND_MUTANT_NO_PARITY
@@ -101,7 +84,7 @@ void expand_roi(const uint8_t *prev, const uint8_t *curr, const int8_t *mv_low, 
             for (int dy = -1; dy <= 1; ++dy)
                 for (int dx = -1; dx <= 1; ++dx) {
                     const int vx = clampi(wx + dx, -127, 127), vy = clampi(wy + dy, -127, 127);
-                    const uint64_t key = key_of(cost_at(prev, curr, W, H, qx, qy, vx, vy, radius), vx, vy);
+                    const uint64_t key = expand_key(cost_at(prev, curr, W, H, qx, qy, vx, vy, radius), vx, vy);
                     if (key < best) { best = key; ox = vx; oy = vy; }
                 }
 #endif
