@@ -2,7 +2,7 @@
 chain, and what the loop must present of them: shared by tests/test_host_stream_cases.py (CPU: the cases can fail) and
 tests/test_gpu_host_schedules.py (GPU: the loop under every schedule).
 
-``stream(w, h, n)`` is the input, ``ROWS`` the four option sets, ``SCHEDULES`` the five ways the loop can be scheduled,
+``stream(w, h, n)`` is the input, ``ROWS`` the seven option sets, ``SCHEDULES`` the five ways the loop can be scheduled,
 ``expected_cpu(frames, row)`` the presented stream from the CPU models alone (output size = input size, where the upscale is the
 identity) and ``expected_capi(ctx, frames, row, out_size)`` the same stream through capi.Context, one call at a time on one
 lane, at any output size.
@@ -13,7 +13,7 @@ frames are windows into a larger canvas of synth noise (no exposed border to fil
 a textured square crosses them with a motion of its own; an overlay -- three one-pixel strokes and a block of noise aligned to
 the chroma quads -- is drawn into every frame after the motion, at the same place with the same bytes.  A cut is a new canvas
 seed.  What tests/pair_model.py reports of it (test_host_stream_cases.py asserts it, for every row, at 96 x 64 with 6 frames):
-the four cut pairs match on 139 pixels per thousand or fewer (32 without NV12 input, whose chroma averaging brings unrelated
+the four cut pairs match on 164 pixels per thousand or fewer (41 without NV12 input, whose chroma averaging brings unrelated
 noise closer together), every other pair on 676 or more, against a threshold of 500: ROOM on both sides."""
 from __future__ import annotations
 
@@ -21,16 +21,16 @@ import numpy as np
 
 from linux_fg_amd import capi, synth
 from tests import cases
-from tests import extrapolate_model as ex
-from tests import overlay_model as ov
 from tests import pair_model as pair
+from tests import resample_model as rsm
+from tests import route_cases as rc
 from tests import sharpen_model as sm
 from tests import yuv_model as ym
 from tests.test_gpu_cut import THRESHOLD
 
 MATCH_SAD = 48                                      # what lfg_host gives lfg_set_interpolator
 SMALL = (96, 64, 6)                                 # the stream of the CPU tests and of the anchor
-ROOM = 150                                          # pixels per thousand that every pair keeps between itself and the threshold
+ROOM = rc.ROOM                                      # pixels per thousand that every pair keeps between itself and the threshold
 
 # ---- the stream
 
@@ -87,11 +87,12 @@ def stream(w: int, h: int, n: int):
 # ---- the rows: option sets of lfg_host.  A row is a dict; options(row) is its command line.
 
 def _row(name, setting, factors=None, generation="interpolate", protect=-1, threshold=-1, sharpen=0, nv12_in=False, nv12_out=False,
-         yuv=(ym.BT709, ym.LIMITED, ym.LEFT)):
+         yuv=(ym.BT709, ym.LIMITED, ym.LEFT), bidirectional=-1, half_res=-1, hole_reach=-1, subpel=-1, scale_filter=None):
     """setting: (estimator, refinement radius, interpolator, semantics) as in tests/cases.py.  factors None: the single entry
-    point at lfg_host's default of 0.5."""
+    point at lfg_host's default of 0.5.  scale_filter: a name of tests/resample_model.py, None for lfg_scale."""
     return dict(name=name, setting=setting, factors=factors, generation=generation, protect=protect, threshold=threshold, sharpen=sharpen,
-                nv12_in=nv12_in, nv12_out=nv12_out, yuv=yuv)
+                nv12_in=nv12_in, nv12_out=nv12_out, yuv=yuv, bidirectional=bidirectional, half_res=half_res, hole_reach=hole_reach,
+                subpel=subpel, scale_filter=scale_filter)
 
 
 ROWS = [
@@ -101,6 +102,12 @@ ROWS = [
          nv12_out=True),
     _row("C", ("full", -1, "shader", 0), threshold=THRESHOLD, sharpen=24),
     _row("D", ("full", -1, "compensated", 1), nv12_out=True),
+    _row("E", ("pyramid", 1, "compensated", 1), factors=(0.25, 0.5, 0.75), bidirectional=1, half_res=1, hole_reach=32, threshold=THRESHOLD,
+         sharpen=24, nv12_out=True),
+    _row("F", ("full", -1, "compensated", 1), factors=(0.3, 0.7), subpel=1, half_res=0, threshold=THRESHOLD),
+    # (with the refinement: on this stream of pure noise the pyramid alone matches the moving pair on 502 pixels per thousand,
+    # which leaves no ROOM above the threshold that test_host_stream_cases.py measures every row against)
+    _row("G", ("pyramid", 1, "compensated", 1), protect=0, hole_reach=32, scale_filter="lanczos3", nv12_in=True, nv12_out=True),
 ]
 ROW = {r["name"]: r for r in ROWS}
 
@@ -130,10 +137,16 @@ def options(row):
         out += ["--generation", row["generation"]]
     if row["protect"] >= 0:
         out += ["--protect-static", str(row["protect"])]
+    for option, key in (("--bidirectional", "bidirectional"), ("--half-res-motion", "half_res"), ("--hole-reach", "hole_reach"),
+                        ("--subpel-vectors", "subpel")):
+        if row[key] >= 0:
+            out += [option, str(row[key])]
     if row["threshold"] >= 0:
         out += ["--cut-threshold", str(row["threshold"])]
     if row["sharpen"]:
         out += ["--sharpen", str(row["sharpen"])]
+    if row["scale_filter"]:
+        out += ["--scale-filter", row["scale_filter"]]
     if row["nv12_in"]:
         out += ["--input-format", "nv12"]
     if row["nv12_out"]:
@@ -152,6 +165,8 @@ def without(row, option):
                "interpolator": dict(setting=(estimator, radius, "shader", semantics)),
                "generation": dict(generation="interpolate"),
                "protect-static": dict(protect=-1), "cut-threshold": dict(threshold=-1), "sharpen": dict(sharpen=0),
+               "bidirectional": dict(bidirectional=-1), "half-res-motion": dict(half_res=-1), "hole-reach": dict(hole_reach=-1),
+               "subpel-vectors": dict(subpel=-1), "scale-filter": dict(scale_filter=None),
                "input-format": dict(nv12_in=False), "output-format": dict(nv12_out=False),
                "yuv": dict(yuv=(ym.BT709, ym.LIMITED, ym.LEFT))}[option]
     out = dict(row, **changed)
@@ -197,26 +212,30 @@ _chains = {}
 def chain_of(prev, curr):
     key = (prev.tobytes(), curr.tobytes())
     if key not in _chains:
-        _chains[key] = cases.Chain(prev, curr)
+        _chains[key] = rc.RouteChain(prev, curr)
     return _chains[key]
+
+
+def route_of(row):
+    """The row as a route of tests/route_cases.py: its threshold is a number, and the pair's record decides."""
+    return rc.route(row["setting"], match_sad=MATCH_SAD, cut=row["threshold"] if row["threshold"] >= 0 else "off", generation=row["generation"],
+                    protect=row["protect"], bidirectional=row["bidirectional"], half_res=row["half_res"], reach=row["hole_reach"],
+                    subpel=row["subpel"])
 
 
 def generated_cpu(prev, curr, row):
     """(the pair's generated frames, one per factor; its record, or None with detection off; whether it is a cut)."""
-    setting, factors = row["setting"], the_factors(row)
-    chain = chain_of(prev, curr)
-    compensated = setting[2] == "compensated"
-    ahead = compensated and row["generation"] == "extrapolate"
-    mv = chain.vectors(setting[0], setting[1], setting[3])
-    stats = pair.pair_stats(prev, curr, mv, MATCH_SAD) if row["threshold"] >= 0 else None
-    if stats is not None and pair.cut(stats, row["threshold"]):
-        return ([curr] * len(factors) if ahead else pair.fallback(prev, curr, factors)), stats, True
-    if ahead:
-        return [ex.extrapolate(prev, curr, mv, a, MATCH_SAD) for a in factors], stats, False
-    if compensated and row["protect"] >= 0:
-        mask = ov.static_mask(prev, curr, row["protect"])
-        return [ov.interpolate_masked(prev, curr, mv, mask, t, MATCH_SAD) for t in factors], stats, False
-    return chain.frames(setting, factors, MATCH_SAD), stats, False
+    chain, route = chain_of(prev, curr), route_of(row)
+    detecting = row["threshold"] >= 0
+    return chain.frames(route, the_factors(row)), (chain.stats(route) if detecting else None), detecting and chain.is_cut(route)
+
+
+def scaled_cpu(frame, row):
+    """The upscale at output size = input size: lfg_scale is the identity there; a filter of lfg_resample need not be."""
+    if not row["scale_filter"]:
+        return frame
+    filt = {name: f for f, name in rsm.NAMES.items()}[row["scale_filter"]]
+    return rsm.resample(frame, frame.shape[1], frame.shape[0], filt)
 
 
 def presented_cpu(frame, row):
@@ -231,6 +250,7 @@ def expected_cpu(frames, row):
     input size, each frame an RGBA array or (y, uv); flags[i] says whether frame i is a generated one, cut_at lists the cut
     pairs, permille each pair's matched pixels per thousand (None with detection off)."""
     real = [ym.nv12_to_rgba(*f, *row["yuv"]) for f in inputs(frames, row)] if row["nv12_in"] else list(frames)
+    real = [scaled_cpu(f, row) for f in real]
     shown, cut_at, permille = [(real[0], False)], [], []
     for k in range(1, len(real)):
         generated, stats, is_cut = generated_cpu(real[k - 1], real[k], row)
@@ -247,7 +267,7 @@ def expected_cpu(frames, row):
 
 def expected_capi(ctx, frames, row, out_size):
     """expected_cpu's dict (without permille) from capi.Context at out_size = (width, height): nv12_to_rgba, scale, the setters,
-    interpolate_frames or _multi, sharpen, rgba_to_nv12, last_pair_stats; one lane, a sync after every call.  Each of those calls
+    (or resample), interpolate_frames or _multi, sharpen, rgba_to_nv12, last_pair_stats; one lane, a sync after every call.  Each of those calls
     is held to its model by its own test file: what this stands for is the chain, not the loop."""
     from tests.gpu_kit import DEFAULT, apply
     (h, w), (ow, oh) = frames[0].shape[:2], out_size
@@ -279,6 +299,11 @@ def expected_capi(ctx, frames, row, out_size):
         apply(ctx, row["setting"], match_sad=MATCH_SAD, threshold=row["threshold"])
         ctx.set_static_protection(row["protect"])
         ctx.set_generation(capi.GENERATION_EXTRAPOLATE if row["generation"] == "extrapolate" else capi.GENERATION_INTERPOLATE)
+        ctx.set_bidirectional(row["bidirectional"])
+        ctx.set_half_resolution_motion(row["half_res"])
+        ctx.set_hole_reach(row["hole_reach"])
+        ctx.set_subpixel_vectors(row["subpel"])
+        filt = {name: f for f, name in rsm.NAMES.items()}[row["scale_filter"]] if row["scale_filter"] else None
         shown, flags, cut_at = [], [], []
         for k, fed in enumerate(inputs(frames, row)):
             prev, curr = ups[(k + 1) % 2], ups[k % 2]
@@ -289,7 +314,10 @@ def expected_capi(ctx, frames, row, out_size):
                 ctx.destroy_frame(staged)
             else:
                 ctx.upload(source, fed)
-            ctx.scale(source, curr)
+            if filt is None:
+                ctx.scale(source, curr)
+            else:
+                ctx.resample(source, curr, filt)
             ctx.sync()
             generated = []
             if k > 0:
@@ -308,7 +336,9 @@ def expected_capi(ctx, frames, row, out_size):
     finally:
         ctx.sync()
         ctx.set_generation(capi.GENERATION_INTERPOLATE)
-        ctx.set_static_protection(-1)
+        for off in (ctx.set_static_protection, ctx.set_bidirectional, ctx.set_half_resolution_motion, ctx.set_hole_reach,
+                    ctx.set_subpixel_vectors):
+            off(-1)
         apply(ctx, DEFAULT)
         for f in made:
             ctx.destroy_frame(f)

@@ -1,19 +1,19 @@
 """lfg_host's loop (host/scaler.cpp, frame_manager.cpp, main.cpp) held to the chain with every stage on, under every schedule:
 the option rows and the stream of tests/host_stream_cases.py, every presented byte and the report's counts.
 
-Anchor.  Rows A to D at 96 x 64, output = input, 6 frames, one lane with --sync-present: every presented byte equals the CPU
+Anchor.  Rows A to G at 96 x 64, output = input, 6 frames, one lane with --sync-present: every presented byte equals the CPU
 models' (host_stream_cases.expected_cpu), and so does the same stream made through capi.Context one call at a time
 (expected_capi), which is the reference of the larger tier.
 
-Schedules.  Rows A to D under all five schedules at 640 x 360 -> 1280 x 720 with 12 frames.  Twelve frames is a condition, not a
+Schedules.  Rows A to G under all five schedules at 640 x 360 -> 1280 x 720 with 12 frames.  Twelve frames is a condition, not a
 tuning knob.  Scaler::Initialize gives the read-back ring (1 + lanes) * (factors + 1) + 2 slots, and --sharpen and
 --output-format nv12 keep one buffer per slot (m_sharpened, m_nv12Out); the upload ring has 2 + lanes slots and every lane one
 NV12 staging buffer (m_nv12In):
 
     lanes  factors  read-back slots  presented = 1 + 11 * (factors + 1)
-      3       3          18               45      (row A)
-      3       2          14               34      (row B)
-      3       1          10               23      (rows C, D)
+      3       3          18               45      (rows A, E)
+      3       2          14               34      (rows B, F)
+      3       1          10               23      (rows C, D, G)
       1       3          10               45
 
 The upload ring's 5 slots (3 lanes) take 12 uploads and each lane's staging buffer 4 or more.  So every slot, every per-slot
@@ -93,13 +93,24 @@ def big(ctx):
 
 @pytest.mark.parametrize("name", ROW_IDS)
 def test_the_large_stream_cuts_where_it_is_made_to(big, name):
-    """Upscaled to 720p the stream still cuts at its four pairs (rows A to C), and the chain's frames tell a stale slot: all
+    """Upscaled to 720p the stream still cuts at its four pairs (the rows with detection on), and the chain's frames tell a stale slot: all
     distinct but for the frames a cut repeats."""
     want = big[1][name]
     row = hc.ROW[name]
     assert want["cut_at"] == (list(hc.cut_pairs(BIG_N)) if row["threshold"] >= 0 else [])
     parts = {b"".join(p.tobytes() for p in (f if isinstance(f, tuple) else (f,))) for f in want["frames"]}
     assert len(parts) == want["presented"] - len(hc.the_factors(row)) * want["cuts"]
+
+
+def test_the_scale_filter_shows_on_the_large_stream(ctx, big):
+    """Row G's --scale-filter lanczos3 is the identity at the anchor's output size = input size (test_host_stream_cases.py:
+    test_the_scale_filter_shows_where_the_loop_scales); here, where the loop scales by 2, the chain without it presents other
+    bytes in every frame, so a loop that dropped the option would fail row G's schedules."""
+    row = hc.ROW["G"]
+    frames = hc.stream(*BIG_IN, BIG_N)[:3]
+    less = hc.expected_capi(ctx, frames, hc.without(row, "scale-filter"), BIG_OUT)
+    with_filter = big[1]["G"]["frames"][:less["presented"]]
+    assert less["presented"] == 5 and not any(hc.same(x, y) for x, y in zip(with_filter, less["frames"]))
 
 
 @pytest.mark.parametrize("schedule", hc.SCHEDULES, ids=[s[0] for s in hc.SCHEDULES])
