@@ -21,46 +21,6 @@ bool FrameManager::Initialize(uint32_t /*width*/, uint32_t /*height*/) {
 
 void FrameManager::Cleanup() { m_initialized = false; }
 
-bool FrameManager::SetGeneration(int generation) {
-    if (lfg_set_generation(Ctx(), generation) != LFG_OK) {
-        LOG_ERROR("Failed to set the generation: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
-        return false;
-    }
-    return true;
-}
-
-bool FrameManager::SetBidirectional(int tolerance) {
-    if (lfg_set_bidirectional(Ctx(), tolerance) != LFG_OK) {
-        LOG_ERROR("Failed to set the bidirectional tolerance: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
-        return false;
-    }
-    return true;
-}
-
-bool FrameManager::SetHalfResolutionMotion(int radius) {
-    if (lfg_set_half_resolution_motion(Ctx(), radius) != LFG_OK) {
-        LOG_ERROR("Failed to set half-resolution motion: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
-        return false;
-    }
-    return true;
-}
-
-bool FrameManager::SetHoleReach(int reach) {
-    if (lfg_set_hole_reach(Ctx(), reach) != LFG_OK) {
-        LOG_ERROR("Failed to set the hole reach: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
-        return false;
-    }
-    return true;
-}
-
-bool FrameManager::SetSubpixelVectors(int radius) {
-    if (lfg_set_subpixel_vectors(Ctx(), radius) != LFG_OK) {
-        LOG_ERROR("Failed to set sub-pixel vectors: ", Ctx() ? lfg_last_error(Ctx()) : "no device context");
-        return false;
-    }
-    return true;
-}
-
 bool FrameManager::CreateFrame(Frame& frame, uint32_t width, uint32_t height) {
     lfg_frame f{};
     const uint32_t format = frame.format;                    // RGBA8 unless the caller asked otherwise

@@ -66,31 +66,6 @@ public:
     bool InterpolateFramesMultiAsync(const Frame& previous, const Frame& current, const std::vector<Frame*>& outputs,
                                      const std::vector<float>& factors);
 
-    // What the four calls above generate (lfg_set_generation): LFG_GENERATION_INTERPOLATE (default), frames between previous and
-    // current, or LFG_GENERATION_EXTRAPOLATE, frames AHEAD of current by `factor` of an interval (with the compensated
-    // interpolator selected on the device context; the reference has no such mode).
-    bool SetGeneration(int generation);
-
-    // The bidirectional route of the four calls above (lfg_set_bidirectional): -1 (default) off; 0 .. 64, with the compensated
-    // interpolator, interpolation and no static protection selected on the device context, the pair is measured both ways and a
-    // vector projects only where the two fields agree within `tolerance` (the reference has no such mode).
-    bool SetBidirectional(int tolerance);
-
-    // Half-resolution motion in the four calls above (lfg_set_half_resolution_motion): -1 (default) off; 0 .. 2, the selected
-    // estimator runs on both frames halved and lfg_motion_expand carries its field to full size with this window radius (the
-    // reference has no such mode).
-    bool SetHalfResolutionMotion(int radius);
-
-    // The hole fill's reach in the four calls above where they take the compensated, masked or bidirectional route
-    // (lfg_set_hole_reach): -1 (default) the 16 px walk; 1 .. LFG_HOLE_REACH_MAX, the fill plane of that reach (the reference
-    // has no such mode).  Extrapolated frames keep the walk.
-    bool SetHoleReach(int reach);
-
-    // Quarter-pixel vectors in the four calls above where they take the plain compensated route with the walk
-    // (lfg_set_subpixel_vectors): -1 (default) off; 0 .. 2, the final integer field is refined to quarter pixels with this window
-    // radius and the sub-pixel compensated call runs (the reference has no such mode).
-    bool SetSubpixelVectors(int radius);
-
     // The one exchange of the multi-GPU path: broadcast a frame from rank `root` to every rank (asynchronous, on the
     // device context's communication stream) and make later work on the compute queue wait for it.
     bool BroadcastFrame(Frame& frame, int root);

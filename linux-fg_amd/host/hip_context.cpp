@@ -40,6 +40,25 @@ bool HipContext::WaitIdle() {
     return true;
 }
 
+bool HipContext::SetRoute(const Route& r) {
+    constexpr int kMatchSad = 48;                             // the compensated interpolator's match gate (lfg_set_interpolator)
+    if (lfg_set_semantics(m_ctx, r.semantics) != LFG_OK ||
+        lfg_set_motion_estimator(m_ctx, r.estimator) != LFG_OK ||
+        lfg_set_interpolator(m_ctx, r.interpolator, kMatchSad) != LFG_OK ||
+        lfg_set_vector_refinement(m_ctx, r.refineRadius) != LFG_OK ||
+        lfg_set_cut_detection(m_ctx, r.cutThreshold) != LFG_OK ||
+        lfg_set_static_protection(m_ctx, r.staticTolerance) != LFG_OK ||
+        lfg_set_generation(m_ctx, r.generation) != LFG_OK ||
+        lfg_set_bidirectional(m_ctx, r.bidirectional) != LFG_OK ||
+        lfg_set_half_resolution_motion(m_ctx, r.halfResMotion) != LFG_OK ||
+        lfg_set_hole_reach(m_ctx, r.holeReach) != LFG_OK ||
+        lfg_set_subpixel_vectors(m_ctx, r.subpelVectors) != LFG_OK) {
+        LOG_ERROR("Failed to set the motion options: ", lfg_last_error(m_ctx));
+        return false;
+    }
+    return true;
+}
+
 // The id file: 8 bytes of magic, the launcher's 8-byte run nonce, then the 128-byte id.  A file left behind by an earlier run
 // (same name, rank 0 of THIS run not there yet) must not be taken for this run's: rank 0 removes the name before it makes
 // the id and again once every rank has joined, and a receiver only accepts a file that carries its own nonce

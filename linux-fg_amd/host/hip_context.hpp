@@ -9,6 +9,14 @@
 #include "linuxfg_hip.h"
 #include "logger.hpp"
 
+// The context's settings that decide how a generated frame is made, each the argument of the lfg_set_* call named after it
+// (include/linuxfg_hip.h says what the values mean; the reference has none of these).  Defaults: the reference's behaviour.
+struct Route {
+    int semantics = LFG_SEMANTICS_REFERENCE, estimator = LFG_ESTIMATOR_FULL_SEARCH, interpolator = LFG_INTERPOLATOR_SHADER;
+    int refineRadius = -1, cutThreshold = -1, staticTolerance = -1;
+    int generation = LFG_GENERATION_INTERPOLATE, bidirectional = -1, halfResMotion = -1, holeReach = -1, subpelVectors = -1;
+};
+
 class HipContext {
 public:
     static HipContext& Get() {
@@ -25,6 +33,7 @@ public:
     void* GetComputeQueue() const;                            // the HIP stream (VulkanContext::GetComputeQueue)
     int GetDeviceOrdinal() const;
     bool WaitIdle();                                          // vkQueueWaitIdle
+    bool SetRoute(const Route& route);                        // every lfg_set_* of a Route, before the first frame
 
     // Several GPUs, one process each (no reference counterpart: one queue, no communication,
     // src/vulkan_context.cpp:130-151).  Rank 0 removes `idFile`, makes the communicator id and leaves it there (magic,

@@ -9,9 +9,7 @@ import pytest
 
 from linux_fg_amd import capi
 from oracle import scale_f64 as f64
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "linux-fg_amd", "lfg_host")
+from tests.host_cli import HOST, ROOT, built
 
 
 @pytest.fixture(scope="module")
@@ -123,9 +121,7 @@ def host_run(tmp_path, frames, out_size, *options, timeout=300):
     global _host_failed
     if _host_failed:
         pytest.fail(f"lfg_host is not started again in this session: {_host_failed}", pytrace=False)
-    if not os.path.exists(HOST):
-        import __graft_entry__ as entry
-        entry.build()
+    built(HOST)
     options = [str(o) for o in options]
 
     def fmt(name):
