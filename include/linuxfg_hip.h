@@ -771,6 +771,48 @@ int  lfg_frame_diff(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, ui
 typedef struct lfg_frame_diff_summary { uint64_t pixels, differing, over_1; uint32_t max_abs, p50, p99; double mse, psnr_db; } lfg_frame_diff_summary;
 int  lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, uint32_t channel_mask, lfg_frame_diff_summary *out);
 
+/* Structural similarity: an exact-integer SSIM of two frames that live on the device, beside lfg_frame_diff's squared error.
+ * No reference counterpart.  Integer arithmetic only; it depends on no setting of the context.  The window layout and the
+ * constants are those of the integer SSIM of x264 and of FFmpeg's ssim filter; those finish in float, this one in integers, so
+ * the figures are comparable in kind and not digit for digit.
+ *   Inputs: a, b RGBA8, both W x H with 8 <= W, H <= 262,144; channel_mask in 1 .. 15, bit c standing for channel c.
+ *   Windows: the frame is cut into 4 x 4 blocks, bw = W >> 2 by bh = H >> 2 of them; the columns and rows past the last
+ *   multiple of 4 are not looked at.  A window is 2 x 2 blocks (8 x 8 pixels) at every block position (wx, wy) with
+ *   wx < bw - 1, wy < bh - 1: (bw - 1) * (bh - 1) windows at stride 4, overlapping.
+ *   Per window and channel c, over its 64 pixels: s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b;
+ *     vars = 64 ss - s1^2 - s2^2;  covar = 64 s12 - s1 s2;
+ *     N = (2 s1 s2 + 416) (2 covar + 235963);  D = (s1^2 + s2^2 + 416) (vars + 235963), both signed 64-bit;
+ *     Q_c = sign(N) floor(|N| 2^24 / D).
+ *   (416 and 235963 are 0.01^2 255^2 64 and 0.03^2 255^2 64 63, rounded.  0 <= |N| <= D < 2^58, so Q_c is in [-2^24, 2^24];
+ *   it is 2^24 exactly where the window is the same in both frames, and negative values occur: a checkerboard against its
+ *   inverse.)
+ *   windows = (bw - 1) (bh - 1);  sum[c] = the sum of Q_c over the windows, signed, for all four channels whatever the mask;
+ *   with m = the smallest Q_c over the channels of channel_mask:  hist[max(m, 0) >> 18] counts the window -- bin 64 the
+ *   windows identical in every masked channel, bin 0 every negative value as well;
+ *   worst = the smallest key ((m + 2^24) << 32) | (wy << 16) | wx over the windows: the lowest value, then the topmost,
+ *   then the leftmost window; all ones where there is none.
+ * All 71 words are 64-bit integers, so neither the order of evaluation nor any tiling changes a result.
+ *   accumulate = 0: the call WRITES the 71 words of `device_stats` (568 bytes of device memory, 8-byte aligned);
+ *   accumulate = 1: the call ADDS to them: windows, sum and hist are added, worst becomes the minimum of both.
+ * Frames: as lfg_frame_diff's -- 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4); a and b may overlap or be the
+ * same frame; a view made with lfg_frame_wrap into a larger frame is a region of interest.  A NULL pointer, a wrong format,
+ * differing sizes, a misaligned frame or record, a mask outside 1 .. 15, any other value of accumulate, or a width or height
+ * below 8 or above 262,144 returns LFG_ERR_INVALID before anything is enqueued.  Enqueued on the selected lane (a clear of the
+ * record unless accumulate is 1, one launch of a fixed grid); keeps no device memory; outside the stage timers. */
+typedef struct lfg_frame_ssim_stats { uint64_t windows; int64_t sum[4]; uint64_t hist[65]; uint64_t worst; } lfg_frame_ssim_stats;   /* 568 bytes */
+int  lfg_frame_ssim(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, uint32_t channel_mask,
+                    int accumulate, void *device_stats /* 568 bytes of device memory, 8-byte aligned */);
+/* A record in HOST memory (copied from the device by the caller) as the figures one quotes.  A pure host function: no
+ * context, no GPU.  channel_mask should be the one the record was made with: hist and worst depend on it, sum does not.
+ *   ssim[c] = sum[c] / (windows * 2^24), in double, for all four channels;  all = the mean of ssim[c] over the channels of
+ *   channel_mask;  db = -10 log10(1 - all), HUGE_VAL where all is 1;
+ *   identical = hist[64];  below_half = hist[0] + .. + hist[31] (the windows with m < 0.5);
+ *   worst_value = ((worst >> 32) - 2^24) / 2^24, in double;  worst_x = 4 wx, worst_y = 4 wy: the window's first pixel.
+ * Returns LFG_ERR_INVALID for a NULL pointer, a mask outside 1 .. 15, windows = 0 or a histogram that does not sum to
+ * windows. */
+typedef struct lfg_frame_ssim_summary { uint64_t windows, identical, below_half; double ssim[4], all, db, worst_value; uint32_t worst_x, worst_y; } lfg_frame_ssim_summary;
+int  lfg_frame_ssim_summarize(const lfg_frame_ssim_stats *host_stats, uint32_t channel_mask, lfg_frame_ssim_summary *out);
+
 /* NV12 input and output: colour conversion between 4:2:0 YUV as decoders write it and encoders read it, and the RGBA8 frames of
  * every other call.  No reference counterpart (the reference captures and presents RGBA only, src/frame_manager.hpp:15).
  * Integer arithmetic only; it depends on no setting of the context.  NV12 is no lfg_format: the planes are described by an

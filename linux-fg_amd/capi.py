@@ -86,6 +86,31 @@ class FrameDiffSummary(ctypes.Structure):
         return {name: (float if name in ("mse", "psnr_db") else int)(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FrameSsimStats(ctypes.Structure):
+    """struct lfg_frame_ssim_stats."""
+    _fields_ = [("windows", ctypes.c_uint64), ("sum", ctypes.c_int64 * 4), ("hist", ctypes.c_uint64 * 65), ("worst", ctypes.c_uint64)]
+
+    def as_tuple(self):
+        return int(self.windows), tuple(int(v) for v in self.sum), tuple(int(v) for v in self.hist), int(self.worst)
+
+
+class FrameSsimSummary(ctypes.Structure):
+    """struct lfg_frame_ssim_summary."""
+    _fields_ = [("windows", ctypes.c_uint64), ("identical", ctypes.c_uint64), ("below_half", ctypes.c_uint64),
+                ("ssim", ctypes.c_double * 4), ("all", ctypes.c_double), ("db", ctypes.c_double), ("worst_value", ctypes.c_double),
+                ("worst_x", ctypes.c_uint32), ("worst_y", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {"windows": int(self.windows), "identical": int(self.identical), "below_half": int(self.below_half),
+                "ssim": tuple(float(v) for v in self.ssim), "all": float(self.all), "db": float(self.db),
+                "worst_value": float(self.worst_value), "worst_x": int(self.worst_x), "worst_y": int(self.worst_y)}
+
+
+# How frame_ssim.hip tiles a frame (its kSsimStripWindows, kSsimSegmentRows, kSsimWaves and kSsimGroupsPerCu, held equal by
+# tests/test_ssim_model.py): a wave owns 63 windows of a block row, an item of its walk is 8 window rows of them, a workgroup is 4
+# waves and the grid at most 4 workgroups per CU.  No result depends on them; the GPU tests name their seam sizes from them.
+SSIM_STRIP_WINDOWS, SSIM_SEGMENT_ROWS, SSIM_GROUP_WAVES, SSIM_GROUPS_PER_CU = 63, 8, 4, 4
+
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 _FP = ctypes.POINTER(Frame)
 
@@ -173,6 +198,8 @@ SIGNATURES = {
     "lfg_last_pair_stats": (_i, [_vp, ctypes.POINTER(PairStats), ctypes.POINTER(_i)]),
     "lfg_frame_diff": (_i, [_vp, _FP, _FP, _u32, _i, _vp]),
     "lfg_frame_diff_summarize": (_i, [ctypes.POINTER(FrameDiffStats), _u32, ctypes.POINTER(FrameDiffSummary)]),
+    "lfg_frame_ssim": (_i, [_vp, _FP, _FP, _u32, _i, _vp]),
+    "lfg_frame_ssim_summarize": (_i, [ctypes.POINTER(FrameSsimStats), _u32, ctypes.POINTER(FrameSsimSummary)]),
     "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
     "lfg_rgba_to_nv12": (_i, [_vp, _FP, ctypes.POINTER(Nv12), _i, _i, _i]),
     "lfg_sharpen": (_i, [_vp, _FP, _FP, _i]),
@@ -215,6 +242,18 @@ def summarize(record, channel_mask: int = 0xF) -> dict:
     rc = load().lfg_frame_diff_summarize(ctypes.byref(s), int(channel_mask), ctypes.byref(out))
     if rc != 0:
         raise LfgError(f"lfg_frame_diff_summarize failed ({rc}): bad mask, no pixels, or a histogram that does not sum to them")
+    return out.as_dict()
+
+
+def summarize_ssim(record, channel_mask: int = 0xF) -> dict:
+    """A record (windows, sum, hist, worst) -- read_ssim_record's tuple -- as lfg_frame_ssim_summarize's figures: a dict of
+    windows, identical, below_half, ssim (4), all, db (inf on identical frames), worst_value, worst_x and worst_y.  Needs no
+    context and no GPU."""
+    windows, total, hist, worst = record
+    s, out = FrameSsimStats(int(windows), (ctypes.c_int64 * 4)(*total), (ctypes.c_uint64 * 65)(*hist), int(worst)), FrameSsimSummary()
+    rc = load().lfg_frame_ssim_summarize(ctypes.byref(s), int(channel_mask), ctypes.byref(out))
+    if rc != 0:
+        raise LfgError(f"lfg_frame_ssim_summarize failed ({rc}): bad mask, no windows, or a histogram that does not sum to them")
     return out.as_dict()
 
 
@@ -739,6 +778,22 @@ class Context:
         """(pixels, sse tuple, hist tuple) of a record in device memory; waits for the context."""
         words = [int(v) for v in self.download(record).reshape(-1).view(np.uint64)]
         return words[0], tuple(words[1:5]), tuple(words[5:])
+
+    # -- structural similarity.  A record is 568 bytes of device memory: here a 142 x 1 RGBA8 frame.
+    def create_ssim_record(self) -> Frame:
+        return self.create_frame(ctypes.sizeof(FrameSsimStats) // 4, 1)
+
+    def frame_ssim(self, a: Frame, b: Frame, record: Frame, channel_mask: int = 0xF, accumulate: bool = False):
+        """Integer SSIM (lfg_frame_ssim) over 8 x 8 windows at stride 4: the sum of Q per channel, the histogram of the smallest
+        Q over the channels of `channel_mask` and the worst window, written into `record` (create_ssim_record) or added to it."""
+        self._check(self.lib.lfg_frame_ssim(self.h, ctypes.byref(a), ctypes.byref(b), int(channel_mask), int(accumulate),
+                                            _vp(record.data)), "lfg_frame_ssim")
+
+    def read_ssim_record(self, record: Frame):
+        """(windows, sum tuple of 4 signed, hist tuple of 65, worst) of a record in device memory; waits for the context."""
+        raw = self.download(record).reshape(-1)
+        words = [int(v) for v in raw.view(np.uint64)]
+        return words[0], tuple(int(v) for v in raw.view(np.int64)[1:5]), tuple(words[5:70]), words[70]
 
     # -- NV12 input and output.  The planes are caller-owned device memory; create_nv12 keeps both in one MV_S8X2 frame of
     # W/2 x 3H/2 (W bytes per row: H rows of luma, then H/2 rows of pairs), so upload() and download() move them.

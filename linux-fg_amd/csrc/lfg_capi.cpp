@@ -1864,6 +1864,58 @@ LFG_EXPORT int lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, 
     return LFG_OK;
 }
 
+// ---- structural similarity (frame_ssim.hip)
+
+LFG_EXPORT int lfg_frame_ssim(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, uint32_t channel_mask,
+                              int accumulate, void *device_stats) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(a, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(b, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: a and b must be non-empty RGBA8");
+    if (!same_size(a, b)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: a and b differ in size");
+    if (a->width < 8u || a->height < 8u || a->width > 262144u || a->height > 262144u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: width and height must be in [8, 262144]");
+    if ((a->pitch | b->pitch) % 4u || ((uintptr_t)a->data | (uintptr_t)b->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: RGBA8 frames must be 4-byte aligned");
+    if (channel_mask < 1u || channel_mask > 15u) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: channel_mask must be in [1, 15]");
+    if (accumulate != 0 && accumulate != 1) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: accumulate must be 0 or 1");
+    if (!device_stats || (uintptr_t)device_stats % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_ssim: device_stats must be non-NULL and 8-byte aligned");
+    hipError_t e = lfg::launch_frame_ssim(ctx->cur().stream, *a, *b, channel_mask, accumulate == 1, ctx->device_cus, device_stats);
+    if (e != hipSuccess) return fail_hip(ctx, e, "frame ssim kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_frame_ssim_summarize(const lfg_frame_ssim_stats *host_stats, uint32_t channel_mask, lfg_frame_ssim_summary *out) {
+    if (!host_stats || !out || channel_mask < 1u || channel_mask > 15u || host_stats->windows == 0) return LFG_ERR_INVALID;
+    const uint64_t windows = host_stats->windows;
+    uint64_t total = 0, below = 0;
+    for (int k = 0; k < 65; ++k) {
+        if (host_stats->hist[k] > windows - total) return LFG_ERR_INVALID;      // (no sum past windows: no wrap either)
+        total += host_stats->hist[k];
+        if (k < 32) below += host_stats->hist[k];
+    }
+    if (total != windows) return LFG_ERR_INVALID;
+    lfg_frame_ssim_summary s{};
+    s.windows = windows;
+    s.identical = host_stats->hist[64];
+    s.below_half = below;
+    const double scale = (double)windows * 16777216.0;
+    double sum = 0.0;
+    int channels = 0;
+    for (int c = 0; c < 4; ++c) {
+        s.ssim[c] = (double)host_stats->sum[c] / scale;
+        if ((channel_mask >> c) & 1u) { sum += s.ssim[c]; ++channels; }
+    }
+    s.all = sum / (double)channels;
+    s.db = s.all < 1.0 ? -10.0 * std::log10(1.0 - s.all) : HUGE_VAL;
+    s.worst_value = ((double)(host_stats->worst >> 32) - 16777216.0) / 16777216.0;
+    s.worst_x = 4u * (uint32_t)(host_stats->worst & 0xffffu);
+    s.worst_y = 4u * (uint32_t)((host_stats->worst >> 16) & 0xffffu);
+    *out = s;
+    return LFG_OK;
+}
+
 // ---- colour conversion (yuv_convert.hip)
 
 LFG_EXPORT int lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_yuv[9]) {

@@ -386,6 +386,11 @@ hipError_t launch_cut_fallback(hipStream_t s, const lfg_frame &prev, const lfg_f
 // that adds the pair's sums and histogram to it; 16-byte loads where base and pitch of both frames allow, dword loads otherwise.
 hipError_t launch_frame_diff(hipStream_t s, const lfg_frame &a, const lfg_frame &b, uint32_t channelMask, bool accumulate,
                              int deviceCus, void *stats);
+// Structural similarity (frame_ssim.hip): clears the 568-byte record `stats` (zeros, `worst` all ones) unless `accumulate`, then
+// enqueues the fixed grid that adds the pair's windows to it; 16-byte loads where base and pitch of both frames allow, dword
+// loads otherwise.  The frames are at least 8 x 8.
+hipError_t launch_frame_ssim(hipStream_t s, const lfg_frame &a, const lfg_frame &b, uint32_t channelMask, bool accumulate,
+                             int deviceCus, void *stats);
 // Colour conversion (yuv_convert.hip): the coefficients of lfg_yuv_coefficients and the range's offset as the kernels take them;
 // one launch each; yuv_grid_ok says whether a frame of this size fits the launch's grid.
 struct YuvCoefficients { int32_t to_rgb[5]; int32_t to_yuv[9]; int32_t offset; };

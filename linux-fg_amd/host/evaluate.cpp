@@ -11,7 +11,6 @@ namespace {
 lfg_context* Ctx() { return HipContext::Get().GetDevice(); }
 
 constexpr uint32_t kMask = 0xF;
-constexpr uint32_t kRecordTexels = (uint32_t)(sizeof(lfg_frame_diff_stats) / 4);     // a record as a row of RGBA8 texels
 
 std::string SummaryJson(const lfg_frame_diff_stats& s, const lfg_frame_diff_summary& m) {
     char psnr[64], text[640];
@@ -24,6 +23,28 @@ std::string SummaryJson(const lfg_frame_diff_stats& s, const lfg_frame_diff_summ
              m.mse, psnr, (unsigned long long)s.sse[0], (unsigned long long)s.sse[1], (unsigned long long)s.sse[2],
              (unsigned long long)s.sse[3]);
     return text;
+}
+
+// The "ssim" value of a summary object: the record's figures, or null where the output is too small for a window.
+std::string SsimJson(bool measured, const lfg_frame_ssim_stats& s, const lfg_frame_ssim_summary& m) {
+    if (!measured) return "null";
+    char db[64], text[960];
+    if (std::isinf(m.db)) snprintf(db, sizeof db, "null");
+    else snprintf(db, sizeof db, "%.17g", m.db);
+    snprintf(text, sizeof text,
+             "{\"windows\": %llu, \"all\": %.17g, \"db\": %s, \"channels\": [%.17g, %.17g, %.17g, %.17g], "
+             "\"sum\": [%lld, %lld, %lld, %lld], \"identical\": %llu, \"below_half\": %llu, "
+             "\"worst\": {\"value\": %.17g, \"x\": %u, \"y\": %u}}",
+             (unsigned long long)m.windows, m.all, db, m.ssim[0], m.ssim[1], m.ssim[2], m.ssim[3], (long long)s.sum[0],
+             (long long)s.sum[1], (long long)s.sum[2], (long long)s.sum[3], (unsigned long long)m.identical,
+             (unsigned long long)m.below_half, m.worst_value, m.worst_x, m.worst_y);
+    return text;
+}
+
+// A summary object with "ssim" behind its last key.
+std::string WithSsim(std::string summary, const std::string& ssim) {
+    summary.insert(summary.size() - 1, ", \"ssim\": " + ssim);
+    return summary;
 }
 
 // Everything the loop owns, released on every way out.
@@ -53,9 +74,11 @@ bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeigh
         return false;
     }
     Resources r;
-    const size_t inBytes = (size_t)inputWidth * inputHeight * 4, recordBytes = 2 * sizeof(lfg_frame_diff_stats);
+    const size_t inBytes = (size_t)inputWidth * inputHeight * 4, diffBytes = 2 * sizeof(lfg_frame_diff_stats);
+    const size_t recordBytes = diffBytes + 2 * sizeof(lfg_frame_ssim_stats);
+    const bool ssim = outputWidth >= 8 && outputHeight >= 8;    // lfg_frame_ssim's smallest frame: one window
     bool ok = fm.CreateFrame(r.input, inputWidth, inputHeight) && fm.CreateFrame(r.out, outputWidth, outputHeight) &&
-              fm.CreateFrame(r.records, 2 * kRecordTexels, 1) && fm.CreateStagingBuffer(r.host, recordBytes);
+              fm.CreateFrame(r.records, (uint32_t)(recordBytes / 4), 1) && fm.CreateStagingBuffer(r.host, recordBytes);
     for (Frame& f : r.up) ok = ok && fm.CreateFrame(f, outputWidth, outputHeight);
     if (!ok || lfg_lanes(Ctx(), 1) != LFG_OK || lfg_ring_create(Ctx(), 3, inBytes, &r.ring) != LFG_OK) {
         LOG_ERROR("Failed to create the evaluation's frames: ", lfg_last_error(Ctx()));
@@ -63,6 +86,12 @@ bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeigh
     }
     void* generated = r.records.data;
     void* repeated = static_cast<uint8_t*>(r.records.data) + sizeof(lfg_frame_diff_stats);
+    void* generatedSsim = static_cast<uint8_t*>(r.records.data) + diffBytes;
+    void* repeatedSsim = static_cast<uint8_t*>(generatedSsim) + sizeof(lfg_frame_ssim_stats);
+    // lfg_frame_ssim beside a lfg_frame_diff, into the record of its own
+    auto similar = [&](const lfg_frame& x, const lfg_frame& y, uint64_t k, void* record) {
+        return !ssim || lfg_frame_ssim(Ctx(), &x, &y, kMask, k > 0 ? 1 : 0, record) == LFG_OK;
+    };
 
     // the next source frame, upscaled into `into`: the upload is ordered behind the scale that last read r.input
     auto next = [&](Frame& into) {
@@ -90,11 +119,11 @@ bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeigh
         // interpolate: frames 2k and 2k + 2 give 2k + 1.  extrapolate: frames 2k and 2k + 1 give 2k + 2, one interval ahead of
         // the newest frame, and the yardstick is that newest frame shown again
         const bool enqueued = extrapolate ? lfg_interpolate_frames(Ctx(), &p, &h, &o, 1.0f) == LFG_OK &&
-                                                lfg_frame_diff(Ctx(), &o, &c, kMask, k > 0 ? 1 : 0, generated) == LFG_OK &&
-                                                lfg_frame_diff(Ctx(), &h, &c, kMask, k > 0 ? 1 : 0, repeated) == LFG_OK
+                                                lfg_frame_diff(Ctx(), &o, &c, kMask, k > 0 ? 1 : 0, generated) == LFG_OK && similar(o, c, k, generatedSsim) &&
+                                                lfg_frame_diff(Ctx(), &h, &c, kMask, k > 0 ? 1 : 0, repeated) == LFG_OK && similar(h, c, k, repeatedSsim)
                                           : lfg_interpolate_frames(Ctx(), &p, &c, &o, 0.5f) == LFG_OK &&
-                                                lfg_frame_diff(Ctx(), &o, &h, kMask, k > 0 ? 1 : 0, generated) == LFG_OK &&
-                                                lfg_frame_diff(Ctx(), &p, &h, kMask, k > 0 ? 1 : 0, repeated) == LFG_OK;
+                                                lfg_frame_diff(Ctx(), &o, &h, kMask, k > 0 ? 1 : 0, generated) == LFG_OK && similar(o, h, k, generatedSsim) &&
+                                                lfg_frame_diff(Ctx(), &p, &h, kMask, k > 0 ? 1 : 0, repeated) == LFG_OK && similar(p, h, k, repeatedSsim);
         if (!enqueued) {
             LOG_ERROR("Failed to enqueue pair ", k, ": ", lfg_last_error(Ctx()));
             return false;
@@ -110,14 +139,19 @@ bool RunEvaluation(FrameSource& source, uint32_t inputWidth, uint32_t inputHeigh
 
     lfg_frame_diff_stats stats[2];
     lfg_frame_diff_summary summary[2];
-    memcpy(stats, r.host, recordBytes);
+    lfg_frame_ssim_stats ssimStats[2];
+    lfg_frame_ssim_summary ssimSummary[2] = {};
+    memcpy(stats, r.host, diffBytes);
+    memcpy(ssimStats, static_cast<uint8_t*>(r.host) + diffBytes, sizeof ssimStats);
     for (int i = 0; i < 2; ++i)
-        if (lfg_frame_diff_summarize(&stats[i], kMask, &summary[i]) != LFG_OK) {
+        if (lfg_frame_diff_summarize(&stats[i], kMask, &summary[i]) != LFG_OK ||
+            (ssim && lfg_frame_ssim_summarize(&ssimStats[i], kMask, &ssimSummary[i]) != LFG_OK)) {
             LOG_ERROR("The ", i == 0 ? "generated" : "repeated", " record is inconsistent");
             return false;
         }
     result.pairs = pairs;
-    result.json = "{\"pairs\": " + std::to_string(pairs) + ", \"generated\": " + SummaryJson(stats[0], summary[0]) +
-                  ", \"repeated\": " + SummaryJson(stats[1], summary[1]) + "}";
+    result.json = "{\"pairs\": " + std::to_string(pairs) + ", \"generated\": " +
+                  WithSsim(SummaryJson(stats[0], summary[0]), SsimJson(ssim, ssimStats[0], ssimSummary[0])) + ", \"repeated\": " +
+                  WithSsim(SummaryJson(stats[1], summary[1]), SsimJson(ssim, ssimStats[1], ssimSummary[1])) + "}";
     return true;
 }

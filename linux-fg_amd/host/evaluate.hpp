@@ -5,6 +5,9 @@
 //     lfg_frame_diff(out,    up[2k+1], generated, 0xF, k > 0)
 //     lfg_frame_diff(up[2k], up[2k+1], repeated,  0xF, k > 0)     the yardstick: showing the previous frame again
 // on one lane, with no wait before the end: one lfg_sync, one download of both records, lfg_frame_diff_summarize on each.
+// Beside each lfg_frame_diff an lfg_frame_ssim of the same two frames goes into a record of its own (downloaded with the
+// others, summarized by lfg_frame_ssim_summarize into the object's "ssim" key), unless the output is smaller than one 8 x 8
+// window in either dimension: then no such call is made and the key is null.
 // Nothing is presented.  Scaler::ProcessFrame is not involved.
 #pragma once
 #include <string>

@@ -97,9 +97,9 @@ def padded(ctx, host):
     return big, capi.Context.wrap(big.data, w, h, pitch=(w + 1) * 4)
 
 
-def kernel_resources():
-    """{"wide" / "dword": "vgprs ..., lds ..., waves/SIMD ..."} of the frame_diff kernels, from the notes of the library's code
-    objects (llvm-objdump --offloading unbundles them into the working directory, here a temporary one)."""
+def kernel_resources(kernel="frame_diff_kernel"):
+    """{"wide" / "dword": "vgprs ..., lds ..., waves/SIMD ..."} of the two variants of `kernel`, from the notes of the library's
+    code objects (llvm-objdump --offloading unbundles them into the working directory, here a temporary one)."""
     llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
     found = {}
     with tempfile.TemporaryDirectory() as d:
@@ -108,7 +108,7 @@ def kernel_resources():
         for f in sorted(glob.glob(os.path.join(d, "*gfx950*"))):
             notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", f], capture_output=True, text=True).stdout
             for block in notes.split("  - .agpr_count:")[1:]:
-                name = re.search(r"\.name:\s+(\S*frame_diff_kernel\S*)", block)
+                name = re.search(rf"\.name:\s+(\S*{kernel}\S*)", block)
                 if not name:
                     continue
                 get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", block)[1])  # noqa: E731

@@ -5,7 +5,9 @@ frame, whose pair's (40, -24) is beyond the full search's 16 px and inside the p
 of independent noise on all three frames; the first pan under a HUD of thin white glyphs and bars that stands still in all three
 frames.  Seven routes: repeating frame 0, and lfg_interpolate_frames under six settings, the last with
 static-overlay protection (lfg_set_static_protection at tolerance 0).
-Everything goes through lfg_interpolate_frames + lfg_frame_diff, with one sync per route (the read of its record).
+Beside PSNR each route gets its SSIM over the same channels (lfg_frame_ssim: the mean over the 8 x 8 windows) and the number of
+windows below 0.5, which a halo or a torn overlay moves and a uniform error of the same size does not.
+Everything goes through lfg_interpolate_frames + lfg_frame_diff + lfg_frame_ssim, with one sync per route (the read of its records).
 
     python tools/quality_report.py [--sizes 1080p,4k] [--json out.json] [--out report.txt]
 """
@@ -75,14 +77,17 @@ def main():
             w, h = SIZES[size]
             for content, f0, f1, f2 in triples(w, h):
                 p, t, c, o = ctx.frame_from(f0), ctx.frame_from(f1), ctx.frame_from(f2), ctx.create_frame(w, h)
-                r = ctx.create_diff_record()
+                r, rs = ctx.create_diff_record(), ctx.create_ssim_record()
 
                 def row(route):
                     s = capi.summarize(ctx.read_diff_record(r), MASK)       # the route's one sync
+                    q = capi.summarize_ssim(ctx.read_ssim_record(rs), MASK)
                     emit(rows, {"size": size, "content": content, "route": route, "psnr_db": s["psnr_db"], "differing": s["differing"],
-                                "over_1": s["over_1"], "p50": s["p50"], "p99": s["p99"], "max_abs": s["max_abs"], "pixels": s["pixels"]})
+                                "over_1": s["over_1"], "p50": s["p50"], "p99": s["p99"], "max_abs": s["max_abs"], "pixels": s["pixels"],
+                                "ssim": q["all"], "below_half": q["below_half"], "worst_ssim": q["worst_value"], "windows": q["windows"]})
 
                 ctx.frame_diff(p, t, r, MASK)
+                ctx.frame_ssim(p, t, rs, MASK)
                 row("repeat prev (no generation)")
                 for name, estimator, radius, interpolator, semantics, *tolerance in ROUTES:
                     ctx.set_static_protection(tolerance[0] if tolerance else -1)
@@ -92,24 +97,26 @@ def main():
                     ctx.set_semantics(semantics)
                     ctx.interpolate_frames(p, c, o, 0.5)
                     ctx.frame_diff(o, t, r, MASK)
+                    ctx.frame_ssim(o, t, rs, MASK)
                     row(name)
-                for f in (p, t, c, o, r):
+                for f in (p, t, c, o, r, rs):
                     ctx.destroy_frame(f)
     write_json(a.json, rows)
     if a.out:
         with open(a.out, "w") as f:
             f.write(f"# lib_sha16 {hashlib.sha256(open(capi.LIB_PATH, 'rb').read()).hexdigest()[:16]}\n")
             f.write(f"# python tools/quality_report.py {' '.join(sys.argv[1:])}: frames 0 and 2 of a synth triple generate frame 1 at 0.5;\n"
-                    "# lfg_interpolate_frames + lfg_frame_diff on one MI355X, PSNR and differing pixels over R, G and B (mask 0x7).\n")
+                    "# lfg_interpolate_frames + lfg_frame_diff + lfg_frame_ssim on one MI355X; PSNR, differing pixels, SSIM and the windows\n"
+                    "# below 0.5 over R, G and B (mask 0x7).\n")
             for row_ in rows:
                 f.write(json.dumps(row_) + "\n")
             for size in a.sizes.split(","):
-                f.write(f"\n## {size}: PSNR dB / differing px of {SIZES[size][0] * SIZES[size][1]:,}\n")
+                f.write(f"\n## {size}: PSNR dB / differing px of {SIZES[size][0] * SIZES[size][1]:,} / SSIM / windows below 0.5\n")
                 names = list(dict.fromkeys(x["content"] for x in rows))
                 f.write("| route | " + " | ".join(names) + " |\n|---|" + "---|" * len(names) + "\n")
                 for route in dict.fromkeys(x["route"] for x in rows):
                     cells = [next(x for x in rows if (x["size"], x["content"], x["route"]) == (size, n, route)) for n in names]
-                    f.write(f"| {route} | " + " | ".join(f"{x['psnr_db']:.2f} / {x['differing']:,}" for x in cells) + " |\n")
+                    f.write(f"| {route} | " + " | ".join(f"{x['psnr_db']:.2f} / {x['differing']:,} / {x['ssim']:.4f} / {x['below_half']:,}" for x in cells) + " |\n")
 
 
 if __name__ == "__main__":
