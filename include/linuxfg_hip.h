@@ -928,6 +928,36 @@ int  lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int fil
  * LFG_ERR_UNSUPPORTED for a refused table (the arrays are then undefined). */
 int  lfg_resample_taps(int filter, uint32_t in_size, uint32_t out_size, int32_t *first, uint32_t *count, int16_t *weights);
 
+/* lfg_resample with the ringing of its upscaling passes limited (anti-ringing, as the scalers of video players have it).  No
+ * reference counterpart.  Lanczos and the cubics with negative lobes overshoot at every hard edge; here the result of a 1-D
+ * pass whose axis grows may not leave the range of the two source samples that bracket the output position, and `strength`
+ * S in 0 .. 64 mixes the clamped result with the plain one in 64ths.  Everything said of lfg_resample holds: frames, checks,
+ * tables, LFG_ERR_INVALID / LFG_ERR_UNSUPPORTED before anything is enqueued, ONE launch on the selected lane, timed under
+ * LFG_STAGE_SCALE, integer arithmetic past the table, no branch on the content.  A strength outside 0 .. 64 is LFG_ERR_INVALID.
+ *   Bracket of output sample p on an axis of `in` -> `out` samples (lfg_resample_brackets): with N = (2p + 1) in - out and
+ *   D = 2 out, a(p) = clamp(floor(N / D), 0, in - 1) and b(p) = clamp(ceil(N / D), 0, in - 1), in integers -- the ceiling and
+ *   not floor + 1: where the output centre is a texel's centre the bracket is that texel.  For every filter of support >= 1
+ *   and out > in, first[p] <= a <= b < first[p] + count[p]: both are taps.
+ *   Where: a pass is anti-ringed if S > 0, the filter is not LFG_FILTER_NEAREST and the pass's axis grows strictly (out > in).
+ *   Any other pass keeps lfg_resample's formula, and where no pass qualifies the call IS lfg_resample: the same kernel, the
+ *   same launch, the same bytes.
+ *   Horizontal pass, with h the exact sum of lfg_resample and per channel c:
+ *     L = 16384 min(in(y, a)_c, in(y, b)_c), U = 16384 max(the same);  d = clamp(h, L, U) - h;  g = h + floor(d S / 64);
+ *     h' = (g + 128) >> 8          in place of (h + 128) >> 8
+ *   Vertical pass, with v the sum over those h':
+ *     L = 16384 min(h'(a, p)_c, h'(b, p)_c), U = 16384 max(the same);  d = clamp(v, L, U) - v, |d| < 2^31;
+ *     u = v + floor(d S / 64)      (exact: (d >> 6) S + (((d & 63) S) >> 6));  out = clamp((u + 2^19) >> 20, 0, 255)
+ *   So S = 64 makes each qualifying pass an exact clamp; with both axes growing every output byte then lies within the four
+ *   texels in({a_y, b_y}, {a_x, b_x}) of its channel; bilinear, whose weights are a convex combination of the bracket, gives
+ *   lfg_resample's bytes at every S; a constant frame stays constant.
+ * The first call for an (in, out) pair of a growing axis builds its brackets with lfg_resample_brackets and uploads them; the
+ * context keeps a bounded number of them, like the tables.  For presented frames: a perceptual control. */
+int  lfg_resample_antiring(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength);
+/* The brackets above -- the one builder: lfg_resample_antiring uploads what this returns.  A pure host function: no context,
+ * no GPU.  lo and hi hold out_size entries each (a and b).  LFG_ERR_INVALID for a NULL pointer, a size of 0 or an in_size of
+ * 2^31 or more. */
+int  lfg_resample_brackets(uint32_t in_size, uint32_t out_size, int32_t *lo, int32_t *hi);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

@@ -205,6 +205,8 @@ SIGNATURES = {
     "lfg_sharpen": (_i, [_vp, _FP, _FP, _i]),
     "lfg_resample": (_i, [_vp, _FP, _FP, _i]),
     "lfg_resample_taps": (_i, [_i, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int16)]),
+    "lfg_resample_antiring": (_i, [_vp, _FP, _FP, _i, _i]),
+    "lfg_resample_brackets": (_i, [_u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
@@ -283,6 +285,21 @@ def resample_taps(filt: int, n_in: int, n_out: int):
         err.code = rc
         raise err
     return first, count, weights
+
+
+def resample_brackets(n_in: int, n_out: int):
+    """(lo[n_out] int32, hi[n_out] int32) of lfg_resample_brackets: the two source samples that bracket each output sample of
+    one axis, which lfg_resample_antiring uploads.  Needs no context and no GPU.  Raises LfgError, with the code as `.code`."""
+    n_in, n_out = int(n_in), int(n_out)
+    rows = n_out if 0 < n_out < 2 ** 32 else 0
+    lo, hi = np.zeros(rows, np.int32), np.zeros(rows, np.int32)
+    rc = load().lfg_resample_brackets(n_in if 0 < n_in < 2 ** 32 else 0, rows, lo.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                      hi.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc != 0:
+        err = LfgError(f"lfg_resample_brackets failed ({rc}): a size of 0, or an input of 2^31 samples or more")
+        err.code = rc
+        raise err
+    return lo, hi
 
 
 def load() -> ctypes.CDLL:
@@ -836,6 +853,13 @@ class Context:
         """lfg_resample: `src` resampled into `dst` (both RGBA8, any sizes, no overlap) under one of FILTER_*, anti-aliased where
         an axis shrinks; one launch, timed under STAGE_SCALE."""
         self._check(self.lib.lfg_resample(self.h, ctypes.byref(src), ctypes.byref(dst), int(filt)), "lfg_resample")
+
+    def resample_antiring(self, src: Frame, dst: Frame, filt: int, strength: int):
+        """lfg_resample_antiring: lfg_resample with each upscaling pass held to the range of the two source samples that bracket
+        the output position, mixed with the plain result by strength 0 .. 64; lfg_resample itself where no axis grows,
+        at strength 0 and under FILTER_NEAREST."""
+        self._check(self.lib.lfg_resample_antiring(self.h, ctypes.byref(src), ctypes.byref(dst), int(filt), int(strength)),
+                    "lfg_resample_antiring")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

@@ -511,6 +511,7 @@ LFG_EXPORT void lfg_context_destroy(lfg_context *ctx) {
     for (auto &t : ctx->tables) { (void)hipFree(t.d_start); (void)hipFree(t.d_weight); (void)hipFree(t.d_class); (void)hipFree(t.d_palette); }
     for (auto &t : ctx->uv_tables) (void)hipFree(t.d_uv);
     for (auto &t : ctx->resample_tables) (void)hipFree(t.d_base);
+    for (auto &t : ctx->resample_brackets) (void)hipFree(t.d_base);
     if (ctx->motion_tables) (void)hipFree(ctx->motion_tables);
     delete ctx;
 }
@@ -2103,6 +2104,18 @@ LFG_EXPORT int lfg_resample_taps(int filter, uint32_t in_size, uint32_t out_size
     return LFG_OK;
 }
 
+LFG_EXPORT int lfg_resample_brackets(uint32_t in_size, uint32_t out_size, int32_t *lo, int32_t *hi) {
+    if (!lo || !hi || in_size == 0 || out_size == 0 || in_size > 0x7fffffffu) return LFG_ERR_INVALID;
+    const __int128 in = in_size, out = out_size, D = 2 * out;
+    const auto clamped = [&](__int128 k) { return k < 0 ? (__int128)0 : k > in - 1 ? in - 1 : k; };
+    for (uint32_t p = 0; p < out_size; ++p) {
+        const __int128 N = (2 * (__int128)p + 1) * in - out;
+        lo[p] = (int32_t)clamped(floor_div(N, D));
+        hi[p] = (int32_t)clamped(-floor_div(-N, D));           // the ceiling: lo where the centre is a texel's
+    }
+    return LFG_OK;
+}
+
 namespace {
 
 // Bounded like the axis tables: called at the top of lfg_resample, before either of its tables is looked up, so that the two
@@ -2113,6 +2126,45 @@ void trim_resample_tables(lfg_context *ctx) {
         (void)hipFree(ctx->resample_tables.front().d_base);
         ctx->resample_tables.erase(ctx->resample_tables.begin());
     }
+    while (ctx->resample_brackets.size() > 14) {
+        (void)sync_lanes(ctx);
+        (void)hipFree(ctx->resample_brackets.front().d_base);
+        ctx->resample_brackets.erase(ctx->resample_brackets.begin());
+    }
+}
+
+// The brackets of one growing axis (out > in), built and uploaded at their first use.  The kernel reads texel a(p) and b(p) of
+// a row, and LDS row a(q) and b(q) of a tile, without a check of its own, on the strength of the lemma
+//   first[p] <= a(p) <= b(p) < first[p] + count[p]   for every filter of support >= 1,
+// which is asserted here on the taps of support 1, |(2k + 1) out - (2p + 1) in| < 2 out folded onto 0 .. in - 1: a wider
+// filter's taps hold those, and folding is monotone.
+int resample_bracket_table(lfg_context *ctx, uint32_t in_size, uint32_t out_size, lfg::ResampleBracket *out) {
+    for (const auto &t : ctx->resample_brackets)
+        if (t.in_size == in_size && t.out_size == out_size) { *out = t.bracket; return LFG_OK; }
+    const size_t n = out_size;
+    std::vector<int32_t> host(2 * n);
+    if (lfg_resample_brackets(in_size, out_size, host.data(), host.data() + n) != LFG_OK)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_resample_antiring: a frame of this size has no brackets");
+    const __int128 in = in_size, o = out_size;
+    for (size_t p = 0; p < n; ++p) {
+        const __int128 centre = (2 * (__int128)p + 1) * in;
+        const __int128 k0 = floor_div(centre - 3 * o, 2 * o) + 1, k1 = floor_div(centre + 3 * o - 1, 2 * o) - 1;
+        const auto clamped = [&](__int128 k) { return k < 0 ? (__int128)0 : k > in - 1 ? in - 1 : k; };
+        const __int128 first = clamped(k0), last = clamped(k1);
+        if (!(first <= host[p] && host[p] <= host[n + p] && host[n + p] <= last))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_resample_antiring: a bracket outside its taps (" + std::to_string(in_size) + " -> " +
+                                                  std::to_string(out_size) + ", sample " + std::to_string(p) + ")");
+    }
+    lfg::ResampleBracketTable t;
+    t.in_size = in_size; t.out_size = out_size;
+    LFG_HIP(ctx, hipMalloc((void **)&t.d_base, 2 * n * sizeof(int32_t)));
+    const hipError_t e = hipMemcpy(t.d_base, host.data(), 2 * n * sizeof(int32_t), hipMemcpyHostToDevice);   // (synchronous, as the axis table's)
+    if (e != hipSuccess) { (void)hipFree(t.d_base); return fail_hip(ctx, e, "hipMemcpy(resample brackets)"); }
+    t.bracket.lo = t.d_base;
+    t.bracket.hi = t.d_base + n;
+    ctx->resample_brackets.push_back(t);
+    *out = t.bracket;
+    return LFG_OK;
 }
 
 // The table of one axis, built and uploaded at its first use.  Returned by value: the pointers in it are the device's.
@@ -2153,26 +2205,45 @@ int resample_table(lfg_context *ctx, int filter, uint32_t in_size, uint32_t out_
     return LFG_OK;
 }
 
-}  // namespace
-
-LFG_EXPORT int lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter) {
+// lfg_resample (strength 0) and lfg_resample_antiring: the checks, the tables and the one launch.  A pass is anti-ringed where
+// the strength is positive, the filter has weights to ring with and the pass's axis grows; where no pass is, this is
+// lfg_resample: the same kernel and the same launch.
+int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength, const char *who) {
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
-        return fail(ctx, LFG_ERR_INVALID, "lfg_resample: in and out must be non-empty RGBA8");
+        return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": in and out must be non-empty RGBA8");
     if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
-        return fail(ctx, LFG_ERR_INVALID, "lfg_resample: RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
-    if (!resample_filter_known(filter)) return fail(ctx, LFG_ERR_INVALID, "lfg_resample: unknown filter");
-    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_resample: the output overlaps the input");
+        return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    if (!resample_filter_known(filter)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": unknown filter");
+    if (strength < 0 || strength > 64) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": strength must be in [0, 64]");
+    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": the output overlaps the input");
     trim_resample_tables(ctx);
     lfg::ResampleTable tx, ty;
     int rc = resample_table(ctx, filter, in->width, out->width, &tx);
     if (rc == LFG_OK) rc = resample_table(ctx, filter, in->height, out->height, &ty);
     if (rc != LFG_OK) return rc;
+    const bool rings = strength > 0 && filter != LFG_FILTER_NEAREST;
+    const int sx = rings && out->width > in->width ? strength : 0, sy = rings && out->height > in->height ? strength : 0;
+    lfg::ResampleBracket bx{}, by{};
+    if (sx) rc = resample_bracket_table(ctx, in->width, out->width, &bx);
+    if (sy && rc == LFG_OK) rc = resample_bracket_table(ctx, in->height, out->height, &by);
+    if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_SCALE);
-    const hipError_t e = lfg::launch_resample(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan);
+    const hipError_t e = sx || sy ? lfg::launch_resample_antiring(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan, bx, by, sx, sy)
+                                  : lfg::launch_resample(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan);
     if (e != hipSuccess) return fail_hip(ctx, e, "resample kernel launch");
     return LFG_OK;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter) {
+    return resample_call(ctx, in, out, filter, 0, "lfg_resample");
+}
+
+LFG_EXPORT int lfg_resample_antiring(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength) {
+    return resample_call(ctx, in, out, filter, strength, "lfg_resample_antiring");
 }
 
 LFG_EXPORT int lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled) {

@@ -153,6 +153,14 @@ struct ResampleTable {
     ResamplePlan plan{};
 };
 
+// The brackets of one growing axis for lfg_resample_antiring, keyed by (in, out) alone: what lfg_resample_brackets returned, on
+// the device in one allocation (lo | hi).
+struct ResampleBracketTable {
+    uint32_t in_size = 0, out_size = 0;
+    int32_t *d_base = nullptr;
+    ResampleBracket bracket{};
+};
+
 struct ProfileSlot {
     hipEvent_t begin = nullptr, end = nullptr;
     int stage = 0;
@@ -223,6 +231,7 @@ struct lfg_context {
     std::vector<lfg::AxisTable> tables;       // small cache, linear search
     std::vector<lfg::UvTable> uv_tables;      // likewise (interpolate)
     std::vector<lfg::ResampleTable> resample_tables;   // likewise (lfg_resample)
+    std::vector<lfg::ResampleBracketTable> resample_brackets;   // likewise (lfg_resample_antiring)
     int motion_slots = 0;                      // prefilter workgroups resident at once on this device (0 = not queried yet)
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only
@@ -403,6 +412,10 @@ hipError_t launch_sharpen(hipStream_t s, const lfg_frame &in, const lfg_frame &o
 // Resampling (resample.hip): one launch, both passes; `plan` is the vertical table's.
 hipError_t launch_resample(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const ResampleAxis &x, const ResampleAxis &y,
                            const ResamplePlan &plan);
+// ... with anti-ringing (resample_antiring.hip): the same launch shape; sx / sy is the strength of the horizontal / vertical pass,
+// 0 where that pass is not anti-ringed (its bracket is then not read), and not both are 0.
+hipError_t launch_resample_antiring(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const ResampleAxis &x, const ResampleAxis &y,
+                                    const ResamplePlan &plan, const ResampleBracket &bx, const ResampleBracket &by, int sx, int sy);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 

@@ -178,4 +178,148 @@ __host__ __device__ inline void resample_phase2(const ResampleArgs &a, uint32_t 
     }
 }
 
+// ---- anti-ringing (lfg_resample_antiring, include/linuxfg_hip.h; resample_antiring.hip; tests/cpp/antiring_on_host.cpp)
+//
+// The same tile plan, LDS layout and thread roles as above; each phase additionally reads the two samples that bracket its
+// output position on its axis -- a(p) <= b(p), both among the output's taps (lfg_resample_brackets) -- and pulls its sum
+// towards their range by strength / 64.  A pass that is not anti-ringed has strength 0 and no bracket table: the mix is then
+// the identity and the bracket is read at the first tap, so neither phase has a branch on the strength or on the content.
+// Everything above stays as it is, loops included: resample_kernel's machine code is what section 4.16 measured.
+
+struct ResampleBracket { const int32_t *lo, *hi; };           // a(p), b(p) of one growing axis on the device
+struct ResampleAntiringArgs {
+    ResampleArgs r;
+    ResampleBracket bx, by;                    // of the width and of the height; not read where the strength is 0
+    int sx, sy;                                // S where the horizontal / the vertical pass is anti-ringed, else 0
+};
+
+// What the sums can be.  A table row has sum q = 16384 and sum |q| <= 32768 (lfg_resample_taps refuses it otherwise), so its
+// positive weights sum to at most 24576 and its negative ones to at least -8192:
+//   h  in [-8192 * 255, 24576 * 255] = [-2,088,960, 6,266,880], and so is h clamped between two texels * 16384: |.| < 2^23;
+//   h' in [-8160, 24480];  v in [-401,080,320, 668,467,200];  16384 h' in [-133,693,440, 401,080,320];
+//   d = clamp(v) - v in [-802,160,640, 802,160,640]: |d| < 2^30.
+
+// x * y for |x|, |y| < 2^23.  Saying that both are sign-extended from 24 bits is what lets the compiler take the full-rate
+// 24-bit multiply (v_mul_i32_i24, v_mad_i32_i24), in which the two shifts disappear; the CPU computes the same number.
+__host__ __device__ inline int resample_mul24(int x, int y) {
+    return ((int)((uint32_t)x << 8) >> 8) * ((int)((uint32_t)y << 8) >> 8);
+}
+
+// The median of v, x and y: v clamped to the range of x and y, whichever of the two is the larger.  min(max(x, y), max(min(x, y), v))
+// is the form the compiler turns into one v_med3_i32.
+__host__ __device__ inline int resample_median(int v, int x, int y) {
+    const int lo = x < y ? x : y, hi = x < y ? y : x, m = lo < v ? v : lo;
+    return hi < m ? hi : m;
+}
+
+// The horizontal pass of one channel between the texels x and y, rounding included: with c = clamp(h, 16384 min, 16384 max),
+// d = c - h and g = h + floor(d s / 64) = floor((64 h + d s) / 64), (g + 128) >> 8 = ((64 - s) h + s c + 8192) >> 14.
+// Both products are 24-bit by the bounds above and their sum is 64 times a value between h and c.
+// (x and y pass through resample_kept_apart so that the compiler forgets they are bytes: knowing it, it orders them with
+// unsigned and h with signed minima and maxima, four instructions where the median is one.)
+__host__ __device__ inline int resample_antiring_h(int h, int x, int y, int s) {
+    const int c = resample_median(h, resample_kept_apart(x * 16384), resample_kept_apart(y * 16384));
+    return (resample_mul24(64 - s, h) + resample_mul24(s, c) + 8192) >> 14;
+}
+
+// The vertical pass of one channel between the h' values x and y: v + floor(d s / 64) with d = clamp(v, 16384 min, 16384 max) - v.
+// d s does not fit 32 bits; d = 256 (d >> 8) + (d & 255) gives floor(d s / 64) = 4 s (d >> 8) + ((d & 255) s >> 6), the same
+// number as the 64-bit product's, from two 24-bit products (|d >> 8| < 2^22).  The result lies between v and the clamped v.
+__host__ __device__ inline int resample_antiring_v(int v, int x, int y, int s) {
+    const int d = resample_median(v, x * 16384, y * 16384) - v;
+    return v + resample_mul24(d >> 8, 4 * s) + (resample_mul24(d & 255, s) >> 6);
+}
+
+// Phase 1 for thread (c, g), as resample_phase1: h' of its column for the source rows of the group's blocks, each sum mixed
+// towards the range of the row's texels a(p) and b(p) before it is rounded.  The two texels are two more dword loads per row
+// from cache lines that the taps bring in anyway (see the header of resample_antiring.hip).
+__host__ __device__ inline void resample_antiring_phase1(const ResampleAntiringArgs &aa, uint32_t tileX, uint32_t tileY, uint32_t c,
+                                                         uint32_t g, ResampleWord *lds) {
+    const ResampleArgs &a = aa.r;
+    const uint32_t p = tileX * kResampleColumns + c;
+    if (p >= a.outW) return;
+    const ResampleTile t = resample_tile(a, tileY);
+    const size_t x0 = (size_t)a.x.first[p] * 4u;
+    const size_t xa = aa.sx ? (size_t)aa.bx.lo[p] * 4u : x0, xb = aa.sx ? (size_t)aa.bx.hi[p] * 4u : x0;
+    const uint32_t n = a.x.count[p];
+    const int16_t *w = a.x.weights + (size_t)p * a.x.stride;
+    for (int32_t r0 = t.rowLo + (int32_t)(g * kResampleBlock); r0 < t.rowHi; r0 += (int32_t)(kResampleGroups * kResampleBlock)) {
+        const uint8_t *row[kResampleBlock];
+        uint32_t ta[kResampleBlock], tb[kResampleBlock];
+        int acc[kResampleBlock][4];
+#pragma unroll
+        for (uint32_t k = 0; k < kResampleBlock; ++k) {
+            const int32_t r = r0 + (int32_t)k < t.rowHi ? r0 + (int32_t)k : t.rowHi - 1;
+            row[k] = a.in + (size_t)r * a.inPitch;
+            ta[k] = *reinterpret_cast<const uint32_t *>(row[k] + xa);
+            tb[k] = *reinterpret_cast<const uint32_t *>(row[k] + xb);
+            row[k] += x0;
+            acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0;
+        }
+        uint32_t j = 0;
+        for (; j + 4u <= n; j += 4u) {
+            const ResampleWeights4 w4 = *reinterpret_cast<const ResampleWeights4 *>(w + j);
+            const int wj[4] = {(int)(int16_t)(w4.w[0] & 0xffffu), (int)w4.w[0] >> 16, (int)(int16_t)(w4.w[1] & 0xffffu), (int)w4.w[1] >> 16};
+#pragma unroll
+            for (uint32_t k = 0; k < kResampleBlock; ++k) {
+                const ResampleTexels4 t4 = *reinterpret_cast<const ResampleTexels4 *>(row[k] + (size_t)j * 4u);
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) resample_accumulate(acc[k], wj[i], t4.t[i]);
+            }
+        }
+        for (; j < n; ++j) {
+            const int wj = w[j];
+#pragma unroll
+            for (uint32_t k = 0; k < kResampleBlock; ++k)
+                resample_accumulate(acc[k], wj, *reinterpret_cast<const uint32_t *>(row[k] + (size_t)j * 4u));
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kResampleBlock; ++k) {
+            if (r0 + (int32_t)k >= t.rowHi) break;
+            int h[4];
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; ++i)
+                h[i] = resample_antiring_h(acc[k][i], (int)((ta[k] >> (8u * i)) & 255u), (int)((tb[k] >> (8u * i)) & 255u), aa.sx);
+            ResampleWord word;
+            word.lo = ((uint32_t)h[0] & 0xffffu) | ((uint32_t)h[1] << 16);
+            word.hi = ((uint32_t)h[2] & 0xffffu) | ((uint32_t)h[3] << 16);
+            lds[(size_t)(r0 + (int32_t)k - t.rowLo) * kResampleColumns + c] = word;
+        }
+    }
+}
+
+// Phase 2 for thread (c, g), as resample_phase2: each sum mixed towards the range of h' in the LDS rows a(q) and b(q) of its
+// column -- two more 8-byte LDS reads per pixel, their rows the same for a whole wave like the taps'.
+__host__ __device__ inline void resample_antiring_phase2(const ResampleAntiringArgs &aa, uint32_t tileX, uint32_t tileY, uint32_t c,
+                                                         uint32_t g, const ResampleWord *lds) {
+    const ResampleArgs &a = aa.r;
+    const uint32_t p = tileX * kResampleColumns + c;
+    if (p >= a.outW) return;
+    const ResampleTile t = resample_tile(a, tileY);
+    for (uint32_t q = t.q0 + g; q < t.q1; q += kResampleGroups) {
+        const uint32_t n = a.y.count[q];
+        const int16_t *w = a.y.weights + (size_t)q * a.y.stride;
+        const int32_t first = a.y.first[q];
+        const ResampleWord *col = lds + (size_t)(first - t.rowLo) * kResampleColumns + c;
+        const ResampleWord ha = lds[(size_t)((aa.sy ? aa.by.lo[q] : first) - t.rowLo) * kResampleColumns + c];
+        const ResampleWord hb = lds[(size_t)((aa.sy ? aa.by.hi[q] : first) - t.rowLo) * kResampleColumns + c];
+        int v[4] = {0, 0, 0, 0};
+        for (uint32_t j = 0; j < n; ++j) {
+            const int wj = w[j];
+            const ResampleWord h = col[(size_t)j * kResampleColumns];
+            v[0] += wj * (int)(int16_t)(h.lo & 0xffffu);
+            v[1] += wj * ((int)h.lo >> 16);
+            v[2] += wj * (int)(int16_t)(h.hi & 0xffffu);
+            v[3] += wj * ((int)h.hi >> 16);
+        }
+        v[0] = resample_antiring_v(v[0], (int)(int16_t)(ha.lo & 0xffffu), (int)(int16_t)(hb.lo & 0xffffu), aa.sy);
+        v[1] = resample_antiring_v(v[1], (int)ha.lo >> 16, (int)hb.lo >> 16, aa.sy);
+        v[2] = resample_antiring_v(v[2], (int)(int16_t)(ha.hi & 0xffffu), (int)(int16_t)(hb.hi & 0xffffu), aa.sy);
+        v[3] = resample_antiring_v(v[3], (int)ha.hi >> 16, (int)hb.hi >> 16, aa.sy);
+        const uint32_t px = (uint32_t)resample_byte(v[0]) | ((uint32_t)resample_byte(v[1]) << 8) | ((uint32_t)resample_byte(v[2]) << 16) |
+                            ((uint32_t)resample_byte(v[3]) << 24);
+        *reinterpret_cast<uint32_t *>(a.out + (size_t)q * a.outPitch + (size_t)p * 4u) = px;
+    }
+}
+
 }  // namespace lfg

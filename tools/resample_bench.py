@@ -33,8 +33,8 @@ FILTERS = (("nearest", capi.FILTER_NEAREST), ("bilinear", capi.FILTER_BILINEAR),
 SCALE_KERNELS = {0: "scale_generic_kernel", 1: "scale_2x_kernel"}
 
 
-def kernel_resources():
-    """"vgprs ..., sgprs ..., lds ..., scratch ..., waves/SIMD ..." of resample_kernel, from the notes of the library's code
+def kernel_resources(kernel="resample_kernel"):
+    """"vgprs ..., sgprs ..., lds ..., scratch ..., waves/SIMD ..." of `kernel`, from the notes of the library's code
     objects (llvm-objdump --offloading unbundles them into the working directory, here a temporary one)."""
     llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
     with tempfile.TemporaryDirectory() as d:
@@ -43,7 +43,7 @@ def kernel_resources():
         for f in sorted(glob.glob(os.path.join(d, "*gfx950*"))):
             notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", f], capture_output=True, text=True).stdout
             for block in notes.split("  - .agpr_count:")[1:]:
-                if not re.search(r"\.name:\s+\S*resample_kernel\S*", block):
+                if not re.search(rf"\.name:\s+\S*{kernel}\S*", block):
                     continue
                 get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", block)[1])  # noqa: E731
                 vgprs = get("vgpr_count")
