@@ -159,6 +159,9 @@ LFG_STAMP(
     // of the unit work on the one segment, and leave together)
     if (segUnit && !fromQueue && __builtin_amdgcn_readfirstlane((int)segDone[tile * (kPTH / kSeg) + (int)((um >> 29) & 3u)]) != 0) return;
     if (tid == 0) sGiveUp = 0u;
+    // (the waves of a unit look at it every 64 entries of a full search; read as LDS: through the generic reference the look
+    //  is a flat load and a wait for the vector-memory counter, behind whatever record stores are still out)
+    auto unitGaveUp = [&]() { return __builtin_amdgcn_readfirstlane((int)*(const volatile __attribute__((address_space(3))) uint32_t *)&sGiveUp) != 0; };
     // (the two flags of this call's order, requested here: read where they are used -- behind the staging barrier -- each
     //  was a scalar load from memory with nothing to hide its latency, two microseconds per unit)
     const uint32_t orderHandOver = order32[kCand], orderHints = order32[kCand + 1];

@@ -107,7 +107,12 @@ LFG_STAMP(
             const lds_ro_f32_ptr nSlabR = (lds_ro_f32_ptr)(sSlab[wave] + (r >> 1) * kNarrowPitch + (r & 1) + 2 * (active ? g : 0));
             const uint32_t nLaneOff = (uint32_t)r * (listK * rowStride) + (uint32_t)(nXb + 4 * g);
             const int segY0 = ty0 + kSeg * seg;
-            auto testCandidate = [&](const float (&X)[4 + kB - 1], uint32_t ord, uint32_t countIt) {
+            // (A candidate no lane records -- nearly every one of the 1,089 -- costs the slab reads, the tree, the compare and
+            //  ONE branch on the ballot itself.  Its entry of the order and all that derives from it are the hit side's business:
+            //  fetched in front of the branch, the entry was an LDS round trip, a readfirstlane and a dozen scalar instructions
+            //  per candidate, and the ballot wrapped in a readfirstlane went through a select, a lane read and a bit test
+            //  before it could branch -- 71 instructions on that path, 46 now: tools/full_search_budget.py.)
+            auto testCandidate = [&](const float (&X)[4 + kB - 1], int idx) {
                 float h2[10], h4[8], sN[4];
 #pragma unroll
                 for (int i = 0; i < 10; ++i) h2[i] = X[i] + X[i + 1];
@@ -118,7 +123,9 @@ LFG_STAMP(
                 float top = thrN[0] - sN[0];
 #pragma unroll
                 for (int j = 1; j < 4; ++j) top = __builtin_fmaxf(top, thrN[j] - sN[j]);
-                if (__builtin_amdgcn_readfirstlane(__ballot(top >= 0.0f) == 0ull)) return;
+                if (__ballot(top >= 0.0f) == 0ull) return;
+                const uint32_t ord = (uint32_t)__builtin_amdgcn_readfirstlane((int)((lds_ro_u32_ptr)sOrder)[entryOf(idx)]);
+                const uint32_t countIt = idx >= nHead ? 1u : 0u;
                 const uint32_t cand = ord & 0xFFFFu;
                 const int candDx = (int)((ord >> 16) / (uint32_t)kWinH) - kR, candDy = (int)((ord >> 16) % (uint32_t)kWinH) - kR;
                 const uint32_t zeroCap = 0x00800000u + cand;
@@ -156,32 +163,39 @@ LFG_STAMP(
             float v8[kSeg];
             bool pending = false;
             int idx0 = iBegin, idxP = 0, started = 0;
+            // (as in the row band: a lane's entry of the order is fetched a pass ahead -- fetched where it is needed, it was an LDS
+            //  round trip of its own in front of the window reads.  The row band's other idiom, the previous pass's first slab
+            //  reads BEFORE the window reads, costs eleven live registers across the 23 window reads here: vgpr_spill_count 6 -> 14.)
+            auto orderAt = [&](int idx) { return ((lds_ro_u32_ptr)sOrder)[entryOf(min(idx + kc, iEnd - 1))]; };
+            auto slabReads = [&](int k, float (&X)[4 + kB - 1]) {
+                const lds_ro_f32_ptr base = nSlabR + 2 * (colsPer / 4) * k;
+#pragma unroll
+                for (int i = 0; i < 4 + kB - 1; ++i) X[i] = base[2 * ((i & 3) * kNarrowQ + (i >> 2))];
+            };
+            uint32_t ordN = orderAt(idx0);
             for (;;) {
                 const bool have = idx0 < iEnd && started < 64;
                 if (!have && !pending) {                               // (the pipeline has drained) every 64 entries: give up?
                     if (idx0 >= iEnd) break;
                     started = 0;
                     const bool over = cntN[0] >= listK || cntN[1] >= listK || cntN[2] >= listK || cntN[3] >= listK;    // (the last slot is a spare)
-                    if (__builtin_amdgcn_readfirstlane(__ballot(over) != 0ull)) sGiveUp = 1u;
-                    if (__builtin_amdgcn_readfirstlane((int)*(volatile uint32_t *)&sGiveUp) != 0) return false;
+                    if (__ballot(over) != 0ull) sGiveUp = 1u;
+                    if (unitGaveUp()) return false;
                     continue;
                 }
                 if (have) {
-                    const uint32_t ordC = ((lds_ro_u32_ptr)sOrder)[entryOf(min(idx0 + kc, iEnd - 1))];
-                    const lds_ro_u32_ptr w = nWin + (ordC >> 16);
+                    const lds_ro_u32_ptr w = nWin + (ordN >> 16);
 #pragma unroll
                     for (int j = 0; j < kSegD; ++j) p[j] = w[j];
+                    ordN = orderAt(idx0 + perPass);
                 }
                 if (pending) {             // the slab holds the previous pass: sixteen rows of perPass candidates' column sums
                     wave_lds_sync();
 #pragma nounroll                   // (one copy of the test, not one per candidate)
-                    for (int k = 0; k < perPass && idxP + k < iEnd; ++k) {
-                        const lds_ro_f32_ptr base = nSlabR + 2 * (colsPer / 4) * k;
+                    for (int k = 0, kEnd = min(perPass, iEnd - idxP); k < kEnd; ++k) {
                         float X[4 + kB - 1];
-#pragma unroll
-                        for (int i = 0; i < 4 + kB - 1; ++i) X[i] = base[2 * ((i & 3) * kNarrowQ + (i >> 2))];
-                        const uint32_t ord = ((lds_ro_u32_ptr)sOrder)[entryOf(idxP + k)];
-                        testCandidate(X, (uint32_t)__builtin_amdgcn_readfirstlane((int)ord), (idxP + k) >= nHead ? 1u : 0u);
+                        slabReads(k, X);
+                        testCandidate(X, idxP + k);
                     }
                     wave_lds_sync();
                 }

@@ -120,14 +120,15 @@ LFG_STAMP(
             //  a bottom-strip unit of the benchmark's pan took 261 us instead of 235: each select waits for a lane mask that went
             //  from the VALU through a scalar AND and back.)
             auto testCandidate = [&](const float (&s)[kRun], uint32_t ord, uint32_t countIt) {
+                unsigned long long hit[kRun], any = 0ull;
+#pragma unroll
+                for (int i = 0; i < kRun; ++i) { hit[i] = __ballot(s[i] <= thrB[i]); any |= hit[i]; }
+                if (any == 0ull) return;                               // (the pass's other candidate: nothing of the entry is needed)
                 const uint32_t cand = ord & 0xFFFFu;
                 const int candDx = (int)((ord >> 16) / (uint32_t)kWinH) - kR, candDy = (int)((ord >> 16) % (uint32_t)kWinH) - kR;
                 const uint32_t zeroCap = 0x00800000u + cand;
                 const bool candMayLeave = windowLeavesPrev &&
                     block_leaves_prev_any(tx0, min(tx0 + kPTW - 1, W - 1), segY0 + rB, min(segY0 + rB + 7, H - 1), candDx, candDy, W, H);
-                unsigned long long hit[kRun];
-#pragma unroll
-                for (int i = 0; i < kRun; ++i) hit[i] = __ballot(s[i] <= thrB[i]);
 #pragma unroll
                 for (int i = 0; i < kRun; ++i) {
                     if (hit[i] != 0ull) {                              // wave-uniform
@@ -170,8 +171,8 @@ LFG_STAMP(
                     bool over = false;
 #pragma unroll
                     for (int i = 0; i < kRun; ++i) over = over || cntB[i] >= listK;     // (the last slot is a spare)
-                    if (__builtin_amdgcn_readfirstlane(__ballot(over) != 0ull)) sGiveUp = 1u;
-                    if (__builtin_amdgcn_readfirstlane((int)*(volatile uint32_t *)&sGiveUp) != 0) return false;
+                    if (__ballot(over) != 0ull) sGiveUp = 1u;
+                    if (unitGaveUp()) return false;
                     continue;
                 }
                 f32x2 X[kRunIn];
@@ -198,7 +199,7 @@ LFG_STAMP(
                         const f32x2 dm = f32x2{thrB[i], thrB[i]} - s2[i];
                         top = __builtin_fmaxf(top, __builtin_fmaxf(dm.x, dm.y));
                     }
-                    if (!__builtin_amdgcn_readfirstlane(__ballot(top >= 0.0f) == 0ull)) {
+                    if (__ballot(top >= 0.0f) != 0ull) {       // (the ballot itself: wrapped in a readfirstlane it went through a select, a lane read and a bit test)
 #pragma nounroll                   // (one copy of the test, not one per candidate)
                         for (int k = 0; k < 2 && idxP + k < iEnd; ++k) {
                             float s[kRun];
