@@ -695,6 +695,62 @@ int  lfg_interpolate_compensated_subpel_multi(lfg_context *ctx, const lfg_frame 
  * Any other radius: LFG_ERR_INVALID and no change.  Measured cost and quality: DESIGN.md section 4.20. */
 int  lfg_set_subpixel_vectors(lfg_context *ctx, int radius);
 
+/* Bicubic sampling in the compensated routes, opt-in.  No reference counterpart.  lfg_interpolate_compensated and
+ * lfg_interpolate_compensated_subpel fetch prev and curr with the 2 x 2 bilinear rule, a low-pass: a generated frame at a half-
+ * or quarter-pixel position is softer than the real frames on either side of it.  LFG_SAMPLING_BICUBIC replaces that fetch, and
+ * nothing else, with a 4 x 4 Catmull-Rom fetch defined in integers.
+ *
+ * The table Wt[phi][k], phi = 0 .. 63, k = 0 .. 3: Catmull-Rom at f = phi / 64 in 14-bit fixed point, from exact integers.
+ *   n0 = -4096 phi + 128 phi^2 - phi^3,  n1 = 524288 - 320 phi^2 + 3 phi^3,  n2 = 4096 phi + 256 phi^2 - 3 phi^3,
+ *   n3 = -64 phi^2 + phi^3 (they sum to 524288 = 2 * 64^3);  Wt[phi][k] = (n_k + 16) >> 5 (arithmetic shift: the floor);  then one
+ *   tap -- k = 1 for phi <= 32, k = 2 for phi > 32 -- is replaced by 16384 minus the other three, so every row sums to 16384.
+ *   Wt[0] = (0, 16384, 0, 0), Wt[16] = (-1152, 14208, 3712, -384), Wt[32] = (-1024, 9216, 9216, -1024), Wt[63] = (-2, 136, 16374,
+ *   -124); Wt[64 - phi] is Wt[phi] reversed; sum of |Wt[phi][k]| <= 20480; the smallest weight is -1213.
+ *   lfg_sampling_weights writes the table, row-major 64 x 4; pure host code, no context.  NULL: LFG_ERR_INVALID.
+ * The fetch of image img at position (px, py) in pixels, for the same P and C as the bilinear routes:
+ *   u = px - 0.5f, fu = floorf(u), a = u - fu, and v, fv, b likewise (the bilinear fetch's own arithmetic);
+ *   i = (int)fu, phix = (int)(a * 64.0f); j, phiy likewise.  (a rounds to 1.0f for a tiny negative u; the rule above at phi = 64
+ *   gives (0, 0, 16384, 0), the texel at i + 1, and that row is used.)
+ *   texel(r, k) = img(clamp(i - 1 + k, 0, W - 1), clamp(j - 1 + r, 0, H - 1)), r, k = 0 .. 3;  per channel c
+ *       h_r = (sum over k of Wt[phix][k] * texel(r, k)_c + 64) >> 7          (arithmetic shift; |h_r| <= 40,800)
+ *       s   = sum over r of Wt[phiy][r] * h_r                                 (|s| <= 835,584,000 < 2^31)
+ *       p   = clamp((s + 4096) >> 13, 0, 65280)
+ *   and the sample value is ((float)p / 255.0f) * 0.00390625f, the division correctly rounded.
+ *   `inside` is the bilinear fetch's test, 0 <= px <= W and 0 <= py <= H; the inside rule, the blend mix(Pv, Cv, t), the clamp
+ *   and the store follow unchanged, as do the gate, the projection, the key order and the hole rules before the fetch.
+ * Hence: (1) where phix = phiy = 0, p = 256 texel and the value is the texel's UNORM value bit for bit, so whenever every fetched
+ * position has integer u and v -- t = 0 and t = 1 with any vectors (t = 1 gives curr exactly), a uniform even vector at t = 0.5,
+ * mvq = 4 mv under those conditions -- the output is the bilinear route's byte for byte;  (2) a constant frame stays constant at
+ * every phase;  (3) a vertical step 40 | 200 fetched half a pixel off gives p / 256 = 30, 120, 210 across the edge: the overshoot
+ * is the filter's and is kept, and at 0 | 255 the clamp of p engages on both sides.
+ *
+ * lfg_interpolate_compensated_sampled[_multi]: mv's format picks the route -- LFG_FORMAT_MV_S8X2 gives
+ * lfg_interpolate_compensated[_multi]'s definition, LFG_FORMAT_MV_S16X2_Q2 lfg_interpolate_compensated_subpel[_multi]'s -- and
+ * `sampling` the fetch.  With LFG_SAMPLING_BILINEAR the call is that existing call: same launches, same bytes.  With
+ * LFG_SAMPLING_BICUBIC the route's clear and projection are followed by a sampling kernel with the fetch above; holes take the
+ * 16 px walk whatever lfg_set_hole_reach says (no fill-plane variant is built).  Frames, checks, the lane's key image and the
+ * stage timer are the existing call's; an unknown `sampling` is LFG_ERR_INVALID before anything is enqueued.
+ * Not built, on purpose: masked, bidirectional, extrapolating and fill-plane variants; the shader interpolator; the gate's and
+ * lfg_motion_subpel's prevq, which stay bilinear; anti-ringing of the fetch. */
+typedef enum lfg_sampling { LFG_SAMPLING_BILINEAR = 0, LFG_SAMPLING_BICUBIC = 1 } lfg_sampling;
+int  lfg_sampling_weights(int16_t weights[256]);
+int  lfg_interpolate_compensated_sampled(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                         lfg_frame *out, float factor, int match_sad, int sampling);
+int  lfg_interpolate_compensated_sampled_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                               lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad,
+                                               int sampling);
+/* The fetch of lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else):
+ *   LFG_SAMPLING_BILINEAR (default): every path enqueues and allocates what it did;
+ *   LFG_SAMPLING_BICUBIC: exactly where those calls would run lfg_interpolate_compensated[_multi] with the 16 px walk, or, under
+ *       lfg_set_subpixel_vectors, lfg_interpolate_compensated_subpel[_multi], the _sampled call with LFG_SAMPLING_BICUBIC runs in
+ *       its place.
+ * Under the shader interpolator, LFG_GENERATION_EXTRAPOLATE, lfg_set_static_protection, lfg_set_bidirectional or any
+ * lfg_set_hole_reach the setting is stored and has no effect; lfg_sampling_effective then returns LFG_SAMPLING_BILINEAR -- it
+ * returns what the next lfg_interpolate_frames call would fetch with (NULL: LFG_SAMPLING_BILINEAR) -- so a host can see that the
+ * setting lapsed.  Any other value: LFG_ERR_INVALID and no change.  Measured cost and quality: DESIGN.md section 4.23. */
+int  lfg_set_sampling(lfg_context *ctx, int sampling);
+int  lfg_sampling_effective(const lfg_context *ctx);
+
 /* Pair statistics: how well a vector field explains a pair of frames.  No reference counterpart.  A pair whose two frames do
  * not show the same scene (a cut, a cold start, a channel change) has no vectors that mean anything, and hardly any pixel
  * passes the compensated interpolator's match gate; moving content of every kind passes it almost everywhere (DESIGN.md

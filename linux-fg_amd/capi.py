@@ -24,6 +24,7 @@ SEMANTICS_REFERENCE, SEMANTICS_INTENDED = 0, 1
 ESTIMATOR_FULL_SEARCH, ESTIMATOR_PYRAMID = 0, 1
 INTERPOLATOR_SHADER, INTERPOLATOR_COMPENSATED = 0, 1
 GENERATION_INTERPOLATE, GENERATION_EXTRAPOLATE = 0, 1
+SAMPLING_BILINEAR, SAMPLING_BICUBIC = 0, 1
 DEFAULT_MATCH_SAD = 48
 HOLE_REACH_MAX = 255
 YUV_BT601, YUV_BT709 = 0, 1
@@ -192,6 +193,11 @@ SIGNATURES = {
     "lfg_interpolate_compensated_subpel": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i]),
     "lfg_interpolate_compensated_subpel_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i]),
     "lfg_set_subpixel_vectors": (_i, [_vp, _i]),
+    "lfg_sampling_weights": (_i, [ctypes.POINTER(ctypes.c_int16)]),
+    "lfg_interpolate_compensated_sampled": (_i, [_vp, _FP, _FP, _FP, _FP, ctypes.c_float, _i, _i]),
+    "lfg_interpolate_compensated_sampled_multi": (_i, [_vp, _FP, _FP, _FP, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32, _i, _i]),
+    "lfg_set_sampling": (_i, [_vp, _i]),
+    "lfg_sampling_effective": (_i, [_vp]),
     "lfg_pair_match": (_i, [_vp, _FP, _FP, _FP, _i, _vp]),
     "lfg_cut_fallback": (_i, [_vp, _FP, _FP, _vp, _i, ctypes.POINTER(_FP), ctypes.POINTER(ctypes.c_float), _u32]),
     "lfg_set_cut_detection": (_i, [_vp, _i]),
@@ -300,6 +306,15 @@ def resample_brackets(n_in: int, n_out: int):
         err.code = rc
         raise err
     return lo, hi
+
+
+def sampling_weights() -> np.ndarray:
+    """(64, 4) int16 of lfg_sampling_weights: the bicubic fetch's weights per phase.  Needs no context and no GPU."""
+    w = np.zeros((64, 4), np.int16)
+    rc = load().lfg_sampling_weights(w.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
+    if rc != 0:
+        raise LfgError(f"lfg_sampling_weights failed ({rc})")
+    return w
 
 
 def load() -> ctypes.CDLL:
@@ -739,6 +754,31 @@ class Context:
         """lfg_set_subpixel_vectors: -1 (default) off; 0 .. 2, where interpolate_frames[_multi] would run the plain compensated
         call with the walk they run motion_subpel with that radius and interpolate_compensated_subpel[_multi] in its place."""
         self._check(self.lib.lfg_set_subpixel_vectors(self.h, int(radius)), "lfg_set_subpixel_vectors")
+
+    def interpolate_compensated_sampled(self, prev: Frame, curr: Frame, mv: Frame, out: Frame, factor: float = 0.5,
+                                        match_sad: int = DEFAULT_MATCH_SAD, sampling: int = SAMPLING_BICUBIC):
+        """lfg_interpolate_compensated_sampled: interpolate_compensated (mv FORMAT_MV_S8X2) or interpolate_compensated_subpel (mv
+        FORMAT_MV_S16X2_Q2) with the fetch `sampling`: SAMPLING_BILINEAR is that call itself, SAMPLING_BICUBIC the 4 x 4 fetch."""
+        self._check(self.lib.lfg_interpolate_compensated_sampled(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                                 ctypes.byref(out), factor, int(match_sad), int(sampling)),
+                    "lfg_interpolate_compensated_sampled")
+
+    def interpolate_compensated_sampled_multi(self, prev: Frame, curr: Frame, mv: Frame, outs, factors, match_sad: int = DEFAULT_MATCH_SAD,
+                                              sampling: int = SAMPLING_BICUBIC):
+        """lfg_interpolate_compensated_sampled_multi: one generated frame per factor, each equal to the single call."""
+        po, pf, n = self._multi_args(outs, factors)
+        self._check(self.lib.lfg_interpolate_compensated_sampled_multi(self.h, ctypes.byref(prev), ctypes.byref(curr), ctypes.byref(mv),
+                                                                       po, pf, n, int(match_sad), int(sampling)),
+                    "lfg_interpolate_compensated_sampled_multi")
+
+    def set_sampling(self, sampling: int):
+        """lfg_set_sampling: SAMPLING_BILINEAR (default) or SAMPLING_BICUBIC, where interpolate_frames[_multi] would run the plain
+        compensated call with the walk or the sub-pixel one; under every other setting it is stored and has no effect."""
+        self._check(self.lib.lfg_set_sampling(self.h, int(sampling)), "lfg_set_sampling")
+
+    def sampling_effective(self) -> int:
+        """lfg_sampling_effective: what the next interpolate_frames[_multi] call would fetch with."""
+        return int(self.lib.lfg_sampling_effective(self.h))
 
     def set_half_resolution_motion(self, radius: int):
         """-1 (default: off) or 0..2: interpolate_frames[_multi] run the selected estimator on both frames halved and

@@ -192,14 +192,23 @@ hipError_t launch_interpolate_compensated_masked(hipStream_t s, const lfg_frame 
     return e;
 }
 
-hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
-                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys, uint32_t *fill, int reach) {
+// The first half of launch_interpolate_compensated on its own, for a sampling kernel of another file (interpolate_bicubic.hip).
+hipError_t launch_compensated_projection(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv, float factor,
+                                         int matchSad, uint32_t *keys) {
     const int W = (int)curr.width, H = (int)curr.height;
     dim3 grid;
     hipError_t e = mc_clear_keys(s, keys, W, H, grid);
     if (e == hipSuccess)
         e = mc_launch(mc_project_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
                       (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch, W, H, factor, matchSad, keys);
+    return e;
+}
+
+hipError_t launch_interpolate_compensated(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                          const lfg_frame &out, float factor, int matchSad, uint32_t *keys, uint32_t *fill, int reach) {
+    const int W = (int)curr.width, H = (int)curr.height;
+    const dim3 grid = mc_grid(W, H);
+    hipError_t e = launch_compensated_projection(s, prev, curr, mv, factor, matchSad, keys);
     if (e == hipSuccess && fill) {
         e = launch_hole_fill_plane(s, keys, (size_t)W, fill, (size_t)W, W, H, reach, false);
         if (e == hipSuccess)

@@ -66,15 +66,23 @@ __global__ __launch_bounds__(kMcBlockX * kMcBlockY) void mcq_sample_kernel(
 
 }  // namespace
 
+// Clear K, project: on its own for a sampling kernel of another file (interpolate_bicubic.hip).
+hipError_t launch_compensated_projection_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvq,
+                                                float factor, int matchSad, unsigned long long *keys) {
+    const int W = (int)curr.width, H = (int)curr.height;
+    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 8u, s);
+    if (e == hipSuccess)
+        e = mc_launch(mcq_project_kernel, mc_grid(W, H), s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
+                      (size_t)curr.pitch, (const uint8_t *)mvq.data, (size_t)mvq.pitch, W, H, factor, matchSad, keys);
+    return e;
+}
+
 // Clear K, project, sample.
 hipError_t launch_interpolate_compensated_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvq,
                                                  const lfg_frame &out, float factor, int matchSad, unsigned long long *keys) {
     const int W = (int)curr.width, H = (int)curr.height;
     const dim3 grid = mc_grid(W, H);
-    hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)W * (size_t)H * 8u, s);
-    if (e == hipSuccess)
-        e = mc_launch(mcq_project_kernel, grid, s, (const uint8_t *)prev.data, (size_t)prev.pitch, (const uint8_t *)curr.data,
-                      (size_t)curr.pitch, (const uint8_t *)mvq.data, (size_t)mvq.pitch, W, H, factor, matchSad, keys);
+    hipError_t e = launch_compensated_projection_subpel(s, prev, curr, mvq, factor, matchSad, keys);
     if (e == hipSuccess)
         e = mc_launch(mcq_sample_kernel, grid, s, (const uint8_t *)prev.data, (int)prev.pitch, (const uint8_t *)curr.data,
                       (int)curr.pitch, (const uint8_t *)mvq.data, (size_t)mvq.pitch, (const unsigned long long *)keys, W, H, factor,

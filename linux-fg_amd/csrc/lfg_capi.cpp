@@ -8,6 +8,7 @@
 #include <cstring>
 #include <new>
 
+#include "lfg_bicubic.hpp"
 #include "lfg_internal.hpp"
 
 #define LFG_EXPORT extern "C" __attribute__((visibility("default")))
@@ -1336,7 +1337,7 @@ enum class McKind { Plain, Masked, Extrapolate, Bidirectional, Subpel };
 
 int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, const lfg_mask *mask, McKind kind,
                     lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad, const char *name,
-                    const lfg_frame *bwd = nullptr, int tolerance = 0) {
+                    const lfg_frame *bwd = nullptr, int tolerance = 0, int sampling = LFG_SAMPLING_BILINEAR) {
     const bool masked = kind == McKind::Masked, bidir = kind == McKind::Bidirectional, subpel = kind == McKind::Subpel;
     const uint32_t mvFormat = subpel ? LFG_FORMAT_MV_S16X2_Q2 : LFG_FORMAT_MV_S8X2, mvAlign = subpel ? 4u : 2u;
     if (!ctx) return LFG_ERR_INVALID;
@@ -1377,7 +1378,9 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     if (rc != LFG_OK) return rc;
     // lfg_set_hole_reach: the three interpolating kinds of whole-pixel vectors fill their holes from the lane's fill plane, made
     // per factor behind K
-    const int reach = kind == McKind::Extrapolate || subpel ? -1 : ctx->hole_reach;
+    // LFG_SAMPLING_BICUBIC (the plain and sub-pixel kinds alone): the walk, as no fill-plane variant of that sampling kernel is built
+    const bool bicubic = sampling == LFG_SAMPLING_BICUBIC && (kind == McKind::Plain || subpel);
+    const int reach = kind == McKind::Extrapolate || subpel || bicubic ? -1 : ctx->hole_reach;
     if (reach >= 1) {
         rc = lane_buffer_grow(ctx, cur.mc_fill, cur.mc_fill_bytes, bytes, "hipMalloc((void **)&cur.mc_fill, bytes)");
         if (rc != LFG_OK) return rc;
@@ -1385,7 +1388,9 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     uint32_t *const fill = reach >= 1 ? cur.mc_fill : nullptr;
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
     for (uint32_t i = 0; i < count; ++i) {                       // one key image (and one fill plane), reused in stream order
-        hipError_t e = subpel ? lfg::launch_interpolate_compensated_subpel(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mcq_keys)
+        hipError_t e = bicubic ? (subpel ? lfg::launch_interpolate_compensated_subpel_bicubic(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mcq_keys)
+                                         : lfg::launch_interpolate_compensated_bicubic(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys))
+                       : subpel ? lfg::launch_interpolate_compensated_subpel(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mcq_keys)
                        : masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys,
                                                                            fill, reach)
                        : kind == McKind::Extrapolate
@@ -1399,11 +1404,14 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     return LFG_OK;
 }
 
-// lfg_set_subpixel_vectors' conditions: exactly where compensated_frames would run the plain kind with the walk.
-bool subpixel_applies(const lfg_context *ctx) {
-    return ctx->subpel_radius >= 0 && ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED && ctx->generation == LFG_GENERATION_INTERPOLATE &&
+// Exactly where compensated_frames would run the plain kind with the walk: lfg_set_subpixel_vectors' conditions, and
+// lfg_set_sampling's, which holds for the sub-pixel kind that then runs in its place too.
+bool plain_walk_applies(const lfg_context *ctx) {
+    return ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED && ctx->generation == LFG_GENERATION_INTERPOLATE &&
            ctx->bidir_tolerance < 0 && ctx->static_tolerance < 0 && ctx->hole_reach < 0;
 }
+bool subpixel_applies(const lfg_context *ctx) { return ctx->subpel_radius >= 0 && plain_walk_applies(ctx); }
+int sampling_effective(const lfg_context *ctx) { return plain_walk_applies(ctx) ? ctx->sampling : (int)LFG_SAMPLING_BILINEAR; }
 
 // The compensated interpolation of lfg_interpolate_frames[_multi]: as it is, or with lfg_set_static_protection on the pair's
 // static mask into the lane's temporary and the masked call in its place; under LFG_GENERATION_EXTRAPOLATE the extrapolation
@@ -1430,11 +1438,13 @@ int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
         rc = lfg_motion_subpel(ctx, prev, curr, vectors, &cur.mvq_tmp, ctx->subpel_radius);
         if (rc != LFG_OK) return rc;
         return compensated_run(ctx, prev, curr, &cur.mvq_tmp, nullptr, McKind::Subpel, outs, factors, count, ctx->match_sad,
-                               multi ? "lfg_interpolate_compensated_subpel_multi" : "lfg_interpolate_compensated_subpel");
+                               multi ? "lfg_interpolate_compensated_subpel_multi" : "lfg_interpolate_compensated_subpel", nullptr, 0,
+                               sampling_effective(ctx));
     }
-    if (ctx->static_tolerance < 0)
+    if (ctx->static_tolerance < 0)                                 // (with a hole reach the effective sampling is bilinear)
         return compensated_run(ctx, prev, curr, vectors, nullptr, McKind::Plain, outs, factors, count, ctx->match_sad,
-                               multi ? "lfg_interpolate_compensated_multi" : "lfg_interpolate_compensated");
+                               multi ? "lfg_interpolate_compensated_multi" : "lfg_interpolate_compensated", nullptr, 0,
+                               sampling_effective(ctx));
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     lfg_lane_state &cur = ctx->cur();
     const size_t bytes = (size_t)curr->width * curr->height;
@@ -1721,6 +1731,55 @@ LFG_EXPORT int lfg_set_subpixel_vectors(lfg_context *ctx, int radius) {
     if (radius < -1 || radius > 2) return fail(ctx, LFG_ERR_INVALID, "lfg_set_subpixel_vectors: radius must be -1 (off) or in [0, 2]");
     ctx->subpel_radius = radius;
     return LFG_OK;
+}
+
+// ---- the bicubic fetch (interpolate_bicubic.hip, lfg_bicubic.hpp)
+
+LFG_EXPORT int lfg_sampling_weights(int16_t weights[256]) {
+    if (!weights) return LFG_ERR_INVALID;
+    for (int phi = 0; phi < lfg::kBicubicPhases; ++phi) {
+        const lfg::BicubicRow row = lfg::bicubic_row(phi);
+        for (int k = 0; k < 4; ++k) weights[4 * phi + k] = (int16_t)row.w[k];
+    }
+    return LFG_OK;
+}
+
+namespace {
+
+// mv's format picks the route; everything else is that kind's, through compensated_run.
+int compensated_sampled(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv, lfg_frame *const *outs,
+                        const float *factors, uint32_t count, int match_sad, int sampling, const char *name) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (sampling != LFG_SAMPLING_BILINEAR && sampling != LFG_SAMPLING_BICUBIC)
+        return fail(ctx, LFG_ERR_INVALID, std::string(name) + ": sampling must be LFG_SAMPLING_BILINEAR or LFG_SAMPLING_BICUBIC");
+    const McKind kind = mv && mv->format == LFG_FORMAT_MV_S16X2_Q2 ? McKind::Subpel : McKind::Plain;
+    return compensated_run(ctx, prev, curr, mv, nullptr, kind, outs, factors, count, match_sad, name, nullptr, 0, sampling);
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_interpolate_compensated_sampled(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                                   lfg_frame *out, float factor, int match_sad, int sampling) {
+    lfg_frame *const outs[1] = {out};
+    return compensated_sampled(ctx, prev, curr, mv, outs, &factor, 1, match_sad, sampling, "lfg_interpolate_compensated_sampled");
+}
+
+LFG_EXPORT int lfg_interpolate_compensated_sampled_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
+                                                         lfg_frame *const *outs, const float *factors, uint32_t count, int match_sad,
+                                                         int sampling) {
+    return compensated_sampled(ctx, prev, curr, mv, outs, factors, count, match_sad, sampling, "lfg_interpolate_compensated_sampled_multi");
+}
+
+LFG_EXPORT int lfg_set_sampling(lfg_context *ctx, int sampling) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (sampling != LFG_SAMPLING_BILINEAR && sampling != LFG_SAMPLING_BICUBIC)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_sampling: sampling must be LFG_SAMPLING_BILINEAR or LFG_SAMPLING_BICUBIC");
+    ctx->sampling = sampling;
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_sampling_effective(const lfg_context *ctx) {
+    return ctx ? sampling_effective(ctx) : (int)LFG_SAMPLING_BILINEAR;
 }
 
 // ---- scene-cut detection (pair_stats.hip)

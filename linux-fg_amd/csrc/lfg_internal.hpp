@@ -247,6 +247,7 @@ struct lfg_context {
     int hole_reach = -1;                       // the compensated, masked and bidirectional calls: the fill plane's reach, -1 = off: the walk (lfg_set_hole_reach)
     int half_res_radius = -1;                  // lfg_interpolate_frames[_multi]: lfg_motion_expand's radius, -1 = off (lfg_set_half_resolution_motion)
     int subpel_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_subpel's radius, -1 = off (lfg_set_subpixel_vectors)
+    int sampling = 0;                          // lfg_interpolate_frames[_multi]: LFG_SAMPLING_BILINEAR / _BICUBIC where the plain or sub-pixel kind runs (lfg_set_sampling)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
     bool fuse_motion_interpolate = false;      // lfg_interpolate_frames: the motion kernels write the generated frame themselves
@@ -385,6 +386,17 @@ hipError_t launch_motion_subpel(hipStream_t s, const lfg_frame &prev, const lfg_
                                 const lfg_frame &mvqOut, int radius);
 hipError_t launch_interpolate_compensated_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvq,
                                                  const lfg_frame &out, float factor, int matchSad, unsigned long long *keys);
+// The bicubic fetch (interpolate_bicubic.hip; lfg_interpolate_compensated_sampled): the two routes' clear and projection on their
+// own (interpolate_mc.hip, interpolate_subpel.hip), and the launchers that follow them with the bicubic sampling kernel.
+hipError_t launch_compensated_projection(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv, float factor,
+                                         int matchSad, uint32_t *keys);
+hipError_t launch_compensated_projection_subpel(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mvq,
+                                                float factor, int matchSad, unsigned long long *keys);
+hipError_t launch_interpolate_compensated_bicubic(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv,
+                                                  const lfg_frame &out, float factor, int matchSad, uint32_t *keys);
+hipError_t launch_interpolate_compensated_subpel_bicubic(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr,
+                                                         const lfg_frame &mvq, const lfg_frame &out, float factor, int matchSad,
+                                                         unsigned long long *keys);
 // Scene-cut detection (pair_stats.hip): launch_pair_match clears the 24-byte record `stats` and enqueues the fixed grid that
 // fills it; launch_cut_fallback enqueues the kernel that reads it and, on a cut, copies prev or curr over every output.
 hipError_t launch_pair_match(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv, int matchSad,

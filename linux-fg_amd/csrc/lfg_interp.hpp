@@ -3,6 +3,7 @@
 // the same bytes.  Operation order as fixed in SURVEY.md section 8(c); the library is built with -ffp-contract=off.
 #pragma once
 
+#include "lfg_bicubic.hpp"
 #include "lfg_device.hpp"
 
 namespace lfg {
@@ -142,6 +143,57 @@ __device__ __forceinline__ V4 blend_taps(const SampleTaps &s, const SampleTexels
     r.z = ((s.w00 * t00.z + s.w10 * t10.z) + s.w01 * t01.z) + s.w11 * t11.z;
     r.w = ((s.w00 * t00.w + s.w10 * t10.w) + s.w01 * t01.w) + s.w11 * t11.w;
     return r;
+}
+
+// ---- the bicubic fetch of lfg_interpolate_compensated_sampled, in the same two steps (interpolate_bicubic.hip): pixel_taps' own
+// position arithmetic, then 4 x 4 texels around it at clamped addresses and the two phases; the weights and the integer body are
+// lfg_bicubic.hpp's.  bicubic_load reads only what the caller's two wave-uniform flags ask for -- an axis whose phase is zero on
+// every lane of the wave needs its own row or column alone, the weights of the others being zero -- and leaves the rest zero:
+// the sum is the same integer either way.
+struct BicubicTaps {
+    const uint8_t *row[4];       // the four texel rows (clamped), at column 0
+    int col[4];                  // the four texel columns (clamped)
+    int phiX, phiY;
+    bool inside;                 // pixel_taps' test
+};
+
+__device__ __forceinline__ BicubicTaps bicubic_taps(const uint8_t *__restrict__ img, int W, int H, int pitch, float px, float py) {
+    BicubicTaps s;
+    s.inside = px >= 0.0f && px <= (float)W && py >= 0.0f && py <= (float)H;
+    const float u = px - 0.5f, v = py - 0.5f;
+    const float fu = __builtin_floorf(u), fv = __builtin_floorf(v);
+    const float a = u - fu, b = v - fv;
+    const int i0 = (int)fu, j0 = (int)fv;
+    s.phiX = bicubic_phase(a); s.phiY = bicubic_phase(b);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        s.col[k] = clampi(i0 - 1 + k, 0, W - 1);
+        s.row[k] = img + (size_t)clampi(j0 - 1 + k, 0, H - 1) * (size_t)pitch;
+    }
+    return s;
+}
+
+struct BicubicTexels { uint32_t t[16]; };
+
+__device__ __forceinline__ BicubicTexels bicubic_load(const BicubicTaps &s, bool allRows, bool allCols) {
+    BicubicTexels t;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t.t[i] = 0u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r != 1 && !allRows) continue;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k != 1 && !allCols) continue;
+            t.t[4 * r + k] = *reinterpret_cast<const uint32_t *>(s.row[r] + (size_t)s.col[k] * 4u);
+        }
+    }
+    return t;
+}
+
+__device__ __forceinline__ V4 bicubic_value(const BicubicTaps &s, const BicubicTexels &t) {
+    const BicubicP p = bicubic_p(t.t, s.phiX, s.phiY);
+    return V4{bicubic_p_to_float(p.p[0]), bicubic_p_to_float(p.p[1]), bicubic_p_to_float(p.p[2]), bicubic_p_to_float(p.p[3])};
 }
 
 // One interpolated pixel as packed RGBA8: mix(S(prev, uv - mv t), S(curr, uv + mv (1 - t)), t), clamped, x 255,

@@ -2,7 +2,7 @@
 // and static words, the packed-texel read, the vector read, the match gate, the start of every launcher and its launches
 // (mc_clear_keys, mc_grid, mc_block, mc_launch), and the two halves that the three sampling kernels which blend both frames
 // have in common (mc_interpolate_kernel, mc_interpolate_masked_kernel, bidir_sample_kernel): the hole walk, mc_fill_vector,
-// and the end of a pixel, mc_store_inside_or_blend.  Both carry the names of their CPU restatements in
+// and the end of a pixel, mc_store_inside_or_blend (mc_store_inside_or_blend_values: the same end for interpolate_bicubic.hip's fetch).  Both carry the names of their CPU restatements in
 // tests/compensated_model.h.  mc_fill_from_plane is what stands in the walk's place under lfg_set_hole_reach (hole_fill.hip
 // makes the plane, tests/fill_model.c restates it), and kFillBand is that file's band height.  The vector word, the longest-first key that K holds (mv_longest_first_key), its decode
 // (mv_order_decode) and the hole walks' way back to the order key (mv_key_flip_length) are lfg_vector_word.hpp's; the taps
@@ -78,6 +78,15 @@ __device__ __forceinline__ void mc_store_inside_or_blend(const SampleTaps &sp, c
                                                          size_t outPitch, int x, int y) {
     if (only == 0) only = sp.inside && !sc.inside ? 1 : (sc.inside && !sp.inside ? 2 : 0);
     const V4 P = blend_taps(sp, tp), C = blend_taps(sc, tc);
+    const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
+    *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
+}
+
+// The same end from two sample values and their inside flags, for a fetch that is not blend_taps (interpolate_bicubic.hip): the
+// decision, mixf and the store are mc_store_inside_or_blend's.
+__device__ __forceinline__ void mc_store_inside_or_blend_values(const V4 &P, bool pInside, const V4 &C, bool cInside, int only, float t,
+                                                                uint8_t *__restrict__ out, size_t outPitch, int x, int y) {
+    if (only == 0) only = pInside && !cInside ? 1 : (cInside && !pInside ? 2 : 0);
     const V4 r = only == 1 ? P : only == 2 ? C : V4{mixf(P.x, C.x, t), mixf(P.y, C.y, t), mixf(P.z, C.z, t), mixf(P.w, C.w, t)};
     *reinterpret_cast<uint32_t *>(out + (size_t)y * outPitch + (size_t)x * 4u) = pack_rgba8_unorm(r.x, r.y, r.z, r.w);
 }
