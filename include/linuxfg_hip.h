@@ -66,7 +66,9 @@ typedef struct lfg_frame {
     void    *data;      /* device memory; NULL = empty frame (VK_NULL_HANDLE) */
     uint32_t width;
     uint32_t height;
-    uint32_t pitch;     /* bytes per row, >= width * bytes-per-pixel */
+    uint32_t pitch;     /* bytes per row, >= width * bytes-per-pixel and <= 0x7fffffff: every call returns LFG_ERR_INVALID
+                         * for a larger one before anything is enqueued or allocated (the frame kernels take it as an int).
+                         * lfg_mask.pitch and the lfg_nv12 pitches have no such limit. */
     uint32_t format;    /* lfg_format */
     uint32_t owned;     /* 1: allocated by lfg_frame_create and freed by lfg_frame_destroy */
     uint32_t reserved;
@@ -139,7 +141,8 @@ const char *lfg_last_error(const lfg_context *ctx);
 int  lfg_frame_create(lfg_context *ctx, uint32_t width, uint32_t height, uint32_t format, lfg_frame *out);
 /* FrameManager::DestroyFrame (src/frame_manager.cpp:71-81): idempotent, NULL-safe. */
 void lfg_frame_destroy(lfg_context *ctx, lfg_frame *frame);
-/* Describe caller-owned device memory (e.g. a torch tensor) as a frame; never freed here. */
+/* Describe caller-owned device memory (e.g. a torch tensor) as a frame; never freed here.  LFG_ERR_INVALID for a pitch below
+ * width * bytes-per-pixel (compared in 64 bits) or above 0x7fffffff (lfg_frame.pitch). */
 int  lfg_frame_wrap(void *device_ptr, uint32_t width, uint32_t height, uint32_t pitch, uint32_t format,
                     lfg_frame *out);
 /* FrameManager::CopyFrameData (src/frame_manager.cpp:83-145): same-size check, then a

@@ -42,9 +42,15 @@ uint32_t bytes_per_pixel(uint32_t format) {
     }
 }
 
+// The largest lfg_frame pitch (include/linuxfg_hip.h): the frame kernels take the pitch as a 32-bit int.
+constexpr uint32_t kMaxFramePitch = 0x7fffffffu;
+
+// A frame whose pitch no call takes: NULL is not this function's to refuse.
+bool pitch_too_large(const lfg_frame *f) { return f && f->pitch > kMaxFramePitch; }
+
 bool frame_ok(const lfg_frame *f, uint32_t format) {
-    return f && f->data && f->width > 0 && f->height > 0 && f->format == format &&
-           f->pitch >= f->width * bytes_per_pixel(format);
+    return f && f->data && f->width > 0 && f->height > 0 && f->format == format && f->pitch <= kMaxFramePitch &&
+           (uint64_t)f->pitch >= (uint64_t)f->width * bytes_per_pixel(format);
 }
 
 bool same_size(const lfg_frame *a, const lfg_frame *b) { return a->width == b->width && a->height == b->height; }
@@ -620,7 +626,9 @@ LFG_EXPORT void lfg_frame_destroy(lfg_context *ctx, lfg_frame *frame) {
 LFG_EXPORT int lfg_frame_wrap(void *device_ptr, uint32_t width, uint32_t height, uint32_t pitch, uint32_t format,
                               lfg_frame *out) {
     const uint32_t bpp = bytes_per_pixel(format);
-    if (!out || !device_ptr || !bpp || width == 0 || height == 0 || pitch < width * bpp) return LFG_ERR_INVALID;
+    if (!out || !device_ptr || !bpp || width == 0 || height == 0 || pitch > kMaxFramePitch ||
+        (uint64_t)pitch < (uint64_t)width * bpp)
+        return LFG_ERR_INVALID;
     out->data = device_ptr; out->width = width; out->height = height; out->pitch = pitch;
     out->format = format; out->owned = 0; out->reserved = 0;
     return LFG_OK;
@@ -628,6 +636,7 @@ LFG_EXPORT int lfg_frame_wrap(void *device_ptr, uint32_t width, uint32_t height,
 
 LFG_EXPORT int lfg_frame_copy(lfg_context *ctx, const lfg_frame *src, lfg_frame *dst) {
     if (!ctx || !src || !dst || !src->data || !dst->data) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_copy: NULL frame");
+    if (pitch_too_large(src) || pitch_too_large(dst)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_copy: a pitch above 0x7fffffff");
     if (!same_size(src, dst) || src->format != dst->format)                  // frame_manager.cpp:84-87
         return fail(ctx, LFG_ERR_INVALID, "Source and destination frame dimensions do not match");
     const size_t row = (size_t)src->width * bytes_per_pixel(src->format);
@@ -651,6 +660,7 @@ LFG_EXPORT void lfg_staging_destroy(lfg_context *ctx, void *host_ptr) {
 
 LFG_EXPORT int lfg_frame_upload(lfg_context *ctx, lfg_frame *dst, const void *host, size_t bytes) {
     if (!ctx || !dst || !dst->data || !host) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_upload: NULL argument");
+    if (pitch_too_large(dst)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_upload: a pitch above 0x7fffffff");
     const size_t row = (size_t)dst->width * bytes_per_pixel(dst->format);
     if (bytes < row * dst->height) {                                          // window_capture.cpp:478-481
         char msg[160];
@@ -663,6 +673,7 @@ LFG_EXPORT int lfg_frame_upload(lfg_context *ctx, lfg_frame *dst, const void *ho
 
 LFG_EXPORT int lfg_frame_download(lfg_context *ctx, const lfg_frame *src, void *host, size_t bytes) {
     if (!ctx || !src || !src->data || !host) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_download: NULL argument");
+    if (pitch_too_large(src)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_download: a pitch above 0x7fffffff");
     const size_t row = (size_t)src->width * bytes_per_pixel(src->format);
     if (bytes < row * src->height) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_download: host buffer too small");
     LFG_HIP(ctx, hipMemcpy2DAsync(host, row, src->data, src->pitch, row, src->height, hipMemcpyDeviceToHost, ctx->cur().stream));
@@ -720,6 +731,7 @@ LFG_EXPORT int lfg_ring_acquire(lfg_ring *ring, void **out_host_ptr, uint32_t *o
 static int ring_transfer(lfg_ring *ring, uint32_t slot, const lfg_frame *f, bool upload) {
     lfg_context *ctx = ring->ctx;
     if (!f || !f->data) return fail(ctx, LFG_ERR_INVALID, "lfg_ring transfer: NULL frame");
+    if (pitch_too_large(f)) return fail(ctx, LFG_ERR_INVALID, "lfg_ring transfer: a pitch above 0x7fffffff");
     const size_t row = (size_t)f->width * bytes_per_pixel(f->format), need = row * f->height;
     if (ring->slot_bytes < need) return fail(ctx, LFG_ERR_INVALID, "lfg_ring transfer: slot smaller than the frame");
     LFG_HIP(ctx, hipSetDevice(ctx->device));
@@ -1229,6 +1241,8 @@ int detecting_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *c
 LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                       lfg_frame *out, float factor) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: NULL argument");
+    if (pitch_too_large(prev) || pitch_too_large(curr) || pitch_too_large(out))     // before the lane's temporaries are made
+        return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: a pitch above 0x7fffffff");
     if (ctx->cut_permille >= 0) {
         lfg_frame *const outs[1] = {out};
         return detecting_frames(ctx, prev, curr, outs, &factor, 1, false);
@@ -1296,6 +1310,9 @@ LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, co
 LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr,
                                             lfg_frame *const *outs, const float *factors, uint32_t count) {
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames_multi: NULL argument");
+    bool too_large = pitch_too_large(prev) || pitch_too_large(curr);                // before the lane's temporaries are made
+    for (uint32_t i = 0; outs && count <= LFG_MAX_FACTORS && i < count; ++i) too_large = too_large || pitch_too_large(outs[i]);
+    if (too_large) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames_multi: a pitch above 0x7fffffff");
     if (ctx->cut_permille >= 0) return detecting_frames(ctx, prev, curr, outs, factors, count, true);
     const lfg_frame *vectors = nullptr;
     int rc = frame_vectors(ctx, prev, curr, &vectors);

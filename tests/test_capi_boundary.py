@@ -57,6 +57,17 @@ def test_abi_version_and_frame_layout(capi):
     assert lib.lfg_frame_wrap(None, 8, 4, 32, capi.FORMAT_RGBA8, ctypes.byref(f)) != 0
 
 
+def test_frame_wrap_checks_the_pitch_in_64_bits_and_caps_it(capi):
+    """width * bytes-per-pixel is compared in 64 bits (2^30 * 4 is 0 in 32), and a pitch above 0x7fffffff is refused: the
+    frame kernels take it as an int."""
+    lib, f, p = capi.load(), capi.Frame(), ctypes.c_void_p(0x1000)
+    assert lib.lfg_frame_wrap(p, 2 ** 30, 2, 4, capi.FORMAT_RGBA8, ctypes.byref(f)) == capi.ERR_INVALID
+    assert lib.lfg_frame_wrap(p, 2 ** 30, 2, 2 ** 31, capi.FORMAT_RGBA8, ctypes.byref(f)) == capi.ERR_INVALID
+    assert lib.lfg_frame_wrap(p, 1, 2, 2 ** 31, capi.FORMAT_RGBA8, ctypes.byref(f)) == capi.ERR_INVALID
+    assert lib.lfg_frame_wrap(p, 1, 2, 0x7fffffff - 3, capi.FORMAT_RGBA8, ctypes.byref(f)) == 0
+    assert (f.width, f.height, f.pitch) == (1, 2, 0x7fffffff - 3)
+
+
 def test_no_gpu_means_a_loud_failure_not_a_fallback(capi):
     import torch
     if torch.cuda.is_available():
