@@ -1017,6 +1017,60 @@ int  lfg_resample_antiring(lfg_context *ctx, const lfg_frame *in, lfg_frame *out
  * 2^31 or more. */
 int  lfg_resample_brackets(uint32_t in_size, uint32_t out_size, int32_t *lo, int32_t *hi);
 
+/* Edge-adaptive upscaling.  No reference counterpart.  Every filter of lfg_resample is separable and cannot tell along an edge
+ * from across it; this call analyses, per output pixel, the direction and the strength of the luma gradient over the 2 x 2
+ * texels that bracket it, weighs 12 taps with a window rotated to that gradient -- narrow across the edge, wide along it -- and
+ * holds the result to the bracket's range (the EASU pass of FSR 1, of which lfg_sharpen is the RCAS half).  It depends on no
+ * setting of the context, is enqueued on the selected lane as ONE launch, is timed under LFG_STAGE_SCALE and leaves
+ * lfg_scale_last_kernel alone.  All integers; >> is the arithmetic shift (floor) and / floor division of non-negatives.
+ *   Frames: both RGBA8, sizes >= 1; `out` at least as large as `in` on each axis (equal sizes are allowed), a shrinking axis
+ *   is LFG_ERR_UNSUPPORTED.  Pitch, alignment, overlap, NULL and format rules are lfg_resample's; a violation is
+ *   LFG_ERR_INVALID.  Both errors return before anything is enqueued, with a message latched.  A view is its own image:
+ *   nothing outside it is read.  Only W * 4 bytes of each output row are written.
+ *   Positions, per axis `in` -> `out` (lfg_upscale_edge_positions): N = (2p + 1) in - out and D = 2 out;
+ *     base a(p) = floor(N / D), in -1 .. in - 1;  frac phi(p) = floor(256 (N - a D) / D), in 0 .. 255.
+ *   Every texel coordinate is clamped to the frame when it is read.
+ *   Per-texel analysis, a property of the source texel, not of the output pixel: luma L = R + 2 G + B; with l, r, u, d the
+ *   clamped neighbours' luma and c the texel's own,
+ *     dX = r - l, mX = max(|r - c|, |c - l|);  dY = d - u, mY = max(|d - c|, |c - u|).
+ *   Per output pixel (px, py): fx = phi_x(px), fy = phi_y(py), ax = a_x(px), ay = a_y(py).  The four bracket texels are
+ *   T(i, j) = (ax + i, ay + j) for i, j in {0, 1}, their weights w = (i ? fx : 256 - fx) (j ? fy : 256 - fy), and the weighted
+ *   sums over the four DX = sum w dX, DY = sum w dY, AX = sum w |dX|, MX = sum w mX, and AY, MY likewise.
+ *   1. Direction.  gx = DX >> 10, gy = DY >> 10; k is the smallest index in 0 .. 15 that maximises |gx COS[k] + gy SIN[k]|,
+ *        COS = 256, 251, 237, 213, 181, 142, 98, 50, 0, -50, -98, -142, -181, -213, -237, -251
+ *        SIN = 0, 50, 98, 142, 181, 213, 237, 251, 256, 251, 237, 213, 181, 142, 98, 50
+ *   2. Edge strength.  level(A, M) = 0 if M = 0, else how many k' in {1, 2, 3, 4} have 4 A >= k' M;
+ *      q = level(AX, MX)^2 + level(AY, MY)^2, in 0 .. 32.  A clean step or ramp has level 4, a one-pixel line level 0.
+ *   3. Flat.  If max(|DX|, |DY|) < 4 * 65536, then k = 0 and q = 0.
+ *   4. Shape (k, q) -> (A, B, C, lob, clp) (lfg_upscale_edge_shapes, the one builder): c = COS[k], s = SIN[k],
+ *      m = max(|c|, |s|), stretch = (65536 + m / 2) / m, len = q^2, sx = 256 + (((stretch - 256) len) >> 10),
+ *      sy = 256 - (len >> 3), lob = 2048 - ((1188 len) >> 10), clp = 2^24 / lob,
+ *        A = (sx^2 c^2 + sy^2 s^2) >> 22,  B = ((sx^2 - sy^2) c s) >> 22 (signed: a floor),  C = (sx^2 s^2 + sy^2 c^2) >> 22.
+ *      All five fit an int16_t: A, C <= 2047 and clp <= 19,508.
+ *   5. Taps: the 4 x 4 texels (ax - 1 .. ax + 2, ay - 1 .. ay + 2) without the four corners, 12 in all.  For tap (i, j):
+ *        ox = 256 i - fx, oy = 256 j - fy
+ *        d2 = clamp((A ((ox ox) >> 4) + 2 B ((ox oy) >> 4) + C ((oy oy) >> 4)) >> 10, 0, clp)
+ *        t1 = ((1638 d2) >> 12) - 4096;  b = ((25 ((t1 t1) >> 12)) >> 4) - 2304
+ *        t2 = ((lob d2) >> 12) - 4096;   wt = (b ((t2 t2) >> 12)) >> 12
+ *      -- EASU's window (25/16 (2/5 x^2 - 1)^2 - 9/16) (lob x^2 - 1)^2 in Q12.
+ *   6. Result.  W = sum wt; for channel c, S_c = sum wt texel_c, all four channels alike;
+ *        out_c = clamp((2 S_c + W) / (2 W), lo_c, hi_c)
+ *      with lo_c and hi_c the minimum and the maximum of the four bracket texels in that channel.  W lies in 3,364 .. 8,356 for
+ *      every shape and every (fx, fy), so the division is defined, and it is exact however the kernel forms it; a numerator
+ *      below 0 ends at lo_c.  Every intermediate fits 32 bits.
+ * Consequences: a constant frame stays constant; every output byte lies within its 2 x 2 bracket, so nothing overshoots;
+ * in == out is allowed but is not the identity.
+ * The first call for an (in, out) pair of an axis builds its positions and uploads them; the context keeps a bounded number
+ * of them, like the tap tables, and one copy of the shape table.  For presented frames. */
+int  lfg_upscale_edge(lfg_context *ctx, const lfg_frame *in, lfg_frame *out);
+/* The positions above -- the one builder: lfg_upscale_edge uploads what this returns.  A pure host function: no context, no
+ * GPU.  base and frac hold out_size entries each.  Any sizes are taken (for out_size < in_size base still is the floor, but
+ * steps by more than 1).  LFG_ERR_INVALID for a NULL pointer, a size of 0 or a size of 2^31 or more. */
+int  lfg_upscale_edge_positions(uint32_t in_size, uint32_t out_size, int32_t *base, uint8_t *frac);
+/* The shape table above: shapes[(k * 33 + q) * 5 + 0 .. 4] = A, B, C, lob, clp.  A pure host function.  LFG_ERR_INVALID for
+ * NULL. */
+int  lfg_upscale_edge_shapes(int16_t shapes[16 * 33 * 5]);
+
 /* The reference's own data flow keeps prev / curr at INPUT resolution (src/scaler.cpp:443,451): there the generated
  * frame is interpolated at input resolution and then upscaled like a captured one.  This does both in one call --
  * identical, byte for byte, to lfg_interpolate into a temporary followed by lfg_scale of that temporary -- and where

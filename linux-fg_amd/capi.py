@@ -213,6 +213,9 @@ SIGNATURES = {
     "lfg_resample_taps": (_i, [_i, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int16)]),
     "lfg_resample_antiring": (_i, [_vp, _FP, _FP, _i, _i]),
     "lfg_resample_brackets": (_i, [_u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "lfg_upscale_edge": (_i, [_vp, _FP, _FP]),
+    "lfg_upscale_edge_positions": (_i, [_u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)]),
+    "lfg_upscale_edge_shapes": (_i, [ctypes.POINTER(ctypes.c_int16)]),
     "lfg_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_set_fused_interpolate_scale": (_i, [_vp, _i]),
     "lfg_set_fused_motion_interpolate": (_i, [_vp, _i]),
@@ -306,6 +309,32 @@ def resample_brackets(n_in: int, n_out: int):
         err.code = rc
         raise err
     return lo, hi
+
+
+def upscale_edge_positions(n_in: int, n_out: int):
+    """(base[n_out] int32, frac[n_out] uint8) of lfg_upscale_edge_positions: the texel left of (above) each output sample of one
+    axis and the sample's distance from it in 256ths, which lfg_upscale_edge uploads.  Needs no context and no GPU.  Raises
+    LfgError, with the code as `.code`."""
+    n_in, n_out = int(n_in), int(n_out)
+    rows = n_out if 0 < n_out < 2 ** 31 else 0
+    base, frac = np.zeros(rows, np.int32), np.zeros(rows, np.uint8)
+    rc = load().lfg_upscale_edge_positions(n_in if 0 < n_in < 2 ** 32 else 0, rows, base.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                           frac.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc != 0:
+        err = LfgError(f"lfg_upscale_edge_positions failed ({rc}): a size of 0, or of 2^31 samples or more")
+        err.code = rc
+        raise err
+    return base, frac
+
+
+def upscale_edge_shapes() -> np.ndarray:
+    """(16, 33, 5) int16 of lfg_upscale_edge_shapes: (A, B, C, lob, clp) per direction and edge strength.  Needs no context and
+    no GPU."""
+    t = np.zeros((16, 33, 5), np.int16)
+    rc = load().lfg_upscale_edge_shapes(t.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
+    if rc != 0:
+        raise LfgError(f"lfg_upscale_edge_shapes failed ({rc})")
+    return t
 
 
 def sampling_weights() -> np.ndarray:
@@ -893,6 +922,11 @@ class Context:
         """lfg_resample: `src` resampled into `dst` (both RGBA8, any sizes, no overlap) under one of FILTER_*, anti-aliased where
         an axis shrinks; one launch, timed under STAGE_SCALE."""
         self._check(self.lib.lfg_resample(self.h, ctypes.byref(src), ctypes.byref(dst), int(filt)), "lfg_resample")
+
+    def upscale_edge(self, src: Frame, dst: Frame):
+        """lfg_upscale_edge: `src` upscaled into `dst` (both RGBA8, `dst` at least as large on each axis, no overlap) by the
+        edge-adaptive 12-tap kernel; every output byte stays within its 2 x 2 bracket.  One launch on the selected lane."""
+        self._check(self.lib.lfg_upscale_edge(self.h, ctypes.byref(src), ctypes.byref(dst)), "lfg_upscale_edge")
 
     def resample_antiring(self, src: Frame, dst: Frame, filt: int, strength: int):
         """lfg_resample_antiring: lfg_resample with each upscaling pass held to the range of the two source samples that bracket

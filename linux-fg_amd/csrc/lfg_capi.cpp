@@ -519,6 +519,8 @@ LFG_EXPORT void lfg_context_destroy(lfg_context *ctx) {
     for (auto &t : ctx->uv_tables) (void)hipFree(t.d_uv);
     for (auto &t : ctx->resample_tables) (void)hipFree(t.d_base);
     for (auto &t : ctx->resample_brackets) (void)hipFree(t.d_base);
+    for (auto &t : ctx->edge_positions) (void)hipFree(t.d_base);
+    if (ctx->edge_shapes) (void)hipFree(ctx->edge_shapes);
     if (ctx->motion_tables) (void)hipFree(ctx->motion_tables);
     delete ctx;
 }
@@ -2281,16 +2283,23 @@ int resample_table(lfg_context *ctx, int filter, uint32_t in_size, uint32_t out_
     return LFG_OK;
 }
 
+// What lfg_resample, lfg_resample_antiring and lfg_upscale_edge ask of their two frames before anything else.
+int resample_frames(lfg_context *ctx, const lfg_frame *in, const lfg_frame *out, const char *who) {
+    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": in and out must be non-empty RGBA8");
+    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    return LFG_OK;
+}
+
 // lfg_resample (strength 0) and lfg_resample_antiring: the checks, the tables and the one launch.  A pass is anti-ringed where
 // the strength is positive, the filter has weights to ring with and the pass's axis grows; where no pass is, this is
 // lfg_resample: the same kernel and the same launch.
 int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength, const char *who) {
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
-    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
-        return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": in and out must be non-empty RGBA8");
-    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
-        return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    const int frames = resample_frames(ctx, in, out, who);
+    if (frames != LFG_OK) return frames;
     if (!resample_filter_known(filter)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": unknown filter");
     if (strength < 0 || strength > 64) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": strength must be in [0, 64]");
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": the output overlaps the input");
@@ -2320,6 +2329,112 @@ LFG_EXPORT int lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *ou
 
 LFG_EXPORT int lfg_resample_antiring(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength) {
     return resample_call(ctx, in, out, filter, strength, "lfg_resample_antiring");
+}
+
+// ---- edge-adaptive upscaling (upscale_edge.hip)
+
+LFG_EXPORT int lfg_upscale_edge_positions(uint32_t in_size, uint32_t out_size, int32_t *base, uint8_t *frac) {
+    if (!base || !frac || in_size == 0 || out_size == 0 || in_size > 0x7fffffffu || out_size > 0x7fffffffu) return LFG_ERR_INVALID;
+    const int64_t in = in_size, out = out_size, D = 2 * out;
+    for (uint32_t p = 0; p < out_size; ++p) {
+        const int64_t N = (2 * (int64_t)p + 1) * in - out;             // below 2^63: both sizes are below 2^31
+        const int64_t a = N >= 0 ? N / D : -((-N + D - 1) / D);
+        base[p] = (int32_t)a;
+        frac[p] = (uint8_t)((256 * (N - a * D)) / D);
+    }
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_upscale_edge_shapes(int16_t *shapes) {
+    if (!shapes) return LFG_ERR_INVALID;
+    static const int kCos[lfg::kEdgeDirections] = {256, 251, 237, 213, 181, 142, 98, 50, 0, -50, -98, -142, -181, -213, -237, -251};
+    static const int kSin[lfg::kEdgeDirections] = {0, 50, 98, 142, 181, 213, 237, 251, 256, 251, 237, 213, 181, 142, 98, 50};
+    const auto floor_shift = [](int64_t v, int n) { return v >= 0 ? v >> n : -((-v + ((int64_t)1 << n) - 1) >> n); };
+    for (int k = 0; k < lfg::kEdgeDirections; ++k)
+        for (int q = 0; q < lfg::kEdgeStrengths; ++q) {
+            const int64_t c = kCos[k], s = kSin[k], m = std::max(std::abs(kCos[k]), std::abs(kSin[k]));
+            const int64_t stretch = (65536 + m / 2) / m, len = q * q;
+            const int64_t sx = 256 + (((stretch - 256) * len) >> 10), sy = 256 - (len >> 3), lob = 2048 - ((1188 * len) >> 10);
+            int16_t *row = shapes + (size_t)(k * lfg::kEdgeStrengths + q) * 5u;
+            row[0] = (int16_t)((sx * sx * c * c + sy * sy * s * s) >> 22);
+            row[1] = (int16_t)floor_shift((sx * sx - sy * sy) * c * s, 22);
+            row[2] = (int16_t)((sx * sx * s * s + sy * sy * c * c) >> 22);
+            row[3] = (int16_t)lob;
+            row[4] = (int16_t)(((int64_t)1 << 24) / lob);
+        }
+    return LFG_OK;
+}
+
+namespace {
+
+// The positions of one axis, built and uploaded at their first use.  The kernel sizes a tile's LDS on the strength of
+//   0 <= base[p + 1] - base[p] <= 1   and   -1 <= base[p] <= in - 1,
+// which hold because out >= in and are asserted here on what the builder returned.
+int edge_position_table(lfg_context *ctx, uint32_t in_size, uint32_t out_size, lfg::EdgeAxis *out) {
+    for (const auto &t : ctx->edge_positions)
+        if (t.in_size == in_size && t.out_size == out_size) { *out = t.axis; return LFG_OK; }
+    const size_t n = out_size;
+    std::vector<uint8_t> host(5 * n);                              // base | frac
+    int32_t *base = reinterpret_cast<int32_t *>(host.data());
+    if (lfg_upscale_edge_positions(in_size, out_size, base, host.data() + 4 * n) != LFG_OK)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_upscale_edge: a frame of this size has no positions");
+    for (size_t p = 0; p < n; ++p)
+        if (base[p] < -1 || (int64_t)base[p] > (int64_t)in_size - 1 || (p > 0 && (base[p] < base[p - 1] || base[p] > base[p - 1] + 1)))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_upscale_edge: positions that leave a tile's span (" + std::to_string(in_size) + " -> " +
+                                                  std::to_string(out_size) + ", sample " + std::to_string(p) + ")");
+    lfg::EdgePositionTable t;
+    t.in_size = in_size; t.out_size = out_size;
+    LFG_HIP(ctx, hipMalloc((void **)&t.d_base, host.size()));
+    const hipError_t e = hipMemcpy(t.d_base, host.data(), host.size(), hipMemcpyHostToDevice);   // (synchronous, as the axis table's)
+    if (e != hipSuccess) { (void)hipFree(t.d_base); return fail_hip(ctx, e, "hipMemcpy(edge positions)"); }
+    t.axis.base = reinterpret_cast<const int32_t *>(t.d_base);
+    t.axis.frac = t.d_base + 4 * n;
+    ctx->edge_positions.push_back(t);
+    *out = t.axis;
+    return LFG_OK;
+}
+
+// The shape table on the device, rows padded to 16 bytes: made once per context.
+int edge_shape_table(lfg_context *ctx) {
+    if (ctx->edge_shapes) return LFG_OK;
+    constexpr size_t kRows = (size_t)lfg::kEdgeDirections * lfg::kEdgeStrengths;
+    std::vector<int16_t> rows(kRows * 5u);
+    std::vector<lfg::EdgeShape> host(kRows);
+    if (lfg_upscale_edge_shapes(rows.data()) != LFG_OK) return fail(ctx, LFG_ERR_INVALID, "lfg_upscale_edge: no shape table");
+    for (size_t i = 0; i < kRows; ++i) host[i] = lfg::EdgeShape{rows[5 * i], rows[5 * i + 1], rows[5 * i + 2], rows[5 * i + 3], rows[5 * i + 4], {0, 0, 0}};
+    lfg::EdgeShape *d = nullptr;
+    LFG_HIP(ctx, hipMalloc((void **)&d, kRows * sizeof(lfg::EdgeShape)));
+    const hipError_t e = hipMemcpy(d, host.data(), kRows * sizeof(lfg::EdgeShape), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail_hip(ctx, e, "hipMemcpy(edge shapes)"); }
+    ctx->edge_shapes = d;
+    return LFG_OK;
+}
+
+}  // namespace
+
+LFG_EXPORT int lfg_upscale_edge(lfg_context *ctx, const lfg_frame *in, lfg_frame *out) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = resample_frames(ctx, in, out, "lfg_upscale_edge");
+    if (rc != LFG_OK) return rc;
+    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_upscale_edge: the output overlaps the input");
+    if (out->width < in->width || out->height < in->height)
+        return fail(ctx, LFG_ERR_UNSUPPORTED, "lfg_upscale_edge: the output is smaller than the input on an axis (lfg_resample shrinks)");
+    // bounded like the tap tables, and trimmed before either lookup so that the two of a call cannot free each other's
+    while (ctx->edge_positions.size() > 14) {
+        (void)sync_lanes(ctx);                                 // a queued kernel may still read it
+        (void)hipFree(ctx->edge_positions.front().d_base);
+        ctx->edge_positions.erase(ctx->edge_positions.begin());
+    }
+    lfg::EdgeAxis x{}, y{};
+    rc = edge_position_table(ctx, in->width, out->width, &x);
+    if (rc == LFG_OK) rc = edge_position_table(ctx, in->height, out->height, &y);
+    if (rc == LFG_OK) rc = edge_shape_table(ctx);
+    if (rc != LFG_OK) return rc;
+    StageTimer timer(ctx, LFG_STAGE_SCALE);
+    const hipError_t e = lfg::launch_upscale_edge(ctx->cur().stream, *in, *out, x, y, ctx->edge_shapes);
+    if (e != hipSuccess) return fail_hip(ctx, e, "upscale_edge kernel launch");
+    return LFG_OK;
 }
 
 LFG_EXPORT int lfg_set_fused_motion_interpolate(lfg_context *ctx, int enabled) {

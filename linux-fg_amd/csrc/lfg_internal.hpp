@@ -11,6 +11,7 @@
 #include "linuxfg_hip.h"
 #include "lfg_motion_verdict.hpp"
 #include "lfg_resample.hpp"
+#include "lfg_upscale_edge.hpp"
 
 namespace lfg {
 
@@ -161,6 +162,14 @@ struct ResampleBracketTable {
     ResampleBracket bracket{};
 };
 
+// The positions of one axis for lfg_upscale_edge, keyed by (in, out): what lfg_upscale_edge_positions returned, on the device in
+// one allocation (base | frac).
+struct EdgePositionTable {
+    uint32_t in_size = 0, out_size = 0;
+    uint8_t *d_base = nullptr;
+    EdgeAxis axis{};
+};
+
 struct ProfileSlot {
     hipEvent_t begin = nullptr, end = nullptr;
     int stage = 0;
@@ -232,6 +241,8 @@ struct lfg_context {
     std::vector<lfg::UvTable> uv_tables;      // likewise (interpolate)
     std::vector<lfg::ResampleTable> resample_tables;   // likewise (lfg_resample)
     std::vector<lfg::ResampleBracketTable> resample_brackets;   // likewise (lfg_resample_antiring)
+    std::vector<lfg::EdgePositionTable> edge_positions;   // likewise (lfg_upscale_edge)
+    lfg::EdgeShape *edge_shapes = nullptr;     // lfg_upscale_edge_shapes on the device, made by the first lfg_upscale_edge
     int motion_slots = 0;                      // prefilter workgroups resident at once on this device (0 = not queried yet)
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only
@@ -428,6 +439,9 @@ hipError_t launch_resample(hipStream_t s, const lfg_frame &in, const lfg_frame &
 // 0 where that pass is not anti-ringed (its bracket is then not read), and not both are 0.
 hipError_t launch_resample_antiring(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const ResampleAxis &x, const ResampleAxis &y,
                                     const ResamplePlan &plan, const ResampleBracket &bx, const ResampleBracket &by, int sx, int sy);
+// Edge-adaptive upscaling (upscale_edge.hip): one launch; `shapes` is the table on the device, 528 rows.
+hipError_t launch_upscale_edge(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const EdgeAxis &x, const EdgeAxis &y,
+                               const EdgeShape *shapes);
 hipError_t launch_mv_export(hipStream_t s, const lfg_frame &mv, float *rgba32f);
 hipError_t launch_sqrt_selftest(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *d_mismatch);
 
