@@ -98,9 +98,13 @@ int         lfg_device_count(void);
 int         lfg_context_create(int device_ordinal, lfg_context **out_ctx);
 /* Replaces VulkanContext::Cleanup / FrameManager::Cleanup / Scaler::Cleanup.  NULL is a no-op. */
 void        lfg_context_destroy(lfg_context *ctx);
-/* Adopt an externally owned hipStream_t (e.g. PyTorch's current stream) as the compute
- * queue, so the caller's events and collectives order against these kernels.  NULL restores
- * the context's own stream. */
+/* Adopt an externally owned hipStream_t (a stream the caller created, e.g. a PyTorch side
+ * stream's handle) as the selected lane's compute queue: the calls made on that lane run on it,
+ * so the caller's events and collectives order against these kernels.  NULL -- handle 0 --
+ * restores the lane's own stream and adopts nothing: HIP's null stream, which is handle 0 and is
+ * PyTorch's DEFAULT stream, cannot be adopted.  The stream stays the caller's: shrinking the lanes
+ * and destroying the context wait for it and never destroy it.  lfg_context_get_stream returns
+ * the stream the selected lane's calls run on, its own or the adopted one. */
 int         lfg_context_set_stream(lfg_context *ctx, void *hip_stream);
 void       *lfg_context_get_stream(lfg_context *ctx);
 int         lfg_context_device(const lfg_context *ctx);
@@ -116,7 +120,10 @@ int         lfg_sync(lfg_context *ctx);
  *                           for the lanes that go and frees what they own
  *   lfg_lane_select(ctx, j) the calls that follow enqueue on lane j
  *   lfg_lane_mark(ctx)      remember "here" on the selected lane
- *   lfg_lane_wait(ctx, i)   the selected lane's later work waits until lane i has reached its last mark
+ *   lfg_lane_wait(ctx, i)   the selected lane's later work waits until lane i has reached its last mark: the newest
+ *                           lfg_lane_mark made on lane i before this call, not the end of lane i -- what lane i was given
+ *                           after that mark is not waited for; before lane i's first mark, and for i the selected lane
+ *                           itself, the call orders nothing
  *   lfg_lane_sync(ctx)      the HOST waits for the selected lane alone (a frame's buffers are free again; lfg_sync waits for
  *                           every lane) -- what vkQueueWaitIdle after each submission (src/scaler.cpp:389-393) becomes when
  *                           n frames are in flight: wait for frame k before frame k + n goes onto its lane
@@ -169,15 +176,17 @@ int  lfg_ring_create(lfg_context *ctx, uint32_t slots, size_t slot_bytes, lfg_ri
 void lfg_ring_destroy(lfg_ring *ring);
 int  lfg_ring_acquire(lfg_ring *ring, void **out_host_ptr, uint32_t *out_slot);
 /* Upload slot -> frame (or download frame -> slot) asynchronously and mark the slot busy
- * until that transfer finishes.  Transfers run on the ring's own stream, next to the kernels:
- * an upload is ordered after everything enqueued so far and before everything enqueued later;
- * a download is ordered after everything enqueued so far only -- later kernels do not wait for it. */
+ * until that transfer finishes.  Transfers run on the ring's own stream, next to the kernels, and
+ * are ordered against the lane SELECTED AT THE CALL, no other: an upload is ordered after everything
+ * enqueued on that lane so far and before everything enqueued on it later; a download is ordered
+ * after everything enqueued on that lane so far only -- later kernels do not wait for it.  Work on
+ * another lane that reads or writes the frame is the caller's to order (lfg_lane_mark / lfg_lane_wait). */
 int  lfg_ring_upload(lfg_ring *ring, uint32_t slot, lfg_frame *dst);
 int  lfg_ring_download(lfg_ring *ring, uint32_t slot, const lfg_frame *src);
 /* Block the host until the slot's last transfer has finished (the vkQueueWaitIdle before the
  * reference maps its staging buffer, src/scaler.cpp:532-536), then the slot's pixels may be read. */
 int  lfg_ring_wait(lfg_ring *ring, uint32_t slot);
-/* Make kernels enqueued from now on wait (on the device, not the host) for the slot's last transfer:
+/* Make kernels enqueued on the selected lane from now on wait (on the device, not the host) for the slot's last transfer:
  * call it before overwriting a frame whose download into `slot` may still be running. */
 int  lfg_ring_fence_slot(lfg_ring *ring, uint32_t slot);
 

@@ -366,6 +366,36 @@ def load() -> ctypes.CDLL:
     return _lib
 
 
+class Ring:
+    """lfg_ring (Context.ring_create): transfers between pinned slots and frames, ordered against the lane selected at the call."""
+
+    def __init__(self, ctx: "Context", handle, slot_bytes: int):
+        self.ctx, self.h, self.slot_bytes = ctx, handle, slot_bytes
+
+    def acquire(self):
+        """(the slot's bytes as a uint8 array (no copy), its index); blocks while the slot's last transfer runs."""
+        p, slot = _vp(), _u32()
+        self.ctx._check(self.ctx.lib.lfg_ring_acquire(self.h, ctypes.byref(p), ctypes.byref(slot)), "lfg_ring_acquire")
+        return np.ctypeslib.as_array((ctypes.c_uint8 * self.slot_bytes).from_address(p.value)), int(slot.value)
+
+    def upload(self, slot: int, dst: Frame):
+        self.ctx._check(self.ctx.lib.lfg_ring_upload(self.h, int(slot), ctypes.byref(dst)), "lfg_ring_upload")
+
+    def download(self, slot: int, src: Frame):
+        self.ctx._check(self.ctx.lib.lfg_ring_download(self.h, int(slot), ctypes.byref(src)), "lfg_ring_download")
+
+    def wait(self, slot: int):
+        self.ctx._check(self.ctx.lib.lfg_ring_wait(self.h, int(slot)), "lfg_ring_wait")
+
+    def fence_slot(self, slot: int):
+        self.ctx._check(self.ctx.lib.lfg_ring_fence_slot(self.h, int(slot)), "lfg_ring_fence_slot")
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.lfg_ring_destroy(self.h)
+            self.h = None
+
+
 class Context:
     """One GPU, one stream (lfg_context).  Mirrors the reference's VulkanContext + FrameManager calls."""
 
@@ -407,6 +437,10 @@ class Context:
 
     def set_stream(self, stream: int | None):
         self._check(self.lib.lfg_context_set_stream(self.h, _vp(stream or 0)), "lfg_context_set_stream")
+
+    def get_stream(self) -> int:
+        """The hipStream_t the selected lane's calls run on, as an integer: its own, or the one it has adopted."""
+        return int(self.lib.lfg_context_get_stream(self.h) or 0)
 
     def sync(self):
         self._check(self.lib.lfg_sync(self.h), "lfg_sync")
@@ -501,6 +535,12 @@ class Context:
 
     def download_async(self, f: Frame, host: np.ndarray):
         self._check(self.lib.lfg_frame_download(self.h, ctypes.byref(f), host.ctypes.data_as(_vp), host.nbytes), "lfg_frame_download")
+
+    def ring_create(self, slots: int, slot_bytes: int) -> "Ring":
+        """lfg_ring_create: a ring of pinned slots with a copy stream of its own.  Destroy it before the context."""
+        r = _vp()
+        self._check(self.lib.lfg_ring_create(self.h, int(slots), int(slot_bytes), ctypes.byref(r)), "lfg_ring_create")
+        return Ring(self, r, int(slot_bytes))
 
     def mv_export_rgba32f(self, mv: Frame) -> np.ndarray:
         """The reference's rgba32f motion-vector image, vec4(mv.x, mv.y, 0, 1) per pixel, as (H, W, 4) float32."""

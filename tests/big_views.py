@@ -180,7 +180,7 @@ def read_rows(ctx, address, pitch, rows, n, right=0):
     return got[:, :n], got[:, n:n + right]
 
 
-def _hip_runtime():
+def hip_runtime():
     """The HIP runtime that liblinuxfg_hip.so itself runs on, found among the process's mappings.  torch's wheel brings a runtime of
     its own under the same name: where torch was imported first the library is bound to that one, and it is the only one mapped;
     where the library was loaded first, torch's is a second runtime, which finds no GPU in a process that has a context.  So a
@@ -201,7 +201,7 @@ class Arena:
 
     def __init__(self, ctx):
         import ctypes
-        self.hip = _hip_runtime()
+        self.hip = hip_runtime()
         assert self.hip.hipSetDevice(int(ctx.lib.lfg_context_device(ctx.h))) == 0
         free, total = ctypes.c_size_t(), ctypes.c_size_t()
         assert self.hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
