@@ -227,6 +227,11 @@ int  lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint32_t *out_
  * kernel, and how many the frame has; every open segment is listed exactly once (synchronises; reporting and tests only).
  * No reference counterpart: motion.comp (shaders/motion.comp:27-52) has one pass and no work lists. */
 int  lfg_motion_open_segments(lfg_context *ctx, uint32_t *out_open, uint32_t *out_segments);
+/* After a prefiltered lfg_motion: how many entries of the run-time queue its work units asked for -- a unit that holds a whole
+ * tile hands a segment without a match over to the workgroups that run out of units, one entry per four parts of the segment --
+ * and how many entries the queue is laid out for; what does not fit is searched in place.  Zero at frame sizes whose tiles are
+ * all shared between several units (synchronises; reporting and tests only).  No reference counterpart, as above. */
+int  lfg_motion_hand_over_stats(lfg_context *ctx, uint32_t *out_entries_asked, uint32_t *out_entries_room);
 /* With frames in flight (lfg_lanes >= 2) a call whose content suits it sends its whole interior tiles through a lean kernel
  * before the general one (same vectors; the choice goes by the lane's previous call).  After an lfg_motion: whether the selected
  * lane's last call did (1/0), how many tiles are listed for that kernel at this frame size, and in how many it left work to the

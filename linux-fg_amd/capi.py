@@ -153,6 +153,7 @@ SIGNATURES = {
     "lfg_set_motion_mode": (_i, [_vp, _i]),
     "lfg_motion_last_stats": (_i, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_double)]),
     "lfg_motion_open_segments": (_i, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "lfg_motion_hand_over_stats": (_i, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "lfg_motion_lean_stats": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "lfg_motion_strip_stats": (_i, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "lfg_motion_prediction_stats": (_i, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
@@ -586,6 +587,12 @@ class Context:
         """(segments the prefilter left to the resolve kernel, segments of the frame) of the last prefiltered lfg_motion."""
         a, b = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self.lib.lfg_motion_open_segments(self.h, ctypes.byref(a), ctypes.byref(b)), "lfg_motion_open_segments")
+        return a.value, b.value
+
+    def motion_hand_over_stats(self):
+        """(entries of the run-time queue the last prefiltered lfg_motion asked for, entries the queue is laid out for)."""
+        a, b = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self.lib.lfg_motion_hand_over_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "lfg_motion_hand_over_stats")
         return a.value, b.value
 
     def motion_lean_stats(self):

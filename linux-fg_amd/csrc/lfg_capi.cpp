@@ -971,6 +971,23 @@ LFG_EXPORT int lfg_motion_open_segments(lfg_context *ctx, uint32_t *out_open, ui
     return LFG_OK;
 }
 
+// Reporting only: how many entries of the run-time queue the whole tiles of the last lfg_motion asked for -- one per four parts of a
+// segment handed over -- and how many the queue is laid out for (a call whose segments go in four parts uses half of them).  More
+// asked for than there is room: the rest was searched in place.  Zero at frame sizes whose every tile is shared between units
+// (prefilter_plan: fewer tiles than half the slots): only a unit that holds a whole tile hands a segment over.
+LFG_EXPORT int lfg_motion_hand_over_stats(lfg_context *ctx, uint32_t *out_entries_asked, uint32_t *out_entries_room) {
+    if (!ctx) return LFG_ERR_INVALID;
+    lfg_lane_state &cur = ctx->cur();
+    if (!out_entries_asked || !out_entries_room) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_hand_over_stats: NULL argument");
+    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_hand_over_stats: the prefiltered path has not run");
+    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
+    uint32_t asked = 0;
+    LFG_HIP(ctx, hipMemcpy(&asked, cur.motion_ws + cur.motion_ws_layout.queueCount, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *out_entries_asked = asked;
+    *out_entries_room = (uint32_t)cur.motion_ws_layout.queueCap;
+    return LFG_OK;
+}
+
 // Reporting only: did the selected lane's last lfg_motion go through the lean kernel (csrc/motion_lean.hip), how many whole
 // interior tiles are listed for it at this frame size, and in how many of them it left a segment to the persistent kernel.
 LFG_EXPORT int lfg_motion_lean_stats(lfg_context *ctx, int *out_used, uint32_t *out_tiles, uint32_t *out_tiles_left) {
