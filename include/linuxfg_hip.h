@@ -844,6 +844,80 @@ int  lfg_frame_diff(lfg_context *ctx, const lfg_frame *a, const lfg_frame *b, ui
 typedef struct lfg_frame_diff_summary { uint64_t pixels, differing, over_1; uint32_t max_abs, p50, p99; double mse, psnr_db; } lfg_frame_diff_summary;
 int  lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, uint32_t channel_mask, lfg_frame_diff_summary *out);
 
+/* Level matching: what keeps the stages' vectors through a fade, a flash or an exposure change, where a piece of content no
+ * longer has the same byte values in prev and curr.  Three device calls and one switch; none has a reference counterpart.
+ * Integer arithmetic only; every result is exact and depends on no setting of the context (the switch apart).
+ *
+ * The histogram of a frame that lives on the device.  No reference counterpart.
+ *   Input: frame RGBA8, W x H.  pixels = W * H;  hist[c][k] = the number of pixels whose byte c equals k, for all four channels.
+ *   accumulate = 0: the call WRITES the 1,025 words of `device_stats` (8,200 bytes of device memory, 8-byte aligned);
+ *   accumulate = 1: the call ADDS to them, pixels included: several frames go into one record with no host wait between them.
+ * Frames: as lfg_frame_diff's -- 4-byte aligned RGBA8 rows (any pitch that is a multiple of 4); a view made with
+ * lfg_frame_wrap into a larger frame is a region of interest; row padding is never read into a count.  A NULL pointer, a wrong
+ * format, a misaligned frame or record or any other value of accumulate returns LFG_ERR_INVALID before anything is enqueued.
+ * Enqueued on the selected lane (a clear of the record unless accumulate is 1, one launch of a fixed grid); keeps no device
+ * memory; outside the stage timers. */
+typedef struct lfg_frame_histogram_stats { uint64_t pixels; uint64_t hist[4][256]; } lfg_frame_histogram_stats;   /* 8,200 bytes */
+int  lfg_frame_histogram(lfg_context *ctx, const lfg_frame *frame, int accumulate,
+                         void *device_stats /* 8,200 bytes of device memory, 8-byte aligned */);
+/* A pair of monotone level maps from two histogram records, built ON THE DEVICE: the host never waits for a histogram.  No
+ * reference counterpart.  A is the record at `device_hist_from`, B the one at `device_hist_to` (both as lfg_frame_histogram
+ * writes them; they may be the same record); cdfX[c][v] = the sum of histX[c][u] over u <= v.  For c = 0, 1, 2 (alpha has no map):
+ *   forward[c][v] = the smallest w with cdfB[c][w] >= cdfA[c][v]: a level of A to B's level of equal rank;
+ *   inverse[c][w] = the smallest v with cdfA[c][v] >= cdfB[c][w];
+ *       (255 where no such level exists, which only records of unequal counts can ask for)
+ *   shift_sum = the sum over c < 3 and v of histA[c][v] * |forward[c][v] - v|;   pixels = A's pixels;   reserved = 0;
+ *   active = 1 when A's and B's pixels are equal and non-zero and 16 * shift_sum >= (uint64_t)min_shift16 * 3 * pixels, in
+ *       64 bits; otherwise active = 0 and BOTH maps are written as the identity (shift_sum stays what the rule gave).
+ * min_shift16 is the mean level shift that makes a pair worth levelling, in sixteenths of a level, 0 .. 4080: 0 levels every
+ * pair of equal size; a larger value leaves pairs alone whose histograms merely differ because content entered or left.
+ * `device_map` is 1,560 bytes of device memory, 8-byte aligned, overlapping neither record.  A NULL or misaligned pointer or a
+ * min_shift16 outside 0 .. 4080 returns LFG_ERR_INVALID before anything is enqueued.  One launch of one workgroup on the
+ * selected lane; keeps no device memory; outside the stage timers. */
+typedef struct lfg_levels_map { uint64_t pixels, shift_sum; uint32_t active, reserved;
+                                uint8_t forward[3][256], inverse[3][256]; } lfg_levels_map;                        /* 1,560 bytes */
+int  lfg_levels_match(lfg_context *ctx, const void *device_hist_from, const void *device_hist_to,
+                      int min_shift16, void *device_map /* 1,560 bytes of device memory, 8-byte aligned */);
+/* A map through every pixel of a frame.  No reference counterpart.  `device_map` is a map as lfg_levels_match writes it, read on
+ * the device when the call's turn on the lane comes.
+ *   LFG_LEVELS_FORWARD: out_c = forward[c][in_c] for c < 3; alpha is copied; `factor` is ignored.
+ *   LFG_LEVELS_AT: tq = (int)floorf(factor * 256.0f + 0.5f), factor finite in [0, 1];
+ *       out_c = ((256 - tq) * inverse[c][in_c] + tq * in_c + 128) >> 8 for c < 3; alpha is copied.  So factor 1 leaves a frame
+ *       as it is and factor 0 takes a frame at B's levels back to A's: a frame generated between a levelled prev and curr, which
+ *       is at curr's levels, is taken to the levels of its own time.
+ * An inactive map gives a byte copy in both modes.  in and out RGBA8 of one size, 4-byte aligned rows; `out` may be `in`
+ * itself (the pass is point-wise) and may overlap it in no other way.  Only the width * 4 bytes of a row are written.  Any
+ * violation, a NULL pointer, another mode or (under LFG_LEVELS_AT) a factor outside [0, 1] returns LFG_ERR_INVALID before
+ * anything is enqueued.  One launch on the selected lane; keeps no device memory; outside the stage timers. */
+typedef enum lfg_levels_mode { LFG_LEVELS_FORWARD = 0, LFG_LEVELS_AT = 1 } lfg_levels_mode;
+int  lfg_levels_apply(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, const void *device_map, int mode, float factor);
+/* Level matching in lfg_interpolate_frames and lfg_interpolate_frames_multi (nothing else).  No reference counterpart.
+ *   min_shift16 = -1 (default): off; every path enqueues and allocates what it always did;
+ *   0 .. 4080: a call, in this order,
+ *     1. checks every argument that a later step can refuse -- lfg_cut_fallback's rules for the frames, and every factor a
+ *        finite number in [0, 1], on the shader route too --: LFG_ERR_INVALID with nothing enqueued;
+ *     2. enqueues lfg_frame_histogram of prev and of curr into two records the lane owns, lfg_levels_match(prev's, curr's,
+ *        min_shift16) into a map the lane owns, and lfg_levels_apply(LFG_LEVELS_FORWARD) from prev into prev', an RGBA8
+ *        temporary of the lane (W x H, pitch 4 W, made again when the size changes);
+ *     3. runs exactly as with the switch off and prev' in prev's place: the selected estimator, halving, refinement, sub-pixel
+ *        vectors, the static mask, the backward field, lfg_pair_match and the selected interpolator or extrapolator all see
+ *        prev'.  lfg_set_fused_motion_interpolate does not apply: the stages run;
+ *     4. under LFG_GENERATION_INTERPOLATE takes every outs[i] through lfg_levels_apply(LFG_LEVELS_AT, factors[i]) in place;
+ *        under LFG_GENERATION_EXTRAPOLATE with the compensated interpolator nothing: those frames are fetched from curr alone;
+ *     5. with lfg_set_cut_detection on runs lfg_cut_fallback last, with the CALLER's prev and curr: a cut still gives byte
+ *        copies of the caller's frames;
+ *     6. copies the map's first three words (pixels, shift_sum, active and reserved) into pinned host memory with an event
+ *        behind the copy.
+ * So an inactive pair gives the bytes of the same call with the switch off, factor 1 still gives curr, and the setting
+ * composes with every other one by substitution.  Per lane it keeps 4 W H + 2 * 8,200 + 1,560 bytes and the pinned words,
+ * made by the lane's first such call and freed with the lane.  Any other value: LFG_ERR_INVALID and no change.
+ * lfg_last_level_match: those words of the SELECTED lane's last such call (any pointer may be NULL).  It waits for that
+ * copy's event only and returns LFG_ERR_INVALID if the lane has made no such call.
+ * Known limit: the maps are global.  A HUD that does not fade while the scene does is levelled with the scene, and under
+ * lfg_set_static_protection such a pixel is no longer equal in prev' and curr. */
+int  lfg_set_level_matching(lfg_context *ctx, int min_shift16);      /* -1 (default): off; 0 .. 4080 */
+int  lfg_last_level_match(lfg_context *ctx, uint64_t *out_shift_sum, uint64_t *out_pixels, int *out_active);
+
 /* Structural similarity: an exact-integer SSIM of two frames that live on the device, beside lfg_frame_diff's squared error.
  * No reference counterpart.  Integer arithmetic only; it depends on no setting of the context.  The window layout and the
  * constants are those of the integer SSIM of x264 and of FFmpeg's ssim filter; those finish in float, this one in integers, so

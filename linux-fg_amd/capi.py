@@ -87,6 +87,21 @@ class FrameDiffSummary(ctypes.Structure):
         return {name: (float if name in ("mse", "psnr_db") else int)(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FrameHistogramStats(ctypes.Structure):
+    """struct lfg_frame_histogram_stats."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("hist", (ctypes.c_uint64 * 256) * 4)]
+
+
+class LevelsMap(ctypes.Structure):
+    """struct lfg_levels_map."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("shift_sum", ctypes.c_uint64), ("active", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("forward", (ctypes.c_uint8 * 256) * 3), ("inverse", (ctypes.c_uint8 * 256) * 3)]
+
+
+LEVELS_FORWARD, LEVELS_AT = 0, 1
+LEVELS_MAX_SHIFT16 = 4080
+
+
 class FrameSsimStats(ctypes.Structure):
     """struct lfg_frame_ssim_stats."""
     _fields_ = [("windows", ctypes.c_uint64), ("sum", ctypes.c_int64 * 4), ("hist", ctypes.c_uint64 * 65), ("worst", ctypes.c_uint64)]
@@ -205,6 +220,11 @@ SIGNATURES = {
     "lfg_last_pair_stats": (_i, [_vp, ctypes.POINTER(PairStats), ctypes.POINTER(_i)]),
     "lfg_frame_diff": (_i, [_vp, _FP, _FP, _u32, _i, _vp]),
     "lfg_frame_diff_summarize": (_i, [ctypes.POINTER(FrameDiffStats), _u32, ctypes.POINTER(FrameDiffSummary)]),
+    "lfg_frame_histogram": (_i, [_vp, _FP, _i, _vp]),
+    "lfg_levels_match": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "lfg_levels_apply": (_i, [_vp, _FP, _FP, _vp, _i, ctypes.c_float]),
+    "lfg_set_level_matching": (_i, [_vp, _i]),
+    "lfg_last_level_match": (_i, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_i)]),
     "lfg_frame_ssim": (_i, [_vp, _FP, _FP, _u32, _i, _vp]),
     "lfg_frame_ssim_summarize": (_i, [ctypes.POINTER(FrameSsimStats), _u32, ctypes.POINTER(FrameSsimSummary)]),
     "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
@@ -911,6 +931,60 @@ class Context:
         """(pixels, sse tuple, hist tuple) of a record in device memory; waits for the context."""
         words = [int(v) for v in self.download(record).reshape(-1).view(np.uint64)]
         return words[0], tuple(words[1:5]), tuple(words[5:])
+
+    # -- level matching.  A histogram record is 8,200 bytes of device memory and a map 1,560: here 2,050 x 1 and 390 x 1 RGBA8
+    # frames, as the records above.
+    def create_histogram_record(self) -> Frame:
+        return self.create_frame(ctypes.sizeof(FrameHistogramStats) // 4, 1)
+
+    def write_histogram_record(self, record: Frame, pixels: int, hist):
+        """`hist` is 4 x 256 counts."""
+        words = np.concatenate([np.array([pixels], np.uint64), np.asarray(hist, np.uint64).reshape(-1)])
+        self.upload(record, words.view(np.uint8).reshape(1, -1, 4))
+
+    def read_histogram_record(self, record: Frame):
+        """(pixels, hist as a 4 x 256 uint64 array) of a record in device memory; waits for the context."""
+        words = self.download(record).reshape(-1).view(np.uint64)
+        return int(words[0]), words[1:].reshape(4, 256).copy()
+
+    def frame_histogram(self, f: Frame, record: Frame, accumulate: bool = False):
+        """Per-channel histogram of a frame (lfg_frame_histogram), written into `record` (create_histogram_record) or added to it."""
+        self._check(self.lib.lfg_frame_histogram(self.h, ctypes.byref(f), int(accumulate), _vp(record.data)), "lfg_frame_histogram")
+
+    def create_levels_map(self) -> Frame:
+        return self.create_frame(ctypes.sizeof(LevelsMap) // 4, 1)
+
+    def levels_match(self, hist_from: Frame, hist_to: Frame, level_map: Frame, min_shift16: int = 0):
+        """The pair of level maps that carries `hist_from`'s levels to `hist_to`'s of equal rank and back (lfg_levels_match),
+        built on the device into `level_map` (create_levels_map)."""
+        self._check(self.lib.lfg_levels_match(self.h, _vp(hist_from.data), _vp(hist_to.data), int(min_shift16), _vp(level_map.data)),
+                    "lfg_levels_match")
+
+    def read_levels_map(self, level_map: Frame) -> dict:
+        """A map in device memory as a dict of pixels, shift_sum, active, reserved and the 3 x 256 forward and inverse tables;
+        waits for the context."""
+        raw = self.download(level_map).reshape(-1)
+        head = raw[:24]
+        return {"pixels": int(head[:8].view(np.uint64)[0]), "shift_sum": int(head[8:16].view(np.uint64)[0]),
+                "active": int(head[16:20].view(np.uint32)[0]), "reserved": int(head[20:24].view(np.uint32)[0]),
+                "forward": raw[24:24 + 768].reshape(3, 256).copy(), "inverse": raw[24 + 768:24 + 1536].reshape(3, 256).copy()}
+
+    def levels_apply(self, src: Frame, dst: Frame, level_map: Frame, mode: int = LEVELS_FORWARD, factor: float = 0.0):
+        """A map through every pixel (lfg_levels_apply): LEVELS_FORWARD, or LEVELS_AT with the frame's time in [0, 1].  `dst` may
+        be `src`."""
+        self._check(self.lib.lfg_levels_apply(self.h, ctypes.byref(src), ctypes.byref(dst), _vp(level_map.data), int(mode),
+                                              ctypes.c_float(factor)), "lfg_levels_apply")
+
+    def set_level_matching(self, min_shift16: int):
+        """-1 (default: off) or 0..4080: interpolate_frames[_multi] level prev onto curr before every stage where the pair's
+        histograms are a mean of min_shift16 / 16 levels apart, and take the generated frames to the levels of their time."""
+        self._check(self.lib.lfg_set_level_matching(self.h, int(min_shift16)), "lfg_set_level_matching")
+
+    def last_level_match(self):
+        """(shift_sum, pixels, active) of the selected lane's last call with level matching on (lfg_last_level_match)."""
+        s, p, a = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        self._check(self.lib.lfg_last_level_match(self.h, ctypes.byref(s), ctypes.byref(p), ctypes.byref(a)), "lfg_last_level_match")
+        return int(s.value), int(p.value), bool(a.value)
 
     # -- structural similarity.  A record is 568 bytes of device memory: here a 142 x 1 RGBA8 frame.
     def create_ssim_record(self) -> Frame:

@@ -3,6 +3,7 @@
 // There is no CPU fallback anywhere: every entry point needs a live HIP device.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "lfg_bicubic.hpp"
 #include "lfg_internal.hpp"
+#include "lfg_levels.hpp"
 
 #define LFG_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -144,7 +146,7 @@ hipError_t sync_lanes(lfg_context *ctx) {
     return e;
 }
 
-// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, half_prev, half_curr, mv_half, mvq_tmp, mid_tmp), at this size: kept while the size stays, made again when it
+// A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, half_prev, half_curr, mv_half, mvq_tmp, mid_tmp, levelled_prev), at this size: kept while the size stays, made again when it
 // changes.  The test comes first because lfg_frame_destroy waits for every lane.  (frame_manager.cpp:226-230)
 int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, uint32_t format) {
     if (f.data && f.width == width && f.height == height) return LFG_OK;
@@ -488,7 +490,7 @@ namespace {
 void lane_release(lfg_lane_state &l) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
-    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.half_prev, &l.half_curr, &l.mv_half, &l.mvq_tmp, &l.mid_tmp})      // (lane_frame)
+    for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.half_prev, &l.half_curr, &l.mv_half, &l.mvq_tmp, &l.mid_tmp, &l.levelled_prev})      // (lane_frame)
         if (f->data && f->owned) (void)hipFree(f->data);
     if (l.motion_ws) (void)hipFree(l.motion_ws);
     if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
@@ -502,6 +504,9 @@ void lane_release(lfg_lane_state &l) {
     if (l.cut.event) (void)hipEventDestroy(l.cut.event);
     if (l.cut.pinned) (void)hipHostFree(l.cut.pinned);
     if (l.cut.device) (void)hipFree(l.cut.device);
+    if (l.levels.event) (void)hipEventDestroy(l.levels.event);
+    if (l.levels.pinned) (void)hipHostFree(l.levels.pinned);
+    if (l.levels.device) (void)hipFree(l.levels.device);
     if (l.own_stream) (void)hipStreamDestroy(l.own_stream);
     l = lfg_lane_state{};
 }
@@ -1218,19 +1223,25 @@ int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
                        lfg_frame *const *outs, const float *factors, uint32_t count, bool multi);
 int cut_fallback_enqueue(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const void *device_stats,
                          int min_matched_permille, lfg_frame *const *outs, const float *factors, uint32_t count);
+bool frames_overlap(const lfg_frame *a, const lfg_frame *b);
 
 // lfg_interpolate_frames[_multi] with lfg_set_cut_detection on: the vectors, their match statistics into the lane's record
 // (and a copy of it on its way to the host, for lfg_last_pair_stats), the selected interpolator, then the fallback, which
 // reads the record on the device.  Everything that can fail on an argument is checked before the first launch.
+// With lfg_set_level_matching on as well, `prev` is the lane's levelled prev', `shown` the caller's prev -- what the checks
+// look at and what a cut shows -- and `level_map` the lane's map, which takes every interpolated output to the levels of its
+// time before the fallback runs; otherwise shown is prev and level_map NULL.
+int levels_at_outputs(lfg_context *ctx, const void *level_map, lfg_frame *const *outs, const float *factors, uint32_t count);
+
 int detecting_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame *const *outs, const float *factors,
-                     uint32_t count, bool multi) {
+                     uint32_t count, bool multi, const lfg_frame *shown, const void *level_map) {
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     lfg::CutDetectState &cut = ctx->cur().cut;
     if (!cut.device) LFG_HIP(ctx, hipMalloc((void **)&cut.device, sizeof(lfg_pair_stats)));
     if (!cut.pinned) LFG_HIP(ctx, hipHostMalloc((void **)&cut.pinned, sizeof(lfg_pair_stats), hipHostMallocDefault));
     if (!cut.event) LFG_HIP(ctx, hipEventCreateWithFlags(&cut.event, hipEventDisableTiming));
     const int permille = ctx->cut_permille;
-    int rc = cut_fallback_check(ctx, prev, curr, cut.device, permille, outs, factors, count);
+    int rc = cut_fallback_check(ctx, shown, curr, cut.device, permille, outs, factors, count);
     if (rc != LFG_OK) return rc;
     const lfg_frame *vectors = nullptr;
     rc = frame_vectors(ctx, prev, curr, &vectors);
@@ -1250,9 +1261,83 @@ int detecting_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *c
     if (ctx->generation == LFG_GENERATION_EXTRAPOLATE && ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {
         float newest[LFG_MAX_FACTORS];                            // a cut repeats the newest frame: curr for every output
         for (uint32_t i = 0; i < count; ++i) newest[i] = 1.0f;
-        return cut_fallback_enqueue(ctx, prev, curr, cut.device, permille, outs, newest, count);
+        return cut_fallback_enqueue(ctx, shown, curr, cut.device, permille, outs, newest, count);
     }
-    return cut_fallback_enqueue(ctx, prev, curr, cut.device, permille, outs, factors, count);
+    if (level_map) {
+        rc = levels_at_outputs(ctx, level_map, outs, factors, count);
+        if (rc != LFG_OK) return rc;
+    }
+    return cut_fallback_enqueue(ctx, shown, curr, cut.device, permille, outs, factors, count);
+}
+
+// What lfg_interpolate_frames[_multi] run where neither cut detection nor the fused kernels apply: the vectors, then the
+// selected interpolator.
+int staged_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame *const *outs, const float *factors,
+                  uint32_t count, bool multi) {
+    const lfg_frame *vectors = nullptr;
+    int rc = frame_vectors(ctx, prev, curr, &vectors);
+    if (rc != LFG_OK) return rc;
+    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) return compensated_frames(ctx, prev, curr, vectors, outs, factors, count, multi);
+    return multi ? lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count)
+                 : lfg_interpolate(ctx, prev, curr, vectors, outs[0], factors[0]);
+}
+
+// lfg_interpolate_frames[_multi] with lfg_set_level_matching on (include/linuxfg_hip.h has the six steps): everything that can
+// fail on an argument is checked before the first launch -- lfg_cut_fallback's rules are the strictest any stage has for the
+// frames, the compensated calls' the strictest for the factors -- then prev is levelled into the lane's prev', the call runs on
+// prev' as it would have run on prev, and the interpolated outputs go to the levels of their own time.
+int levelled_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, lfg_frame *const *outs, const float *factors,
+                    uint32_t count, bool multi) {
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    const char *name = multi ? "lfg_interpolate_frames_multi" : "lfg_interpolate_frames";
+    const std::string n(name);
+    if (!outs || !factors || count == 0 || count > LFG_MAX_FACTORS)
+        return fail(ctx, LFG_ERR_INVALID, n + ": count must be in [1, LFG_MAX_FACTORS] and outs/factors non-NULL");
+    if (!frame_ok(prev, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !same_size(prev, curr))
+        return fail(ctx, LFG_ERR_INVALID, n + ": prev and curr must be non-empty RGBA8 frames of one size");
+    if ((prev->pitch | curr->pitch) % 4u || ((uintptr_t)prev->data | (uintptr_t)curr->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, n + ": RGBA8 frames must be 4-byte aligned");
+    for (uint32_t i = 0; i < count; ++i) {
+        const lfg_frame *o = outs[i];
+        if (!frame_ok(o, LFG_FORMAT_RGBA8_UNORM) || !same_size(curr, o) || o->pitch % 4u || (uintptr_t)o->data % 4u)
+            return fail(ctx, LFG_ERR_INVALID, n + ": bad output frame (NULL, empty, wrong format, size or alignment)");
+        if (!std::isfinite(factors[i]) || factors[i] < 0.0f || factors[i] > 1.0f)
+            return fail(ctx, LFG_ERR_INVALID, n + ": with level matching on every factor must be a finite number in [0, 1]");
+        if (frames_overlap(o, prev) || frames_overlap(o, curr)) return fail(ctx, LFG_ERR_INVALID, n + ": an output overlaps an input");
+        for (uint32_t j = 0; j < i; ++j)
+            if (frames_overlap(outs[j], o)) return fail(ctx, LFG_ERR_INVALID, n + ": two outputs overlap each other");
+    }
+    lfg_lane_state &cur = ctx->cur();
+    lfg::LevelMatchState &lv = cur.levels;
+    constexpr size_t kRecord = sizeof(lfg_frame_histogram_stats), kHead = 3 * sizeof(uint64_t);
+    if (!lv.device) LFG_HIP(ctx, hipMalloc((void **)&lv.device, 2 * kRecord + sizeof(lfg_levels_map)));
+    if (!lv.pinned) LFG_HIP(ctx, hipHostMalloc((void **)&lv.pinned, kHead, hipHostMallocDefault));
+    if (!lv.event) LFG_HIP(ctx, hipEventCreateWithFlags(&lv.event, hipEventDisableTiming));
+    int rc = lane_frame(ctx, cur.levelled_prev, curr->width, curr->height, LFG_FORMAT_RGBA8_UNORM);
+    if (rc != LFG_OK) return fail(ctx, rc, "Failed to create the levelled frame");
+    void *const from = lv.device, *const to = lv.device + kRecord, *const map = lv.device + 2 * kRecord;
+    rc = lfg_frame_histogram(ctx, prev, 0, from);
+    if (rc == LFG_OK) rc = lfg_frame_histogram(ctx, curr, 0, to);
+    if (rc == LFG_OK) rc = lfg_levels_match(ctx, from, to, ctx->level_shift16, map);
+    if (rc == LFG_OK) rc = lfg_levels_apply(ctx, prev, &cur.levelled_prev, map, LFG_LEVELS_FORWARD, 0.0f);
+    if (rc != LFG_OK) return rc;
+    LFG_HIP(ctx, hipMemcpyAsync(lv.pinned, map, kHead, hipMemcpyDeviceToHost, cur.stream));
+    LFG_HIP(ctx, hipEventRecord(lv.event, cur.stream));
+    lv.recorded = true;
+    const lfg_frame *levelled = &cur.levelled_prev;
+    if (ctx->cut_permille >= 0) return detecting_frames(ctx, levelled, curr, outs, factors, count, multi, prev, map);
+    rc = staged_frames(ctx, levelled, curr, outs, factors, count, multi);
+    if (rc != LFG_OK) return rc;
+    if (ctx->generation == LFG_GENERATION_EXTRAPOLATE && ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) return LFG_OK;
+    return levels_at_outputs(ctx, map, outs, factors, count);
+}
+
+int levels_at_outputs(lfg_context *ctx, const void *level_map, lfg_frame *const *outs, const float *factors, uint32_t count) {
+    for (uint32_t i = 0; i < count; ++i) {
+        const int rc = lfg_levels_apply(ctx, outs[i], outs[i], level_map, LFG_LEVELS_AT, factors[i]);
+        if (rc != LFG_OK) return rc;
+    }
+    return LFG_OK;
 }
 
 }  // namespace
@@ -1262,9 +1347,13 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
     if (!ctx || !curr) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: NULL argument");
     if (pitch_too_large(prev) || pitch_too_large(curr) || pitch_too_large(out))     // before the lane's temporaries are made
         return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames: a pitch above 0x7fffffff");
+    if (ctx->level_shift16 >= 0) {
+        lfg_frame *const outs[1] = {out};
+        return levelled_frames(ctx, prev, curr, outs, &factor, 1, false);
+    }
     if (ctx->cut_permille >= 0) {
         lfg_frame *const outs[1] = {out};
-        return detecting_frames(ctx, prev, curr, outs, &factor, 1, false);
+        return detecting_frames(ctx, prev, curr, outs, &factor, 1, false, prev, nullptr);
     }
     // The fused motion kernels are the full search's and write the shader's interpolation: every other setting takes the stages.
     if (ctx->fuse_motion_interpolate && ctx->estimator == LFG_ESTIMATOR_FULL_SEARCH && ctx->refine_radius < 0 &&
@@ -1286,14 +1375,8 @@ LFG_EXPORT int lfg_interpolate_frames(lfg_context *ctx, const lfg_frame *prev, c
         if (rc != LFG_OK || done) return rc;
         return lfg_interpolate(ctx, prev, curr, &mv, out, factor);     // (the generic kernel ran: it wrote the vectors)
     }
-    const lfg_frame *vectors = nullptr;
-    int rc = frame_vectors(ctx, prev, curr, &vectors);
-    if (rc != LFG_OK) return rc;
-    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) {
-        lfg_frame *const outs[1] = {out};
-        return compensated_frames(ctx, prev, curr, vectors, outs, &factor, 1, false);
-    }
-    return lfg_interpolate(ctx, prev, curr, vectors, out, factor);
+    lfg_frame *const outs[1] = {out};
+    return staged_frames(ctx, prev, curr, outs, &factor, 1, false);
 }
 
 LFG_EXPORT int lfg_interpolate_multi(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *curr, const lfg_frame *mv,
@@ -1332,12 +1415,9 @@ LFG_EXPORT int lfg_interpolate_frames_multi(lfg_context *ctx, const lfg_frame *p
     bool too_large = pitch_too_large(prev) || pitch_too_large(curr);                // before the lane's temporaries are made
     for (uint32_t i = 0; outs && count <= LFG_MAX_FACTORS && i < count; ++i) too_large = too_large || pitch_too_large(outs[i]);
     if (too_large) return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_frames_multi: a pitch above 0x7fffffff");
-    if (ctx->cut_permille >= 0) return detecting_frames(ctx, prev, curr, outs, factors, count, true);
-    const lfg_frame *vectors = nullptr;
-    int rc = frame_vectors(ctx, prev, curr, &vectors);
-    if (rc != LFG_OK) return rc;
-    if (ctx->interpolator == LFG_INTERPOLATOR_COMPENSATED) return compensated_frames(ctx, prev, curr, vectors, outs, factors, count, true);
-    return lfg_interpolate_multi(ctx, prev, curr, vectors, outs, factors, count);
+    if (ctx->level_shift16 >= 0) return levelled_frames(ctx, prev, curr, outs, factors, count, true);
+    if (ctx->cut_permille >= 0) return detecting_frames(ctx, prev, curr, outs, factors, count, true, prev, nullptr);
+    return staged_frames(ctx, prev, curr, outs, factors, count, true);
 }
 
 // ---- motion-compensated interpolation (interpolate_mc.hip)
@@ -1957,6 +2037,84 @@ LFG_EXPORT int lfg_frame_diff_summarize(const lfg_frame_diff_stats *host_stats, 
     s.mse = sum / ((double)channels * (double)pixels);
     s.psnr_db = s.mse > 0.0 ? 10.0 * std::log10(65025.0 / s.mse) : HUGE_VAL;
     *out = s;
+    return LFG_OK;
+}
+
+// ---- level matching (levels.hip)
+
+static_assert(sizeof(lfg_frame_histogram_stats) == lfg::kHistWords * 8 && sizeof(lfg_levels_map) == lfg::kMapBytes &&
+              offsetof(lfg_levels_map, forward) == lfg::kMapHeadBytes, "lfg_levels.hpp lays the records out as the header declares them");
+
+LFG_EXPORT int lfg_frame_histogram(lfg_context *ctx, const lfg_frame *frame, int accumulate, void *device_stats) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(frame, LFG_FORMAT_RGBA8_UNORM)) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_histogram: frame must be non-empty RGBA8");
+    if (frame->pitch % 4u || (uintptr_t)frame->data % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_histogram: RGBA8 frames must be 4-byte aligned");
+    if (accumulate != 0 && accumulate != 1) return fail(ctx, LFG_ERR_INVALID, "lfg_frame_histogram: accumulate must be 0 or 1");
+    if (!device_stats || (uintptr_t)device_stats % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_frame_histogram: device_stats must be non-NULL and 8-byte aligned");
+    hipError_t e = lfg::launch_frame_histogram(ctx->cur().stream, *frame, accumulate == 1, ctx->device_cus, device_stats);
+    if (e != hipSuccess) return fail_hip(ctx, e, "frame histogram kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_levels_match(lfg_context *ctx, const void *device_hist_from, const void *device_hist_to, int min_shift16,
+                                void *device_map) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!device_hist_from || !device_hist_to || !device_map ||
+        ((uintptr_t)device_hist_from | (uintptr_t)device_hist_to | (uintptr_t)device_map) % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_match: both records and the map must be non-NULL and 8-byte aligned");
+    if (min_shift16 < 0 || min_shift16 > lfg::kLevelsMaxShift16)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_match: min_shift16 must be in [0, 4080]");
+    const uintptr_t m0 = (uintptr_t)device_map, m1 = m0 + sizeof(lfg_levels_map);
+    for (const void *h : {device_hist_from, device_hist_to})
+        if ((uintptr_t)h < m1 && m0 < (uintptr_t)h + sizeof(lfg_frame_histogram_stats))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_levels_match: the map overlaps a record");
+    hipError_t e = lfg::launch_levels_match(ctx->cur().stream, device_hist_from, device_hist_to, min_shift16, device_map);
+    if (e != hipSuccess) return fail_hip(ctx, e, "levels match kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_levels_apply(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, const void *device_map, int mode, float factor) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: in and out must be non-empty RGBA8");
+    if (!same_size(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: in and out differ in size");
+    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: RGBA8 frames must be 4-byte aligned");
+    if (!(in->data == out->data && in->pitch == out->pitch) && frames_overlap(in, out))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: out overlaps in without being in itself");
+    if (!device_map || (uintptr_t)device_map % 8u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: device_map must be non-NULL and 8-byte aligned");
+    if (mode != LFG_LEVELS_FORWARD && mode != LFG_LEVELS_AT) return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: mode must be LFG_LEVELS_FORWARD or LFG_LEVELS_AT");
+    if (mode == LFG_LEVELS_AT && (!std::isfinite(factor) || factor < 0.0f || factor > 1.0f))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_levels_apply: under LFG_LEVELS_AT the factor must be a finite number in [0, 1]");
+    const int tq = mode == LFG_LEVELS_AT ? lfg::levels_tq(factor) : 0;
+    hipError_t e = lfg::launch_levels_apply(ctx->cur().stream, *in, *out, device_map, mode, tq);
+    if (e != hipSuccess) return fail_hip(ctx, e, "levels apply kernel launch");
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_set_level_matching(lfg_context *ctx, int min_shift16) {
+    if (!ctx) return LFG_ERR_INVALID;
+    if (min_shift16 < -1 || min_shift16 > lfg::kLevelsMaxShift16)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_set_level_matching: min_shift16 must be -1 (off) or in [0, 4080]");
+    ctx->level_shift16 = min_shift16;
+    return LFG_OK;
+}
+
+LFG_EXPORT int lfg_last_level_match(lfg_context *ctx, uint64_t *out_shift_sum, uint64_t *out_pixels, int *out_active) {
+    if (!ctx) return LFG_ERR_INVALID;
+    const lfg::LevelMatchState &lv = ctx->cur().levels;
+    if (!lv.recorded) return fail(ctx, LFG_ERR_INVALID, "lfg_last_level_match: the selected lane has made no call with level matching on");
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    LFG_HIP(ctx, hipEventSynchronize(lv.event));
+    if (out_pixels) *out_pixels = lv.pinned[0];
+    if (out_shift_sum) *out_shift_sum = lv.pinned[1];
+    if (out_active) *out_active = (uint32_t)lv.pinned[2] != 0u ? 1 : 0;
     return LFG_OK;
 }
 

@@ -185,6 +185,16 @@ struct CutDetectState {
     int permille = -1;                         // the threshold that call ran with
 };
 
+// Level matching behind lfg_interpolate_frames[_multi] (lfg_set_level_matching): both frames' histogram records and the map on
+// the device (one allocation: from | to | map), the pinned copy of the map's first three words that each such call refreshes,
+// and the event behind that copy.  Made by the lane's first such call.
+struct LevelMatchState {
+    uint8_t *device = nullptr;                 // 2 x lfg_frame_histogram_stats, then the lfg_levels_map
+    uint64_t *pinned = nullptr;                // pixels, shift_sum, (active, reserved) (lfg_last_level_match)
+    hipEvent_t event = nullptr;                // recorded behind the copy
+    bool recorded = false;                     // the lane has made a levelling call
+};
+
 }  // namespace lfg
 
 // What a lane (lfg_lanes: one of several frames in flight on a GPU) owns apart from the context: its stream, the temporaries
@@ -223,6 +233,8 @@ struct lfg_lane_state {
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
     lfg::CutDetectState cut;                   // lfg_set_cut_detection: the record of the lane's last detecting call
+    lfg::LevelMatchState levels;               // lfg_set_level_matching: the records and the map of the lane's last levelling call
+    lfg_frame levelled_prev{};                 // ... and prev at curr's levels, made on demand
 };
 
 struct lfg_context {
@@ -258,6 +270,7 @@ struct lfg_context {
     int hole_reach = -1;                       // the compensated, masked and bidirectional calls: the fill plane's reach, -1 = off: the walk (lfg_set_hole_reach)
     int half_res_radius = -1;                  // lfg_interpolate_frames[_multi]: lfg_motion_expand's radius, -1 = off (lfg_set_half_resolution_motion)
     int subpel_radius = -1;                    // lfg_interpolate_frames[_multi]: lfg_motion_subpel's radius, -1 = off (lfg_set_subpixel_vectors)
+    int level_shift16 = -1;                    // lfg_interpolate_frames[_multi]: lfg_levels_match's threshold, -1 = off (lfg_set_level_matching)
     int sampling = 0;                          // lfg_interpolate_frames[_multi]: LFG_SAMPLING_BILINEAR / _BICUBIC where the plain or sub-pixel kind runs (lfg_set_sampling)
     uint32_t *motion_tables = nullptr;         // device: [semantics][rank2scan | order32 | entryOfScan], then baseScan
     bool fuse_interpolate_scale = false;       // lfg_interpolate_scale: one fused kernel instead of the two stages (measured slower)
@@ -418,6 +431,12 @@ hipError_t launch_cut_fallback(hipStream_t s, const lfg_frame &prev, const lfg_f
 // that adds the pair's sums and histogram to it; 16-byte loads where base and pitch of both frames allow, dword loads otherwise.
 hipError_t launch_frame_diff(hipStream_t s, const lfg_frame &a, const lfg_frame &b, uint32_t channelMask, bool accumulate,
                              int deviceCus, void *stats);
+// Level matching (levels.hip): launch_frame_histogram clears the 8,200-byte record `stats` unless `accumulate`, then enqueues the
+// fixed grid that fills it; launch_levels_match one workgroup that writes the 1,560-byte map; launch_levels_apply the map through
+// `in` into `out` (tq: LFG_LEVELS_AT's factor in 256ths, lfg_levels.hpp).
+hipError_t launch_frame_histogram(hipStream_t s, const lfg_frame &frame, bool accumulate, int deviceCus, void *stats);
+hipError_t launch_levels_match(hipStream_t s, const void *from, const void *to, int minShift16, void *map);
+hipError_t launch_levels_apply(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const void *map, int mode, int tq);
 // Structural similarity (frame_ssim.hip): clears the 568-byte record `stats` (zeros, `worst` all ones) unless `accumulate`, then
 // enqueues the fixed grid that adds the pair's windows to it; 16-byte loads where base and pitch of both frames allow, dword
 // loads otherwise.  The frames are at least 8 x 8.
