@@ -67,9 +67,28 @@ float lanczos_ref(float x) {                                   // scale.comp:16-
     return 3.0f * s1 * s2 / (px * px);
 }
 
-int build_axis_table(lfg_context *ctx, int in_size, int out_size, lfg::AxisTable **out) {
-    for (auto &t : ctx->tables)
-        if (t.in_size == in_size && t.out_size == out_size) { *out = &t; return LFG_OK; }
+// Everything the context has enqueued, on every lane (a resource shared by the lanes is about to go or to be read).
+hipError_t sync_lanes(lfg_context *ctx) {
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < ctx->lanes.size() && e == hipSuccess; ++k) e = hipStreamSynchronize(ctx->from_selected(k).stream);
+    return e;
+}
+
+// The one place that allocates and fills a device table (lfg_table_cache.hpp: upload): `what` names it in the error.
+int upload_table(lfg_context *ctx, const void *host, size_t bytes, const char *what, uint8_t **out) {
+    const lfg::DeviceStatus s = lfg::upload<lfg::HipDevice>(host, bytes, out);
+    if (s.ok()) return LFG_OK;
+    return fail_hip(ctx, (hipError_t)s.error, ((s.failed == lfg::DeviceStep::Allocate ? "hipMalloc(" : "hipMemcpy(") + std::string(what) + ")").c_str());
+}
+
+// The one place that evicts: at the top of an entry point, before its first lookup in `cache` (lfg_table_cache.hpp: TableCache).
+template <class Cache>
+void trim_tables(lfg_context *ctx, Cache &cache) {
+    cache.trim([&] { (void)sync_lanes(ctx); });                 // a queued kernel may still read what goes
+}
+
+int build_axis_table(lfg_context *ctx, int in_size, int out_size, lfg::AxisTable *out) {
+    if (const auto hit = ctx->tables.find(std::make_pair(in_size, out_size))) { *out = *hit; return LFG_OK; }
 
     std::vector<int> start((size_t)out_size);
     std::vector<float> weight((size_t)out_size * 6u);
@@ -120,30 +139,28 @@ int build_axis_table(lfg_context *ctx, int in_size, int out_size, lfg::AxisTable
 
     if (t.pattern_2x) t.strips_per_xcd = lfg::scale_2x_strips_per_xcd(in_size);
 
-    auto release = [&]() {
-        (void)hipFree(t.d_start); (void)hipFree(t.d_weight); (void)hipFree(t.d_class); (void)hipFree(t.d_palette);
-    };
-    LFG_HIP(ctx, hipMalloc((void **)&t.d_start, start.size() * sizeof(int)));
-    hipError_t e = hipMalloc((void **)&t.d_weight, weight.size() * sizeof(float));
-    if (e == hipSuccess && t.palette_rows) e = hipMalloc((void **)&t.d_class, cls.size());
-    if (e == hipSuccess && t.palette_rows) e = hipMalloc((void **)&t.d_palette, palette.size() * sizeof(float));
-    if (e != hipSuccess) { release(); return fail_hip(ctx, e, "hipMalloc(weights)"); }
-    // Synchronous copies: pageable host vectors go out of scope when this function returns.
-    e = hipMemcpy(t.d_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t.d_weight, weight.data(), weight.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && t.palette_rows) e = hipMemcpy(t.d_class, cls.data(), cls.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && t.palette_rows) e = hipMemcpy(t.d_palette, palette.data(), palette.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { release(); return fail_hip(ctx, e, "hipMemcpy(tables)"); }
-    ctx->tables.push_back(t);
-    *out = &ctx->tables.back();
+    // start | weight | class | palette (the last two where there is a palette), each at a multiple of 256 bytes
+    const auto up256 = [](size_t n) { return (n + 255u) & ~(size_t)255u; };
+    const size_t offWeight = up256(start.size() * sizeof(int)), offClass = offWeight + up256(weight.size() * sizeof(float));
+    const size_t offPalette = offClass + (t.palette_rows ? up256(cls.size()) : 0u);
+    std::vector<uint8_t> host(offPalette + (t.palette_rows ? palette.size() * sizeof(float) : 0u), 0);
+    memcpy(host.data(), start.data(), start.size() * sizeof(int));
+    memcpy(host.data() + offWeight, weight.data(), weight.size() * sizeof(float));
+    if (t.palette_rows) {
+        memcpy(host.data() + offClass, cls.data(), cls.size());
+        memcpy(host.data() + offPalette, palette.data(), palette.size() * sizeof(float));
+    }
+    const int rc = upload_table(ctx, host.data(), host.size(), "tables", &t.d_base);
+    if (rc != LFG_OK) return rc;
+    t.d_start = reinterpret_cast<int *>(t.d_base);
+    t.d_weight = reinterpret_cast<float *>(t.d_base + offWeight);
+    if (t.palette_rows) {
+        t.d_class = t.d_base + offClass;
+        t.d_palette = reinterpret_cast<float *>(t.d_base + offPalette);
+    }
+    ctx->tables.insert(t);
+    *out = t;
     return LFG_OK;
-}
-
-// Everything the context has enqueued, on every lane (a resource shared by the lanes is about to go or to be read).
-hipError_t sync_lanes(lfg_context *ctx) {
-    hipError_t e = hipSuccess;
-    for (size_t k = 0; k < ctx->lanes.size() && e == hipSuccess; ++k) e = hipStreamSynchronize(ctx->from_selected(k).stream);
-    return e;
 }
 
 // A frame the selected lane owns (mv_tmp, mv_refined, mv_bwd, mv_bwd_refined, half_prev, half_curr, mv_half, mvq_tmp, mid_tmp, levelled_prev), at this size: kept while the size stays, made again when it
@@ -154,33 +171,17 @@ int lane_frame(lfg_context *ctx, lfg_frame &f, uint32_t width, uint32_t height, 
     return lfg_frame_create(ctx, width, height, format, &f);
 }
 
-// A device buffer the selected lane owns and only ever grows (pyramid_ws, mc_keys, mc_fill, static_mask, mcq_keys).  `what` names the allocation in the error.
-template <typename T>
-int lane_buffer_grow(lfg_context *ctx, T *&buf, size_t &have, size_t need, const char *what) {
-    if (need <= have) return LFG_OK;
-    lfg_lane_state &cur = ctx->cur();
-    LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // the lane's earlier calls may still read the old one
-    if (buf) (void)hipFree(buf);
-    buf = nullptr; have = 0;
-    const hipError_t e = hipMalloc((void **)&buf, need);
-    if (e != hipSuccess) return fail_hip(ctx, e, what);
-    have = need;
-    return LFG_OK;
+// The one place that grows a buffer of the selected lane (lfg_lane_state::buffers; lfg_table_cache.hpp: grow).  `what` names the
+// allocation in the error.
+int lane_buffer_grow(lfg_context *ctx, lfg::DeviceBuffer &buf, size_t need, const char *what) {
+    const lfg::DeviceStatus s = lfg::grow<lfg::HipDevice>(buf, need, [&] { return (int)hipStreamSynchronize(ctx->cur().stream); });
+    if (s.ok()) return LFG_OK;
+    return fail_hip(ctx, (hipError_t)s.error, s.failed == lfg::DeviceStep::Synchronize ? "hipStreamSynchronize(cur.stream)" : what);
 }
 
-// uv table of one axis length (lfg_internal.hpp: UvTable); a handful of sizes per context, kept until it goes.
-// Bounded like the axis tables: trim_uv_tables runs at the top of the interpolate entry points, BEFORE any pointer is taken,
-// so that the two lookups of a call (width, height) can never free each other's table.
-void trim_uv_tables(lfg_context *ctx) {
-    while (ctx->uv_tables.size() > 14) {
-        (void)sync_lanes(ctx);                                 // a queued kernel may still read it
-        (void)hipFree(ctx->uv_tables.front().d_uv);
-        ctx->uv_tables.erase(ctx->uv_tables.begin());
-    }
-}
-int build_uv_table(lfg_context *ctx, int size, const lfg::UvTable **out) {
-    for (auto &t : ctx->uv_tables)
-        if (t.size == size) { *out = &t; return LFG_OK; }
+// uv table of one axis length (lfg_internal.hpp: UvTable); a handful of sizes per context.
+int build_uv_table(lfg_context *ctx, int size, lfg::UvTable *out) {
+    if (const auto hit = ctx->uv_tables.find(size)) { *out = *hit; return LFG_OK; }
     const size_t n4 = ((size_t)size + 3u) & ~(size_t)3u, quads = n4 / 4u;
     std::vector<float> uv(n4, 0.0f);
     std::vector<uint8_t> centre(n4, 0);
@@ -212,43 +213,28 @@ int build_uv_table(lfg_context *ctx, int size, const lfg::UvTable **out) {
     memcpy(host.data(), uv.data(), n4 * sizeof(float));
     memcpy(host.data() + offCentre, centre.data(), n4);
     memcpy(host.data() + offGood, good.data(), good.size() * sizeof(uint64_t));
-    uint8_t *d = nullptr;
-    LFG_HIP(ctx, hipMalloc((void **)&d, bytes));
-    const hipError_t e = hipMemcpy(d, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return fail_hip(ctx, e, "hipMemcpy(uv table)"); }
-    t.d_uv = reinterpret_cast<float *>(d);
-    t.d_centre = d + offCentre;
-    t.d_goodMask = reinterpret_cast<uint64_t *>(d + offGood);
-    ctx->uv_tables.push_back(t);
-    *out = &ctx->uv_tables.back();
+    const int rc = upload_table(ctx, host.data(), bytes, "uv table", &t.d_base);
+    if (rc != LFG_OK) return rc;
+    t.d_uv = reinterpret_cast<float *>(t.d_base);
+    t.d_centre = t.d_base + offCentre;
+    t.d_goodMask = reinterpret_cast<uint64_t *>(t.d_base + offGood);
+    ctx->uv_tables.insert(t);
+    *out = t;
     return LFG_OK;
 }
 
-// Both axes' tables of one interpolate call.  (The x table is looked up again after the y table has been built: the push may
-// have moved the vector.)
+// Both axes' tables of one interpolate call.
 int interp_tables(lfg_context *ctx, int width, int height, lfg::InterpTables *tb) {
-    trim_uv_tables(ctx);
-    const lfg::UvTable *tx = nullptr, *ty = nullptr;
+    trim_tables(ctx, ctx->uv_tables);
+    lfg::UvTable tx, ty;
     int rc = build_uv_table(ctx, width, &tx);
     if (rc == LFG_OK) rc = build_uv_table(ctx, height, &ty);
-    if (rc == LFG_OK) rc = build_uv_table(ctx, width, &tx);
     if (rc != LFG_OK) return rc;
-    tb->uvx = tx->d_uv; tb->uvy = ty->d_uv;
-    tb->centreX = tx->d_centre; tb->centreY = ty->d_centre;
-    tb->goodMask = tx->d_goodMask;
-    tb->rcpW = tx->rcp; tb->rcpH = ty->rcp; tb->rcpExact = tx->rcpExact && ty->rcpExact ? 1 : 0;
+    tb->uvx = tx.d_uv; tb->uvy = ty.d_uv;
+    tb->centreX = tx.d_centre; tb->centreY = ty.d_centre;
+    tb->goodMask = tx.d_goodMask;
+    tb->rcpW = tx.rcp; tb->rcpH = ty.rcp; tb->rcpExact = tx.rcpExact && ty.rcpExact ? 1 : 0;
     return LFG_OK;
-}
-
-// Bounded cache: called at the top of lfg_scale, before any table pointer is taken, so the two
-// lookups that follow can never evict each other.
-void trim_axis_tables(lfg_context *ctx) {
-    while (ctx->tables.size() > 14) {
-        (void)sync_lanes(ctx);                                 // a queued kernel may still read it
-        lfg::AxisTable &old = ctx->tables.front();
-        (void)hipFree(old.d_start); (void)hipFree(old.d_weight); (void)hipFree(old.d_class); (void)hipFree(old.d_palette);
-        ctx->tables.erase(ctx->tables.begin());
-    }
 }
 
 // ---- candidate tables of the 8/16 motion paths, both tie-break rules (tiny; built at the first lfg_motion)
@@ -261,12 +247,10 @@ int ensure_motion_tables(lfg_context *ctx) {
                            host.data() + (3 * sem + 1) * lfg::kMotionTableWords,
                            host.data() + (3 * sem + 2) * lfg::kMotionTableWords, host.data() + 6 * lfg::kMotionTableWords);
     // Published only once the copy has succeeded: a later call must never find a half-initialised table.
-    uint32_t *d = nullptr;
-    LFG_HIP(ctx, hipMalloc((void **)&d, host.size() * sizeof(uint32_t)));
-    const hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return fail_hip(ctx, e, "hipMemcpy(motion tables)"); }
-    ctx->motion_tables = d;
-    return LFG_OK;
+    uint8_t *d = nullptr;
+    const int rc = upload_table(ctx, host.data(), host.size() * sizeof(uint32_t), "motion tables", &d);
+    if (rc == LFG_OK) ctx->motion_tables = reinterpret_cast<uint32_t *>(d);
+    return rc;
 }
 
 // ---- scratch of the prefiltered motion path (per frame size; kept between calls)
@@ -297,7 +281,7 @@ int motion_rim_split_lean(const lfg_context *ctx) {
 int ensure_motion_workspace(lfg_context *ctx, uint32_t width, uint32_t height) {
     lfg_lane_state &cur = ctx->cur();
     const int rimSplit = motion_rim_split(ctx), rimSplit2 = motion_rim_split_lean(ctx);
-    if (cur.motion_ws && cur.motion_ws_w == width && cur.motion_ws_h == height && cur.motion_ws_layout.rimSplit == rimSplit &&
+    if (cur.motion_ws.data && cur.motion_ws_w == width && cur.motion_ws_h == height && cur.motion_ws_layout.rimSplit == rimSplit &&
         cur.motion_ws_layout.rimSplit2 == rimSplit2) return LFG_OK;
     lfg::MotionWorkspaceLayout layout;
     if (ctx->motion_slots == 0) {
@@ -305,14 +289,11 @@ int ensure_motion_workspace(lfg_context *ctx, uint32_t width, uint32_t height) {
         if (ctx->knobs.debug) fprintf(stderr, "lfg: motion prefilter: %d workgroups resident at once\n", ctx->motion_slots);
     }
     const size_t bytes = lfg::motion_workspace_bytes(width, height, ctx->motion_slots, rimSplit, rimSplit2, &layout);
-    if (bytes > cur.motion_ws_bytes) {
-        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // a queued kernel may still use the old one
-        if (cur.motion_ws) (void)hipFree(cur.motion_ws);
-        cur.motion_ws = nullptr; cur.motion_ws_bytes = 0; cur.motion_ws_w = cur.motion_ws_h = 0;
-        LFG_HIP(ctx, hipMalloc((void **)&cur.motion_ws, bytes));
-        cur.motion_ws_bytes = bytes;
+    if (bytes > cur.motion_ws.bytes) {
+        const int rc = lane_buffer_grow(ctx, cur.motion_ws, bytes, "hipMalloc((void **)&cur.motion_ws, bytes)");
+        if (rc != LFG_OK) return rc;
     } else {
-        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
+        LFG_HIP(ctx, hipStreamSynchronize(cur.stream));          // a queued kernel may still read the plan tables about to be overwritten
     }
     // work-unit tables of this frame size: unitMap | unitAux | tileMap
     const lfg::PrefilterPlanHost plan = lfg::prefilter_plan(width, height, ctx->motion_slots, rimSplit);
@@ -320,24 +301,24 @@ int ensure_motion_workspace(lfg_context *ctx, uint32_t width, uint32_t height) {
     tables.insert(tables.end(), plan.unitMap.begin(), plan.unitMap.end());
     tables.insert(tables.end(), plan.unitAux.begin(), plan.unitAux.end());
     tables.insert(tables.end(), plan.tileMap.begin(), plan.tileMap.end());
-    LFG_HIP(ctx, hipMemcpy(cur.motion_ws + layout.plan, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    LFG_HIP(ctx, hipMemcpy(cur.motion_ws.data + layout.plan, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (rimSplit2) {        // the plan of the calls that go through the lean kernel, and that kernel's tiles
         const lfg::PrefilterPlanHost plan2 = lfg::prefilter_plan(width, height, ctx->motion_slots, rimSplit2);
         std::vector<uint32_t> t2;
         t2.insert(t2.end(), plan2.unitMap.begin(), plan2.unitMap.end());
         t2.insert(t2.end(), plan2.unitAux.begin(), plan2.unitAux.end());
         t2.insert(t2.end(), plan2.tileMap.begin(), plan2.tileMap.end());
-        LFG_HIP(ctx, hipMemcpy(cur.motion_ws + layout.plan2, t2.data(), t2.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LFG_HIP(ctx, hipMemcpy(cur.motion_ws.data + layout.plan2, t2.data(), t2.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (!plan2.leanTiles.empty()) {
             std::vector<uint32_t> listed = plan2.leanTiles;
             listed.insert(listed.end(), plan2.leanPartial.begin(), plan2.leanPartial.end());
-            LFG_HIP(ctx, hipMemcpy(cur.motion_ws + layout.leanTiles, listed.data(), listed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            LFG_HIP(ctx, hipMemcpy(cur.motion_ws.data + layout.leanTiles, listed.data(), listed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
     // what the kernels expect to find between calls: a cleared control area (the hint kernel's counter of finished
     // workgroups lies in it, and that kernel is what clears the rest per call) and the merge words of the flagged tiles all ones
-    LFG_HIP(ctx, hipMemset(cur.motion_ws + layout.tileFlags, 0, layout.order - layout.tileFlags));
-    LFG_HIP(ctx, hipMemset(cur.motion_ws + layout.merge, 0xFF, layout.mergeBytes));
+    LFG_HIP(ctx, hipMemset(cur.motion_ws.data + layout.tileFlags, 0, layout.order - layout.tileFlags));
+    LFG_HIP(ctx, hipMemset(cur.motion_ws.data + layout.merge, 0xFF, layout.mergeBytes));
     cur.motion_units = plan.units;
     layout.lastLean = 0;
     cur.motion_ws_layout = layout;
@@ -461,7 +442,6 @@ LFG_EXPORT int lfg_context_create(int device_ordinal, lfg_context **out_ctx) {
     if (e != hipSuccess) { delete ctx; return fail_hip(nullptr, e, "hipStreamCreate"); }
     lane0.stream = lane0.own_stream;
     ctx->lanes.push_back(lane0);
-    ctx->tables.reserve(17);                 // AxisTable pointers handed out stay valid
     if (const char *m = getenv("LFG_MOTION_HINTS")) ctx->motion_hints = atoi(m) != 0;
     if (const char *m = getenv("LFG_MOTION_LEAN")) ctx->motion_lean = atoi(m) != 0;
     if (const char *m = getenv("LFG_MOTION_RIM_SPLIT")) { const int v = atoi(m); if (v == 4 || v == 8 || v == 48) ctx->rim_split_env = v; }
@@ -492,12 +472,7 @@ void lane_release(lfg_lane_state &l) {
     if (l.own_stream && l.own_stream != l.stream) (void)hipStreamSynchronize(l.own_stream);
     for (lfg_frame *f : {&l.mv_tmp, &l.mv_refined, &l.mv_bwd, &l.mv_bwd_refined, &l.half_prev, &l.half_curr, &l.mv_half, &l.mvq_tmp, &l.mid_tmp, &l.levelled_prev})      // (lane_frame)
         if (f->data && f->owned) (void)hipFree(f->data);
-    if (l.motion_ws) (void)hipFree(l.motion_ws);
-    if (l.pyramid_ws) (void)hipFree(l.pyramid_ws);
-    if (l.mc_keys) (void)hipFree(l.mc_keys);
-    if (l.mc_fill) (void)hipFree(l.mc_fill);
-    if (l.static_mask) (void)hipFree(l.static_mask);
-    if (l.mcq_keys) (void)hipFree(l.mcq_keys);
+    for (lfg::DeviceBuffer *b : l.buffers()) lfg::release<lfg::HipDevice>(*b);
     if (l.mark) (void)hipEventDestroy(l.mark);
     if (l.verdict.event) (void)hipEventDestroy(l.verdict.event);
     if (l.verdict.pinned) (void)hipHostFree(l.verdict.pinned);
@@ -520,11 +495,8 @@ LFG_EXPORT void lfg_context_destroy(lfg_context *ctx) {
     for (auto &l : ctx->lanes) lane_release(l);
     for (auto &s : ctx->prof_pending) { (void)hipEventDestroy(s.begin); (void)hipEventDestroy(s.end); }
     for (auto &p : ctx->prof_free) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &t : ctx->tables) { (void)hipFree(t.d_start); (void)hipFree(t.d_weight); (void)hipFree(t.d_class); (void)hipFree(t.d_palette); }
-    for (auto &t : ctx->uv_tables) (void)hipFree(t.d_uv);
-    for (auto &t : ctx->resample_tables) (void)hipFree(t.d_base);
-    for (auto &t : ctx->resample_brackets) (void)hipFree(t.d_base);
-    for (auto &t : ctx->edge_positions) (void)hipFree(t.d_base);
+    ctx->tables.release_all(); ctx->uv_tables.release_all(); ctx->resample_tables.release_all();
+    ctx->resample_brackets.release_all(); ctx->edge_positions.release_all();
     if (ctx->edge_shapes) (void)hipFree(ctx->edge_shapes);
     if (ctx->motion_tables) (void)hipFree(ctx->motion_tables);
     delete ctx;
@@ -783,16 +755,16 @@ LFG_EXPORT int lfg_scale(lfg_context *ctx, const lfg_frame *in, lfg_frame *out) 
     if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
         return fail(ctx, LFG_ERR_INVALID, "lfg_scale: frames must be non-empty RGBA8");
     if (in->data == out->data) return fail(ctx, LFG_ERR_INVALID, "lfg_scale: in-place scaling is not supported");
-    trim_axis_tables(ctx);
-    lfg::AxisTable *tx = nullptr, *ty = nullptr;               // vector capacity is reserved: pointers stay valid
+    trim_tables(ctx, ctx->tables);
+    lfg::AxisTable tx, ty;
     int rc = build_axis_table(ctx, (int)in->width, (int)out->width, &tx);
     if (rc != LFG_OK) return rc;
     rc = build_axis_table(ctx, (int)in->height, (int)out->height, &ty);
     if (rc != LFG_OK) return rc;
-    const bool fast = tx->pattern_2x && ty->pattern_2x && tx->palette_rows > 0 && ty->strips_per_xcd > 0 && lfg::scale_2x_supported(*in, *out);
+    const bool fast = tx.pattern_2x && ty.pattern_2x && tx.palette_rows > 0 && ty.strips_per_xcd > 0 && lfg::scale_2x_supported(*in, *out);
     StageTimer timer(ctx, LFG_STAGE_SCALE);
-    hipError_t e = fast ? lfg::launch_scale_2x(ctx->cur().stream, *in, *out, *tx, *ty)
-                        : lfg::launch_scale_generic(ctx->cur().stream, *in, *out, *tx, *ty);
+    hipError_t e = fast ? lfg::launch_scale_2x(ctx->cur().stream, *in, *out, tx, ty)
+                        : lfg::launch_scale_generic(ctx->cur().stream, *in, *out, tx, ty);
     if (e != hipSuccess) return fail_hip(ctx, e, "scale kernel launch");
     ctx->scale_last_kernel = fast ? 1 : 0;
     return LFG_OK;
@@ -874,7 +846,7 @@ static int motion_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *
         const lfg::MotionCall call = lfg::motion_call_policy(v, in, ctx->knobs);
         cur.motion_ws_layout.lastLean = call.lean ? 1 : 0;
         ctx->motion_last_tier = fo.data ? 0 : call.tier;
-        e = lfg::launch_motion_prefiltered_8_16(cur.stream, *prev, *curr, *mv, cur.motion_ws, cur.motion_ws_layout, cur.motion_units,
+        e = lfg::launch_motion_prefiltered_8_16(cur.stream, *prev, *curr, *mv, cur.motion_ws.data, cur.motion_ws_layout, cur.motion_units,
                                                 rank2scan, order32, order32 + lfg::kMotionTableWords,
                                                 ctx->motion_tables + 6 * lfg::kMotionTableWords, ctx->motion_hints, ctx->lanes.size() >= 2, fo,
                                                 call.lean, call.deliverWord ? v.pinned : nullptr, call.groupsCap, call.expectNoFallback, ctx->knobs,
@@ -929,10 +901,10 @@ LFG_EXPORT int lfg_motion_pyramid(lfg_context *ctx, const lfg_frame *prev, const
     lfg_lane_state &cur = ctx->cur();
     lfg::PyramidLayout layout;
     const size_t bytes = lfg::pyramid_workspace_bytes(curr->width, curr->height, levels, &layout);
-    int rc = lane_buffer_grow(ctx, cur.pyramid_ws, cur.pyramid_ws_bytes, bytes, "hipMalloc((void **)&cur.pyramid_ws, bytes)");
+    int rc = lane_buffer_grow(ctx, cur.pyramid_ws, bytes, "hipMalloc((void **)&cur.pyramid_ws, bytes)");
     if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_MOTION);
-    hipError_t e = lfg::launch_motion_pyramid(cur.stream, *prev, *curr, *mv, levels, coarse_radius, refine_radius, cur.pyramid_ws, layout);
+    hipError_t e = lfg::launch_motion_pyramid(cur.stream, *prev, *curr, *mv, levels, coarse_radius, refine_radius, cur.pyramid_ws.data, layout);
     if (e != hipSuccess) return fail_hip(ctx, e, "pyramid motion kernel launch");
     return LFG_OK;
 }
@@ -966,11 +938,11 @@ LFG_EXPORT int lfg_motion_open_segments(lfg_context *ctx, uint32_t *out_open, ui
     if (!ctx) return LFG_ERR_INVALID;
     lfg_lane_state &cur = ctx->cur();
     if (!out_open || !out_segments) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_open_segments: NULL argument");
-    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_open_segments: the prefiltered path has not run");
+    if (!cur.motion_ws.data || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_open_segments: the prefiltered path has not run");
     LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     const uint32_t tx = (cur.motion_ws_w + 55u) / 56u, ty = (cur.motion_ws_h + 63u) / 64u;      // (prefilter tiles: 56 x 64 pixels)
     uint32_t open = 0;
-    LFG_HIP(ctx, hipMemcpy(&open, cur.motion_ws + cur.motion_ws_layout.ctrl + lfg::kCtrlOpenCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(&open, cur.motion_ws.data + cur.motion_ws_layout.ctrl + lfg::kCtrlOpenCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_open = open;
     *out_segments = tx * ty * 4u;
     return LFG_OK;
@@ -984,10 +956,10 @@ LFG_EXPORT int lfg_motion_hand_over_stats(lfg_context *ctx, uint32_t *out_entrie
     if (!ctx) return LFG_ERR_INVALID;
     lfg_lane_state &cur = ctx->cur();
     if (!out_entries_asked || !out_entries_room) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_hand_over_stats: NULL argument");
-    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_hand_over_stats: the prefiltered path has not run");
+    if (!cur.motion_ws.data || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_hand_over_stats: the prefiltered path has not run");
     LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     uint32_t asked = 0;
-    LFG_HIP(ctx, hipMemcpy(&asked, cur.motion_ws + cur.motion_ws_layout.queueCount, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(&asked, cur.motion_ws.data + cur.motion_ws_layout.queueCount, sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_entries_asked = asked;
     *out_entries_room = (uint32_t)cur.motion_ws_layout.queueCap;
     return LFG_OK;
@@ -999,10 +971,10 @@ LFG_EXPORT int lfg_motion_lean_stats(lfg_context *ctx, int *out_used, uint32_t *
     if (!ctx) return LFG_ERR_INVALID;
     lfg_lane_state &cur = ctx->cur();
     if (!out_used || !out_tiles || !out_tiles_left) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_lean_stats: NULL argument");
-    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_lean_stats: the prefiltered path has not run");
+    if (!cur.motion_ws.data || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_lean_stats: the prefiltered path has not run");
     LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     uint32_t left = 0;
-    LFG_HIP(ctx, hipMemcpy(&left, cur.motion_ws + cur.motion_ws_layout.ctrl + lfg::kCtrlHardCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(&left, cur.motion_ws.data + cur.motion_ws_layout.ctrl + lfg::kCtrlHardCount * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_used = cur.motion_ws_layout.lastLean;
     *out_tiles = (uint32_t)cur.motion_ws_layout.leanCount;
     *out_tiles_left = cur.motion_ws_layout.lastLean ? left : 0u;
@@ -1013,10 +985,10 @@ LFG_EXPORT int lfg_motion_strip_stats(lfg_context *ctx, uint32_t *out_rows, uint
     if (!ctx) return LFG_ERR_INVALID;
     lfg_lane_state &cur = ctx->cur();
     if (!out_rows || !out_columns) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_strip_stats: NULL argument");
-    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_strip_stats: the prefiltered path has not run");
+    if (!cur.motion_ws.data || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_strip_stats: the prefiltered path has not run");
     LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     std::vector<uint32_t> t((size_t)cur.motion_ws_h + cur.motion_ws_w);
-    LFG_HIP(ctx, hipMemcpy(t.data(), cur.motion_ws + cur.motion_ws_layout.colBand, t.size() * 4, hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(t.data(), cur.motion_ws.data + cur.motion_ws_layout.colBand, t.size() * 4, hipMemcpyDeviceToHost));
     uint32_t rows = 0, cols = 0;
     for (uint32_t y = 0; y < cur.motion_ws_h; ++y) rows += t[y] != 0u;
     for (uint32_t x = 0; x < cur.motion_ws_w; ++x) cols += t[cur.motion_ws_h + x] != 0u;
@@ -1038,31 +1010,31 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
                                      double *out_mean_recorded) {
     if (!ctx) return LFG_ERR_INVALID;
     lfg_lane_state &cur = ctx->cur();
-    if (!cur.motion_ws || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_last_stats: the prefiltered path has not run");
+    if (!cur.motion_ws.data || cur.motion_ws_w == 0) return fail(ctx, LFG_ERR_INVALID, "lfg_motion_last_stats: the prefiltered path has not run");
     LFG_HIP(ctx, hipStreamSynchronize(cur.stream));
     const uint32_t tx = (cur.motion_ws_w + 63u) / 64u, ty = (cur.motion_ws_h + 63u) / 64u;
     std::vector<uint32_t> flags((size_t)tx * ty);
-    LFG_HIP(ctx, hipMemcpy(flags.data(), cur.motion_ws + cur.motion_ws_layout.tileFlags, flags.size() * 4, hipMemcpyDeviceToHost));
+    LFG_HIP(ctx, hipMemcpy(flags.data(), cur.motion_ws.data + cur.motion_ws_layout.tileFlags, flags.size() * 4, hipMemcpyDeviceToHost));
     uint32_t fb = 0;
     for (uint32_t f : flags) fb += f != 0u;
     if (ctx->knobs.debug) {
         uint32_t handed[2] = {0, 0};
-        LFG_HIP(ctx, hipMemcpy(handed, cur.motion_ws + cur.motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(handed, cur.motion_ws.data + cur.motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
         fprintf(stderr, "lfg: motion prefilter: %u requests to hand a segment over (room for %d), %u tiles flagged for the exact kernel\n",
                 handed[0], cur.motion_ws_layout.queueCap, handed[1]);
         uint32_t lean[2] = {0, 0};
-        LFG_HIP(ctx, hipMemcpy(lean, cur.motion_ws + cur.motion_ws_layout.ctrl + lfg::kCtrlLeanSettled * sizeof(uint32_t), 8, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(lean, cur.motion_ws.data + cur.motion_ws_layout.ctrl + lfg::kCtrlLeanSettled * sizeof(uint32_t), 8, hipMemcpyDeviceToHost));
         uint32_t flags[3] = {0, 0, 0};
-        LFG_HIP(ctx, hipMemcpy(flags, cur.motion_ws + cur.motion_ws_layout.orderFlags, 12, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(flags, cur.motion_ws.data + cur.motion_ws_layout.orderFlags, 12, hipMemcpyDeviceToHost));
         fprintf(stderr, "lfg: lean kernel: %d tiles listed, %u segments settled, %u left to the generic kernel (counted in -DLFG_LEAN_STATS builds); order flags: hand-over %u, hints %u, lean %u (sample blocks with a close match %u, with an exact one %u)\n",
                 cur.motion_ws_layout.leanCount, lean[0], lean[1], flags[0], flags[1], lfg::verdict_lean(flags[2]) ? 1u : 0u, lfg::verdict_close(flags[2]), lfg::verdict_exact(flags[2]));
     }
     if (ctx->knobs.debugDyn) {       // the deepest private lists of the handed-over segments: block (4 x queue slot + wave), pixel, records
         uint32_t handed[2] = {0, 0};
-        LFG_HIP(ctx, hipMemcpy(handed, cur.motion_ws + cur.motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(handed, cur.motion_ws.data + cur.motion_ws_layout.queueCount, 8, hipMemcpyDeviceToHost));
         const size_t blocks = (size_t)std::min<uint32_t>(handed[0], (uint32_t)cur.motion_ws_layout.queueCap) * 4u, per = 16u * 56u;
         std::vector<uint32_t> dc(blocks * per);
-        if (!dc.empty()) LFG_HIP(ctx, hipMemcpy(dc.data(), cur.motion_ws + cur.motion_ws_layout.dynCount, dc.size() * 4, hipMemcpyDeviceToHost));
+        if (!dc.empty()) LFG_HIP(ctx, hipMemcpy(dc.data(), cur.motion_ws.data + cur.motion_ws_layout.dynCount, dc.size() * 4, hipMemcpyDeviceToHost));
         size_t hist[40] = {0};
         int dumped = 0;
         const uint32_t deep = (uint32_t)ctx->knobs.debugDynDeep;
@@ -1075,8 +1047,8 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
                     const int K = cur.motion_ws_layout.listDyn;
                     for (int k = 0; k < std::min<int>((int)dc[i], K); ++k) {
                         uint32_t rec = 0; float thr = 0.f;
-                        (void)hipMemcpy(&rec, cur.motion_ws + cur.motion_ws_layout.dynList + (((blk * 16u + row) * (size_t)K + (size_t)k) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
-                        (void)hipMemcpy(&thr, cur.motion_ws + cur.motion_ws_layout.dynUmin + ((blk * 16u + row) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
+                        (void)hipMemcpy(&rec, cur.motion_ws.data + cur.motion_ws_layout.dynList + (((blk * 16u + row) * (size_t)K + (size_t)k) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
+                        (void)hipMemcpy(&thr, cur.motion_ws.data + cur.motion_ws_layout.dynUmin + ((blk * 16u + row) * 56u + col) * 4u, 4, hipMemcpyDeviceToHost);
                         const uint32_t bits = (rec >> 11) << 10; float c; memcpy(&c, &bits, 4);
                         fprintf(stderr, "      record %2d: cost >= %.3f rank %4u (dx %+d, dy %+d)%s\n", k, c, rec & 0x7FFu, (int)((rec & 0x7FFu) % 33u) - 16, (int)((rec & 0x7FFu) / 33u) - 16, k == 0 ? "" : "");
                         if (k + 1 == std::min<int>((int)dc[i], K)) fprintf(stderr, "      final threshold %.3f\n", thr);
@@ -1087,7 +1059,7 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
         {   // which segments under the flagged tiles were handed over
             const uint32_t ptx = (cur.motion_ws_w + 55u) / 56u, pty = (cur.motion_ws_h + 63u) / 64u;
             std::vector<uint32_t> sm((size_t)ptx * pty * 4u);
-            LFG_HIP(ctx, hipMemcpy(sm.data(), cur.motion_ws + cur.motion_ws_layout.segMap, sm.size() * 4, hipMemcpyDeviceToHost));
+            LFG_HIP(ctx, hipMemcpy(sm.data(), cur.motion_ws.data + cur.motion_ws_layout.segMap, sm.size() * 4, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < flags.size(); ++i) if (flags[i]) {
                 const uint32_t fx = (uint32_t)(i % tx), fy = (uint32_t)(i / tx);
                 for (uint32_t px = fx * 64u / 56u; px <= std::min(ptx - 1u, (fx * 64u + 63u) / 56u); ++px)
@@ -1119,14 +1091,14 @@ LFG_EXPORT int lfg_motion_last_stats(lfg_context *ctx, uint32_t *out_tiles, uint
     if (out_mean_recorded) {
         const size_t px = (size_t)cur.motion_ws_w * cur.motion_ws_h;
         std::vector<uint32_t> cnt(px);
-        LFG_HIP(ctx, hipMemcpy(cnt.data(), cur.motion_ws + cur.motion_ws_layout.count, px * 4, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(cnt.data(), cur.motion_ws.data + cur.motion_ws_layout.count, px * 4, hipMemcpyDeviceToHost));
         // (tiles whose candidates were shared between several workgroups keep their counts elsewhere: left out)
         const lfg::PrefilterPlanHost plan = lfg::prefilter_plan(cur.motion_ws_w, cur.motion_ws_h, ctx->motion_slots,
                                                                 cur.motion_ws_layout.lastLean ? cur.motion_ws_layout.rimSplit2 : cur.motion_ws_layout.rimSplit);
         // (a segment that settled all of its pixels in the prefilter wrote no counts: its pixels hold at most two records,
         //  counted as none here)
         std::vector<uint32_t> segDone((size_t)plan.tiles * 4u);
-        LFG_HIP(ctx, hipMemcpy(segDone.data(), cur.motion_ws + cur.motion_ws_layout.segDone, segDone.size() * 4, hipMemcpyDeviceToHost));
+        LFG_HIP(ctx, hipMemcpy(segDone.data(), cur.motion_ws.data + cur.motion_ws_layout.segDone, segDone.size() * 4, hipMemcpyDeviceToHost));
         double sum = 0; size_t n = 0;
         for (uint32_t y = 0; y < cur.motion_ws_h; ++y)
             for (uint32_t x = 0; x < cur.motion_ws_w; ++x) {
@@ -1489,8 +1461,8 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     }
     lfg_lane_state &cur = ctx->cur();
     const size_t bytes = (size_t)curr->width * curr->height * 4u;
-    int rc = subpel ? lane_buffer_grow(ctx, cur.mcq_keys, cur.mcq_keys_bytes, 2u * bytes, "hipMalloc((void **)&cur.mcq_keys, 2 * bytes)")
-                    : lane_buffer_grow(ctx, cur.mc_keys, cur.mc_keys_bytes, bytes, "hipMalloc((void **)&cur.mc_keys, bytes)");
+    int rc = subpel ? lane_buffer_grow(ctx, cur.mcq_keys, 2u * bytes, "hipMalloc((void **)&cur.mcq_keys, 2 * bytes)")
+                    : lane_buffer_grow(ctx, cur.mc_keys, bytes, "hipMalloc((void **)&cur.mc_keys, bytes)");
     if (rc != LFG_OK) return rc;
     // lfg_set_hole_reach: the three interpolating kinds of whole-pixel vectors fill their holes from the lane's fill plane, made
     // per factor behind K
@@ -1498,22 +1470,23 @@ int compensated_run(lfg_context *ctx, const lfg_frame *prev, const lfg_frame *cu
     const bool bicubic = sampling == LFG_SAMPLING_BICUBIC && (kind == McKind::Plain || subpel);
     const int reach = kind == McKind::Extrapolate || subpel || bicubic ? -1 : ctx->hole_reach;
     if (reach >= 1) {
-        rc = lane_buffer_grow(ctx, cur.mc_fill, cur.mc_fill_bytes, bytes, "hipMalloc((void **)&cur.mc_fill, bytes)");
+        rc = lane_buffer_grow(ctx, cur.mc_fill, bytes, "hipMalloc((void **)&cur.mc_fill, bytes)");
         if (rc != LFG_OK) return rc;
     }
-    uint32_t *const fill = reach >= 1 ? cur.mc_fill : nullptr;
+    uint32_t *const fill = reach >= 1 ? cur.mc_fill.as<uint32_t>() : nullptr, *const keys = cur.mc_keys.as<uint32_t>();
+    unsigned long long *const keys64 = cur.mcq_keys.as<unsigned long long>();
     StageTimer timer(ctx, LFG_STAGE_INTERPOLATE);
     for (uint32_t i = 0; i < count; ++i) {                       // one key image (and one fill plane), reused in stream order
-        hipError_t e = bicubic ? (subpel ? lfg::launch_interpolate_compensated_subpel_bicubic(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mcq_keys)
-                                         : lfg::launch_interpolate_compensated_bicubic(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys))
-                       : subpel ? lfg::launch_interpolate_compensated_subpel(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mcq_keys)
-                       : masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, cur.mc_keys,
+        hipError_t e = bicubic ? (subpel ? lfg::launch_interpolate_compensated_subpel_bicubic(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, keys64)
+                                         : lfg::launch_interpolate_compensated_bicubic(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, keys))
+                       : subpel ? lfg::launch_interpolate_compensated_subpel(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, keys64)
+                       : masked ? lfg::launch_interpolate_compensated_masked(cur.stream, *prev, *curr, *mv, *mask, *outs[i], factors[i], match_sad, keys,
                                                                            fill, reach)
                        : kind == McKind::Extrapolate
-                              ? lfg::launch_extrapolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys)
+                              ? lfg::launch_extrapolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, keys)
                        : bidir ? lfg::launch_interpolate_compensated_bidirectional(cur.stream, *prev, *curr, *mv, *bwd, *outs[i], factors[i],
-                                                                                   match_sad, tolerance, cur.mc_keys, fill, reach)
-                              : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, cur.mc_keys,
+                                                                                   match_sad, tolerance, keys, fill, reach)
+                              : lfg::launch_interpolate_compensated(cur.stream, *prev, *curr, *mv, *outs[i], factors[i], match_sad, keys,
                                                                     fill, reach);
         if (e != hipSuccess) return fail_hip(ctx, e, kind == McKind::Extrapolate ? "compensated extrapolate kernel launch" : "compensated interpolate kernel launch");
     }
@@ -1564,9 +1537,9 @@ int compensated_frames(lfg_context *ctx, const lfg_frame *prev, const lfg_frame 
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     lfg_lane_state &cur = ctx->cur();
     const size_t bytes = (size_t)curr->width * curr->height;
-    int rc = lane_buffer_grow(ctx, cur.static_mask, cur.static_mask_bytes, bytes, "hipMalloc((void **)&cur.static_mask, bytes)");
+    int rc = lane_buffer_grow(ctx, cur.static_mask, bytes, "hipMalloc((void **)&cur.static_mask, bytes)");
     if (rc != LFG_OK) return rc;
-    const lfg_mask mask{cur.static_mask, curr->width, curr->height, curr->width};
+    const lfg_mask mask{cur.static_mask.data, curr->width, curr->height, curr->width};
     rc = lfg_static_mask(ctx, prev, curr, ctx->static_tolerance, &mask);
     if (rc != LFG_OK) return rc;
     return compensated_run(ctx, prev, curr, vectors, &mask, McKind::Masked, outs, factors, count, ctx->match_sad,
@@ -2371,29 +2344,13 @@ LFG_EXPORT int lfg_resample_brackets(uint32_t in_size, uint32_t out_size, int32_
 
 namespace {
 
-// Bounded like the axis tables: called at the top of lfg_resample, before either of its tables is looked up, so that the two
-// lookups of a call can never free each other's table.
-void trim_resample_tables(lfg_context *ctx) {
-    while (ctx->resample_tables.size() > 14) {
-        (void)sync_lanes(ctx);                                 // a queued kernel may still read it
-        (void)hipFree(ctx->resample_tables.front().d_base);
-        ctx->resample_tables.erase(ctx->resample_tables.begin());
-    }
-    while (ctx->resample_brackets.size() > 14) {
-        (void)sync_lanes(ctx);
-        (void)hipFree(ctx->resample_brackets.front().d_base);
-        ctx->resample_brackets.erase(ctx->resample_brackets.begin());
-    }
-}
-
 // The brackets of one growing axis (out > in), built and uploaded at their first use.  The kernel reads texel a(p) and b(p) of
 // a row, and LDS row a(q) and b(q) of a tile, without a check of its own, on the strength of the lemma
 //   first[p] <= a(p) <= b(p) < first[p] + count[p]   for every filter of support >= 1,
 // which is asserted here on the taps of support 1, |(2k + 1) out - (2p + 1) in| < 2 out folded onto 0 .. in - 1: a wider
 // filter's taps hold those, and folding is monotone.
 int resample_bracket_table(lfg_context *ctx, uint32_t in_size, uint32_t out_size, lfg::ResampleBracket *out) {
-    for (const auto &t : ctx->resample_brackets)
-        if (t.in_size == in_size && t.out_size == out_size) { *out = t.bracket; return LFG_OK; }
+    if (const auto hit = ctx->resample_brackets.find(std::make_pair(in_size, out_size))) { *out = hit->bracket; return LFG_OK; }
     const size_t n = out_size;
     std::vector<int32_t> host(2 * n);
     if (lfg_resample_brackets(in_size, out_size, host.data(), host.data() + n) != LFG_OK)
@@ -2410,20 +2367,18 @@ int resample_bracket_table(lfg_context *ctx, uint32_t in_size, uint32_t out_size
     }
     lfg::ResampleBracketTable t;
     t.in_size = in_size; t.out_size = out_size;
-    LFG_HIP(ctx, hipMalloc((void **)&t.d_base, 2 * n * sizeof(int32_t)));
-    const hipError_t e = hipMemcpy(t.d_base, host.data(), 2 * n * sizeof(int32_t), hipMemcpyHostToDevice);   // (synchronous, as the axis table's)
-    if (e != hipSuccess) { (void)hipFree(t.d_base); return fail_hip(ctx, e, "hipMemcpy(resample brackets)"); }
-    t.bracket.lo = t.d_base;
-    t.bracket.hi = t.d_base + n;
-    ctx->resample_brackets.push_back(t);
+    const int rc = upload_table(ctx, host.data(), 2 * n * sizeof(int32_t), "resample brackets", &t.d_base);
+    if (rc != LFG_OK) return rc;
+    t.bracket.lo = reinterpret_cast<int32_t *>(t.d_base);
+    t.bracket.hi = t.bracket.lo + n;
+    ctx->resample_brackets.insert(t);
     *out = t.bracket;
     return LFG_OK;
 }
 
 // The table of one axis, built and uploaded at its first use.  Returned by value: the pointers in it are the device's.
 int resample_table(lfg_context *ctx, int filter, uint32_t in_size, uint32_t out_size, lfg::ResampleTable *out) {
-    for (const auto &t : ctx->resample_tables)
-        if (t.filter == filter && t.in_size == in_size && t.out_size == out_size) { *out = t; return LFG_OK; }
+    if (const auto hit = ctx->resample_tables.find(std::make_tuple(filter, in_size, out_size))) { *out = *hit; return LFG_OK; }
     const size_t n = out_size;
     std::vector<int32_t> first(n);
     std::vector<uint32_t> count(n);
@@ -2445,15 +2400,13 @@ int resample_table(lfg_context *ctx, int filter, uint32_t in_size, uint32_t out_
     memcpy(host.data() + offCount, count.data(), n * sizeof(uint32_t));
     for (size_t p = 0; p < n; ++p)
         memcpy(host.data() + offWeights + p * stride * sizeof(int16_t), &weights[p * LFG_RESAMPLE_MAX_TAPS], count[p] * sizeof(int16_t));
-    LFG_HIP(ctx, hipMalloc((void **)&t.d_base, bytes));
-    // A synchronous copy: the pageable host vector goes out of scope when this function returns.
-    const hipError_t e = hipMemcpy(t.d_base, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(t.d_base); return fail_hip(ctx, e, "hipMemcpy(resample table)"); }
+    const int up = upload_table(ctx, host.data(), bytes, "resample table", &t.d_base);
+    if (up != LFG_OK) return up;
     t.axis.first = reinterpret_cast<const int32_t *>(t.d_base);
     t.axis.count = reinterpret_cast<const uint32_t *>(t.d_base + offCount);
     t.axis.weights = reinterpret_cast<const int16_t *>(t.d_base + offWeights);
     t.axis.stride = stride;
-    ctx->resample_tables.push_back(t);
+    ctx->resample_tables.insert(t);
     *out = t;
     return LFG_OK;
 }
@@ -2478,7 +2431,8 @@ int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int fil
     if (!resample_filter_known(filter)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": unknown filter");
     if (strength < 0 || strength > 64) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": strength must be in [0, 64]");
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": the output overlaps the input");
-    trim_resample_tables(ctx);
+    trim_tables(ctx, ctx->resample_tables);
+    trim_tables(ctx, ctx->resample_brackets);
     lfg::ResampleTable tx, ty;
     int rc = resample_table(ctx, filter, in->width, out->width, &tx);
     if (rc == LFG_OK) rc = resample_table(ctx, filter, in->height, out->height, &ty);
@@ -2546,8 +2500,7 @@ namespace {
 //   0 <= base[p + 1] - base[p] <= 1   and   -1 <= base[p] <= in - 1,
 // which hold because out >= in and are asserted here on what the builder returned.
 int edge_position_table(lfg_context *ctx, uint32_t in_size, uint32_t out_size, lfg::EdgeAxis *out) {
-    for (const auto &t : ctx->edge_positions)
-        if (t.in_size == in_size && t.out_size == out_size) { *out = t.axis; return LFG_OK; }
+    if (const auto hit = ctx->edge_positions.find(std::make_pair(in_size, out_size))) { *out = hit->axis; return LFG_OK; }
     const size_t n = out_size;
     std::vector<uint8_t> host(5 * n);                              // base | frac
     int32_t *base = reinterpret_cast<int32_t *>(host.data());
@@ -2559,12 +2512,11 @@ int edge_position_table(lfg_context *ctx, uint32_t in_size, uint32_t out_size, l
                                                   std::to_string(out_size) + ", sample " + std::to_string(p) + ")");
     lfg::EdgePositionTable t;
     t.in_size = in_size; t.out_size = out_size;
-    LFG_HIP(ctx, hipMalloc((void **)&t.d_base, host.size()));
-    const hipError_t e = hipMemcpy(t.d_base, host.data(), host.size(), hipMemcpyHostToDevice);   // (synchronous, as the axis table's)
-    if (e != hipSuccess) { (void)hipFree(t.d_base); return fail_hip(ctx, e, "hipMemcpy(edge positions)"); }
+    const int rc = upload_table(ctx, host.data(), host.size(), "edge positions", &t.d_base);
+    if (rc != LFG_OK) return rc;
     t.axis.base = reinterpret_cast<const int32_t *>(t.d_base);
     t.axis.frac = t.d_base + 4 * n;
-    ctx->edge_positions.push_back(t);
+    ctx->edge_positions.insert(t);
     *out = t.axis;
     return LFG_OK;
 }
@@ -2577,12 +2529,10 @@ int edge_shape_table(lfg_context *ctx) {
     std::vector<lfg::EdgeShape> host(kRows);
     if (lfg_upscale_edge_shapes(rows.data()) != LFG_OK) return fail(ctx, LFG_ERR_INVALID, "lfg_upscale_edge: no shape table");
     for (size_t i = 0; i < kRows; ++i) host[i] = lfg::EdgeShape{rows[5 * i], rows[5 * i + 1], rows[5 * i + 2], rows[5 * i + 3], rows[5 * i + 4], {0, 0, 0}};
-    lfg::EdgeShape *d = nullptr;
-    LFG_HIP(ctx, hipMalloc((void **)&d, kRows * sizeof(lfg::EdgeShape)));
-    const hipError_t e = hipMemcpy(d, host.data(), kRows * sizeof(lfg::EdgeShape), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return fail_hip(ctx, e, "hipMemcpy(edge shapes)"); }
-    ctx->edge_shapes = d;
-    return LFG_OK;
+    uint8_t *d = nullptr;
+    const int rc = upload_table(ctx, host.data(), kRows * sizeof(lfg::EdgeShape), "edge shapes", &d);
+    if (rc == LFG_OK) ctx->edge_shapes = reinterpret_cast<lfg::EdgeShape *>(d);
+    return rc;
 }
 
 }  // namespace
@@ -2595,12 +2545,7 @@ LFG_EXPORT int lfg_upscale_edge(lfg_context *ctx, const lfg_frame *in, lfg_frame
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_upscale_edge: the output overlaps the input");
     if (out->width < in->width || out->height < in->height)
         return fail(ctx, LFG_ERR_UNSUPPORTED, "lfg_upscale_edge: the output is smaller than the input on an axis (lfg_resample shrinks)");
-    // bounded like the tap tables, and trimmed before either lookup so that the two of a call cannot free each other's
-    while (ctx->edge_positions.size() > 14) {
-        (void)sync_lanes(ctx);                                 // a queued kernel may still read it
-        (void)hipFree(ctx->edge_positions.front().d_base);
-        ctx->edge_positions.erase(ctx->edge_positions.begin());
-    }
+    trim_tables(ctx, ctx->edge_positions);
     lfg::EdgeAxis x{}, y{};
     rc = edge_position_table(ctx, in->width, out->width, &x);
     if (rc == LFG_OK) rc = edge_position_table(ctx, in->height, out->height, &y);
@@ -2637,19 +2582,19 @@ LFG_EXPORT int lfg_interpolate_scale(lfg_context *ctx, const lfg_frame *prev, co
         return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_scale: row pitch not a multiple of the pixel size");
     if (out->data == prev->data || out->data == curr->data)
         return fail(ctx, LFG_ERR_INVALID, "lfg_interpolate_scale: output aliases an input");
-    trim_axis_tables(ctx);
-    lfg::AxisTable *tx = nullptr, *ty = nullptr;
+    trim_tables(ctx, ctx->tables);
+    lfg::AxisTable tx, ty;
     int rc = build_axis_table(ctx, (int)curr->width, (int)out->width, &tx);
     if (rc != LFG_OK) return rc;
     rc = build_axis_table(ctx, (int)curr->height, (int)out->height, &ty);
     if (rc != LFG_OK) return rc;
-    const bool fused = ctx->fuse_interpolate_scale && tx->pattern_2x && ty->pattern_2x && tx->palette_rows > 0 && ty->strips_per_xcd > 0 && lfg::scale_2x_supported(*curr, *out) &&
+    const bool fused = ctx->fuse_interpolate_scale && tx.pattern_2x && ty.pattern_2x && tx.palette_rows > 0 && ty.strips_per_xcd > 0 && lfg::scale_2x_supported(*curr, *out) &&
                        (uint64_t)prev->height * prev->pitch < 0x7fffffffull;
     if (fused) {
         // one kernel: the generated frame is interpolated row by row inside the 2x scale kernel and never stored at
         // input resolution; accounted to the scale stage
         StageTimer timer(ctx, LFG_STAGE_SCALE);
-        hipError_t e = lfg::launch_interpolate_scale_2x(ctx->cur().stream, *prev, *curr, *mv, *out, *tx, *ty, factor, ctx->semantics != 0);
+        hipError_t e = lfg::launch_interpolate_scale_2x(ctx->cur().stream, *prev, *curr, *mv, *out, tx, ty, factor, ctx->semantics != 0);
         if (e != hipSuccess) return fail_hip(ctx, e, "fused interpolate + scale kernel launch");
         ctx->scale_last_kernel = 2;
         return LFG_OK;

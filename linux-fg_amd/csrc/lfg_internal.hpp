@@ -4,16 +4,27 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdint>
 #include <string>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "linuxfg_hip.h"
 #include "lfg_motion_verdict.hpp"
 #include "lfg_resample.hpp"
+#include "lfg_table_cache.hpp"
 #include "lfg_upscale_edge.hpp"
 
 namespace lfg {
+
+// What lfg_table_cache.hpp allocates, frees and copies with: the table caches' and the lane buffers' device.
+struct HipDevice {
+    static int allocate(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static int release(void *p) { return (int)hipFree(p); }
+    static int copy(void *dst, const void *host, size_t bytes) { return (int)hipMemcpy(dst, host, bytes, hipMemcpyHostToDevice); }
+};
 
 // Per-axis Lanczos tables for one (inSize -> outSize) resample, as shaders/scale.comp:24-41
 // computes them per output coordinate: first tap index (floor(pixelPos) - 2, unclamped) and six
@@ -22,7 +33,9 @@ namespace lfg {
 // the shader skips (scale.comp:34-37).
 struct AxisTable {
     int in_size = 0, out_size = 0;
+    std::pair<int, int> key() const { return {in_size, out_size}; }
     bool pattern_2x = false;      // start[2k] == k-3 and start[2k+1] == k-2 for every k
+    uint8_t *d_base = nullptr;    // ONE allocation: start | weight | class | palette, each at a multiple of 256 bytes (hipMalloc's own alignment)
     int *d_start = nullptr;       // [out_size]
     float *d_weight = nullptr;    // [out_size][6]
     // pattern_2x tables only.  At exact 2x the shader's per-column fp32 arithmetic yields a handful of DISTINCT weight
@@ -49,7 +62,9 @@ struct AxisTable {
 // consecutive quads and learns with one scalar load which of its lanes need the two-texel blends of interpolate.hip.
 struct UvTable {
     int size = 0;
-    float *d_uv = nullptr;          // [size rounded up to 4]; the base of ONE allocation that also holds the arrays below
+    int key() const { return size; }
+    uint8_t *d_base = nullptr;      // ONE allocation: uv | centre | goodMask
+    float *d_uv = nullptr;          // [size rounded up to 4]
     uint8_t *d_centre = nullptr;    // [size rounded up to 64]: 1 where the undisplaced sample of p is exactly texel p
     uint64_t *d_goodMask = nullptr; // [blocks]: bit l of word b: quad 64 b + l lies inside the axis and is all centres
     int blocks = 0;                 // ceil(quads / 64)
@@ -149,6 +164,7 @@ struct PyramidLayout {
 struct ResampleTable {
     int filter = 0;
     uint32_t in_size = 0, out_size = 0;
+    std::tuple<int, uint32_t, uint32_t> key() const { return {filter, in_size, out_size}; }
     uint8_t *d_base = nullptr;
     ResampleAxis axis{};
     ResamplePlan plan{};
@@ -158,7 +174,8 @@ struct ResampleTable {
 // the device in one allocation (lo | hi).
 struct ResampleBracketTable {
     uint32_t in_size = 0, out_size = 0;
-    int32_t *d_base = nullptr;
+    std::pair<uint32_t, uint32_t> key() const { return {in_size, out_size}; }
+    uint8_t *d_base = nullptr;
     ResampleBracket bracket{};
 };
 
@@ -166,6 +183,7 @@ struct ResampleBracketTable {
 // one allocation (base | frac).
 struct EdgePositionTable {
     uint32_t in_size = 0, out_size = 0;
+    std::pair<uint32_t, uint32_t> key() const { return {in_size, out_size}; }
     uint8_t *d_base = nullptr;
     EdgeAxis axis{};
 };
@@ -207,28 +225,24 @@ struct lfg_lane_state {
     lfg_frame half_prev{}, half_curr{}, mv_half{};   // ... and both frames halved and their vectors (lfg_set_half_resolution_motion), made on demand
     lfg_frame mid_tmp{};                       // temporary of lfg_interpolate_scale where the fused kernel does not apply
     // prefiltered motion path: scratch for one frame size, grown on demand
-    uint8_t *motion_ws = nullptr;
-    size_t motion_ws_bytes = 0;
+    lfg::DeviceBuffer motion_ws;
     uint32_t motion_ws_w = 0, motion_ws_h = 0;
     lfg::MotionWorkspaceLayout motion_ws_layout{};
     int motion_units = 0;                      // work units of the prefilter for the current workspace size
     // lfg_motion_pyramid: both frames' pyramids and the vector fields of levels 1 .. L, grown on demand
-    uint8_t *pyramid_ws = nullptr;
-    size_t pyramid_ws_bytes = 0;
+    lfg::DeviceBuffer pyramid_ws;
     // lfg_interpolate_compensated: the key image K of one factor (W * H words), grown on demand
-    uint32_t *mc_keys = nullptr;
-    size_t mc_keys_bytes = 0;
+    lfg::DeviceBuffer mc_keys;
     // lfg_set_hole_reach: the fill plane of that key image (W * H words), grown on demand
-    uint32_t *mc_fill = nullptr;
-    size_t mc_fill_bytes = 0;
+    lfg::DeviceBuffer mc_fill;
     // lfg_set_static_protection: the pair's static mask (W * H bytes), grown on demand
-    uint8_t *static_mask = nullptr;
-    size_t static_mask_bytes = 0;
+    lfg::DeviceBuffer static_mask;
     // lfg_set_subpixel_vectors: the quarter-pixel field of the pair (W x H MV_S16X2_Q2), made on demand, and
     // lfg_interpolate_compensated_subpel: the key image of that route (W * H 64-bit words), grown on demand
     lfg_frame mvq_tmp{};
-    unsigned long long *mcq_keys = nullptr;
-    size_t mcq_keys_bytes = 0;
+    lfg::DeviceBuffer mcq_keys;
+    // every DeviceBuffer above, for lane_release's one loop: a new one is added here, next to its declaration
+    std::array<lfg::DeviceBuffer *, 6> buffers() { return {&motion_ws, &pyramid_ws, &mc_keys, &mc_fill, &static_mask, &mcq_keys}; }
     hipEvent_t mark = nullptr;                 // lfg_lane_mark
     bool marked = false;
     lfg::MotionVerdictState verdict;           // the order kernel's verdict on the lane's last call (lfg_motion_verdict.hpp)
@@ -249,11 +263,12 @@ struct lfg_context {
     // lfg_motion_prediction_stats: calls whose verdict came back, and the guesses it contradicted (all lanes together)
     uint64_t pred_verdicts = 0, pred_lean_wrong = 0, pred_grid_wrong = 0, pred_second_wrong = 0;
     std::string error;
-    std::vector<lfg::AxisTable> tables;       // small cache, linear search
-    std::vector<lfg::UvTable> uv_tables;      // likewise (interpolate)
-    std::vector<lfg::ResampleTable> resample_tables;   // likewise (lfg_resample)
-    std::vector<lfg::ResampleBracketTable> resample_brackets;   // likewise (lfg_resample_antiring)
-    std::vector<lfg::EdgePositionTable> edge_positions;   // likewise (lfg_upscale_edge)
+    // the per-size tables (lfg_table_cache.hpp has the contract): scale, interpolate, lfg_resample, lfg_resample_antiring, lfg_upscale_edge
+    lfg::TableCache<lfg::AxisTable, lfg::HipDevice> tables;
+    lfg::TableCache<lfg::UvTable, lfg::HipDevice> uv_tables;
+    lfg::TableCache<lfg::ResampleTable, lfg::HipDevice> resample_tables;
+    lfg::TableCache<lfg::ResampleBracketTable, lfg::HipDevice> resample_brackets;
+    lfg::TableCache<lfg::EdgePositionTable, lfg::HipDevice> edge_positions;
     lfg::EdgeShape *edge_shapes = nullptr;     // lfg_upscale_edge_shapes on the device, made by the first lfg_upscale_edge
     int motion_slots = 0;                      // prefilter workgroups resident at once on this device (0 = not queried yet)
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)

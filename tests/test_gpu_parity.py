@@ -857,6 +857,29 @@ def test_interpolate_table_cache_survives_many_sizes(oracle):
         c.close()
 
 
+@pytest.mark.parametrize("kind", ["2x", "generic"])
+def test_scale_table_cache_survives_many_pairs(kind):
+    """The same arrangement on lfg_scale's cache of (in, out) axis tables, which holds 14: eight calls with sixteen distinct
+    pairs, so the ninth call's trim drops the first call's two and leaves the second call's width pair the oldest entry; the
+    ninth call takes that pair for its width and a new one for its height.  Every result is held to the float64 model, and the
+    ninth, byte for byte, to the same call on a context that has built nothing else."""
+    from linux_fg_amd import capi
+    two = kind == "2x"
+    calls = [(20 + i, 8 + i, 40 + 2 * i if two else 45 + 2 * i, 16 + 2 * i if two else 19 + 3 * i) for i in range(8)]
+    calls.append((calls[1][0], 19 if two else 16, calls[1][2], 38 if two else 50))
+    pairs = [p for (w, h, ow, oh) in calls for p in ((w, ow), (h, oh))]
+    assert len(set(pairs[:16])) == 16 and pairs[16] == pairs[2] and pairs[17] not in pairs[:16]
+    rng = np.random.default_rng(7)
+    with capi.Context(0) as c:
+        for (w, h, ow, oh) in calls:
+            src = rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8)
+            got = run_scale(c, src, ow, oh)
+            assert_matches_f64(got, f64.scale_f64(src, ow, oh), what=f"{kind} {w}x{h} -> {ow}x{oh}")
+    with capi.Context(0) as alone:
+        want = run_scale(alone, src, ow, oh)
+    assert (got == want).all(), first_bad(got, want)
+
+
 def test_interpolate_kats(ctx):
     W, H = 64, 24
     p, c = rand_frame(W, H), rand_frame(W, H)

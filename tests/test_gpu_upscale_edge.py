@@ -181,6 +181,21 @@ def test_three_lanes_give_the_same(ctx):
     three_lanes(ctx, frames, enqueue, alone)
 
 
+def test_position_cache_survives_many_pairs():
+    """The context keeps 14 position tables, for both axes together.  Eight calls with sixteen distinct (in, out) pairs: the
+    ninth call's trim drops the first call's two, which leaves the second call's width pair the oldest entry, and the ninth
+    call takes that pair for its width and a new one for its height -- whose table must not cost the width's its memory."""
+    cases = [(13 + i, 5 + i, 26 + 3 * i, 11 + 2 * i) for i in range(8)]
+    cases.append((cases[1][0], 23, cases[1][2], 57))
+    pairs = [p for (w, h, ow, oh) in cases for p in ((w, ow), (h, oh))]
+    assert len(set(pairs[:16])) == 16 and pairs[16] == pairs[2] and pairs[17] not in pairs[:16]
+    with capi.Context(0) as own:
+        for i, (w, h, ow, oh) in enumerate(cases):
+            frame = em.random_bytes(w, h, 700 + i)
+            got, want = gpu(own, frame, ow, oh), model(frame, ow, oh)
+            assert (got == want).all(), f"{w}x{h}->{ow}x{oh}: {first_bad(got, want)}"
+
+
 # ---- 5. validation launches nothing
 
 def test_invalid_arguments_launch_nothing(ctx):
