@@ -1028,6 +1028,38 @@ int  lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_y
  * padding. */
 int  lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int strength);
 
+/* Motion-compensated temporal denoising, opt-in, in the caller's loop.  No reference counterpart.  Every frame-taking stage
+ * thresholds per-pixel differences (the full search's exact-match shortcut, the match gate, the static mask, the cut
+ * statistics), and sensor or encoder noise is what exhausts those thresholds; this averages each pixel of the current frame
+ * with the content that the pair's vectors point at in one or two reference frames, where that content fits.  Integer
+ * arithmetic only; it depends on no setting of the context, lfg_set_semantics included.
+ *   Inputs: curr, out and refs[i] RGBA8, all W x H with W, H >= 1; mvs[i] LFG_FORMAT_MV_S8X2, W x H, on curr's grid as
+ *   lfg_motion(refs[i], curr) writes it, so that refs[i](q + v_i(q)) ~ curr(q) -- the match gate's reading; any byte values;
+ *   count = 1 or 2; 0 <= radius <= 2; 1 <= tolerance <= 1020; 0 <= strength <= 256; 0 <= limit <= 255.
+ *   Cost of reference i at pixel q (the convention of lfg_motion_refine's cost): c_i = the sum over texels r of the
+ *   (2 radius + 1)^2 window centred on q, and over the four channels, of |curr(r)_c - refs[i](r + v_i(q))_c|; texels r outside
+ *   the image are skipped, refs[i] outside the image reads as 0.  n = the number of window texels inside the image,
+ *   L = tolerance * n.
+ *   Weight: w_i = (strength * max(0, L - c_i)) >> 6, and w_i = 0 if q + v_i(q) lies outside the image.  D = L + sum w_i;
+ *   a_i = (256 * w_i) / D, the floor division of unsigned 32-bit values; a_0 = 256 - sum a_i.
+ *   Mix, per channel c, all four alike:  m_c = (a_0 * curr(q)_c + sum a_i * refs[i](q + v_i(q))_c + 128) >> 8;
+ *   out(q)_c = clamp(m_c, curr(q)_c - limit, curr(q)_c + limit).
+ *   Bounds: c_i <= 25,500, w_i <= 102,000, D <= 229,500, 256 * w_i < 2^32, a_0 >= 1: every intermediate fits 32 bits.
+ * Hence: strength = 0 or limit = 0 copies curr.  A reference whose window differs by `tolerance` or more per texel on average
+ * contributes nothing, so a wrong vector, an occlusion or a cut leaves curr as it is.  Every output byte lies within the range
+ * of the bytes mixed and within curr +- limit.  Identical references (a clean, correctly compensated stream) give out = curr.
+ * At strength 64 a perfect reference gets half the weight, at 192 three quarters: the recursive use, where refs[0] is the
+ * previous call's out and mvs[0] the field of lfg_motion(that out, curr), which the interpolator of the pair can use as well
+ * (INTEGRATION.md).
+ * Frames: rows 4-byte aligned, RGBA8 pitches multiples of 4; mv 2-byte aligned; out overlaps no byte of any input (a pixel
+ * reads its neighbours, so the call cannot run in place); offsets are size_t, as in lfg_sharpen.  Any violation, a NULL
+ * pointer (refs, mvs and their first `count` entries included) or NULL data, a wrong format or a parameter out of range returns
+ * LFG_ERR_INVALID before anything is enqueued, and latches a message.  LFG_FORMAT_MV_S16X2_Q2 fields are refused: a
+ * quarter-pixel variant is out of scope.  One launch on the selected lane; keeps no device memory; outside the stage timers.
+ * Only the W * 4 bytes of each output row are written, never the row padding. */
+int  lfg_denoise_temporal(lfg_context *ctx, const lfg_frame *curr, const lfg_frame *const *refs, const lfg_frame *const *mvs,
+                          int count, lfg_frame *out, int radius, int tolerance, int strength, int limit);
+
 /* Resampling with a choice of filter and anti-aliased downscaling.  No reference counterpart: lfg_scale is the reference's
  * scale.comp, six Lanczos-3 taps per axis at every ratio, which point-samples once the ratio is far below 1 (at 3:1 the
  * output centres fall on texel centres, where Lanczos-3 is an impulse).  lfg_scale stays as it is; this is a separate call.

@@ -230,6 +230,7 @@ SIGNATURES = {
     "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
     "lfg_rgba_to_nv12": (_i, [_vp, _FP, ctypes.POINTER(Nv12), _i, _i, _i]),
     "lfg_sharpen": (_i, [_vp, _FP, _FP, _i]),
+    "lfg_denoise_temporal": (_i, [_vp, _FP, ctypes.POINTER(_FP), ctypes.POINTER(_FP), _i, _FP, _i, _i, _i, _i]),
     "lfg_resample": (_i, [_vp, _FP, _FP, _i]),
     "lfg_resample_taps": (_i, [_i, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int16)]),
     "lfg_resample_antiring": (_i, [_vp, _FP, _FP, _i, _i]),
@@ -1038,6 +1039,18 @@ class Context:
         """lfg_sharpen: `src` sharpened into `dst` (both RGBA8, one size, no overlap), strength 0 .. MAX_SHARPEN, limited to
         the range of each pixel and its four neighbours; for presented frames only, never for one a motion stage reads."""
         self._check(self.lib.lfg_sharpen(self.h, ctypes.byref(src), ctypes.byref(dst), int(strength)), "lfg_sharpen")
+
+    def denoise_temporal(self, curr: Frame, refs, mvs, dst: Frame, radius: int = 1, tolerance: int = 32, strength: int = 192,
+                         limit: int = 255):
+        """lfg_denoise_temporal: `curr` mixed into `dst` with one or two reference frames `refs`, each displaced by its field of
+        `mvs` (MV_S8X2 on curr's grid, as motion(ref, curr) writes it), where the (2 radius + 1)^2 window fits within
+        `tolerance` per texel; no output byte leaves curr +- limit.  One launch on the selected lane."""
+        if len(refs) != len(mvs):
+            raise LfgError(f"denoise_temporal: {len(refs)} references and {len(mvs)} fields")
+        n = len(refs)
+        ref_ptrs, mv_ptrs = (_FP * n)(*[ctypes.pointer(f) for f in refs]), (_FP * n)(*[ctypes.pointer(f) for f in mvs])
+        self._check(self.lib.lfg_denoise_temporal(self.h, ctypes.byref(curr), ref_ptrs, mv_ptrs, n, ctypes.byref(dst), int(radius),
+                                                  int(tolerance), int(strength), int(limit)), "lfg_denoise_temporal")
 
     def resample(self, src: Frame, dst: Frame, filt: int):
         """lfg_resample: `src` resampled into `dst` (both RGBA8, any sizes, no overlap) under one of FILTER_*, anti-aliased where

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "lfg_bicubic.hpp"
+#include "lfg_denoise.hpp"
 #include "lfg_internal.hpp"
 #include "lfg_levels.hpp"
 
@@ -2238,6 +2239,45 @@ LFG_EXPORT int lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: the output overlaps the input");
     hipError_t e = lfg::launch_sharpen(ctx->cur().stream, *in, *out, strength);
     if (e != hipSuccess) return fail_hip(ctx, e, "sharpen kernel launch");
+    return LFG_OK;
+}
+
+// ---- motion-compensated temporal denoising (denoise.hip)
+
+LFG_EXPORT int lfg_denoise_temporal(lfg_context *ctx, const lfg_frame *curr, const lfg_frame *const *refs, const lfg_frame *const *mvs,
+                                    int count, lfg_frame *out, int radius, int tolerance, int strength, int limit) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (count < 1 || count > lfg::kDenoiseMaxRefs) return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: count must be 1 or 2");
+    if (!refs || !mvs) return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: refs and mvs must not be NULL");
+    if (!frame_ok(curr, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: curr and out must be non-empty RGBA8");
+    if (!same_size(curr, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: curr and out differ in size");
+    if ((curr->pitch | out->pitch) % 4u || ((uintptr_t)curr->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    if (frames_overlap(out, curr)) return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: out overlaps curr (it cannot run in place)");
+    for (int i = 0; i < count; ++i) {
+        if (mvs[i] && mvs[i]->format == LFG_FORMAT_MV_S16X2_Q2)
+            return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: quarter-pixel vectors (MV_S16X2_Q2) are not supported");
+        if (!frame_ok(refs[i], LFG_FORMAT_RGBA8_UNORM) || !frame_ok(mvs[i], LFG_FORMAT_MV_S8X2))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: every reference must be non-empty RGBA8 and every field MV_S8X2");
+        if (!same_size(curr, refs[i]) || !same_size(curr, mvs[i]))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: curr, the references and the fields differ in size");
+        if (refs[i]->pitch % 4u || (uintptr_t)refs[i]->data % 4u)
+            return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+        if (mvs[i]->pitch % 2u || (uintptr_t)mvs[i]->data % 2u)
+            return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: mv must be 2-byte aligned with a pitch that is a multiple of 2");
+        if (frames_overlap(out, refs[i]) || frames_overlap(out, mvs[i]))
+            return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: out overlaps a reference or a field");
+    }
+    if (radius < 0 || radius > lfg::kDenoiseMaxRadius) return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: radius must be in [0, 2]");
+    if (tolerance < 1 || tolerance > lfg::kDenoiseMaxTolerance)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: tolerance must be in [1, 1020]");
+    if (strength < 0 || strength > lfg::kDenoiseMaxStrength)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: strength must be in [0, 256]");
+    if (limit < 0 || limit > lfg::kDenoiseMaxLimit) return fail(ctx, LFG_ERR_INVALID, "lfg_denoise_temporal: limit must be in [0, 255]");
+    hipError_t e = lfg::launch_denoise_temporal(ctx->cur().stream, *curr, refs, mvs, count, *out, radius, tolerance, strength, limit);
+    if (e != hipSuccess) return fail_hip(ctx, e, "temporal denoise kernel launch");
     return LFG_OK;
 }
 
