@@ -18,19 +18,18 @@
 //     below, where the window is the kept sum plus the new one.  An item of the walk is a strip of 64 block columns by
 //     kSsimSegmentRows window rows, so kSsimSegmentRows + 1 block rows; its first block row only fills the kept sums.  Lanes
 //     past the last block column read the last one and their windows count nowhere.
-//   * Items go to waves in a grid-stride walk of a FIXED grid (kSsimGroupsPerCu workgroups of kSsimWaves waves per CU); every
-//     wave runs the host's `trips`, and whether an item exists, how many block rows it has and which lanes hold a window follow
-//     from the sizes alone.  The one data-dependent branch is wave-uniform: where N = D in every window of the wave (identical
-//     content: Q = 2^24) the 25 steps of the restoring division are skipped for that channel.
+//   * Items go to waves by lfg_record_plan.hpp's fixed grid and cursor, (segment, strip) per wave; every wave runs the host's
+//     `trips`, and whether an item exists, how many block rows it has and which lanes hold a window follow from the sizes
+//     alone.  The one data-dependent branch is wave-uniform: where N = D in every window of the wave (identical content:
+//     Q = 2^24) the 25 steps of the restoring division are skipped for that channel.
 //   * D < 2^58 and |N| <= D, so the division shifts a remainder below D left by one bit 24 times inside 64 bits.
-//   * The histogram: bin 64 (identical windows) is counted by ballot and population count into a wave-uniform scalar, as
-//     frame_diff.hip counts its zeros; the other bins go to a workgroup-private LDS histogram of 32-bit bins.  One merge per
-//     workgroup: 64-bit atomic adds of the sums and the non-empty bins, one 64-bit atomic minimum of the key.
+//   * The histogram: bin 64 (identical windows) is counted by ballot and population count into a wave-uniform scalar -- two
+//     frames that are the same put every window there; the other bins go to the workgroup's LDS bins.  The merge is
+//     lfg_record.hpp's, with one 64-bit atomic minimum for the key beside the sums.
 // No float anywhere.  All 71 results are integers: neither the walk nor the order of the atomics changes them.
-#include <algorithm>
-
 #include "lfg_internal.hpp"
-#include "lfg_device.hpp"
+#include "lfg_record.hpp"
+#include "lfg_record_plan.hpp"
 
 namespace lfg {
 namespace {
@@ -137,21 +136,17 @@ __global__ __launch_bounds__(kSsimThreads) void frame_ssim_kernel(
     if (tid < (uint32_t)kSsimBins) bins[tid] = 0u;
     __syncthreads();
 
-    // this wave's first item as (segment, strip): first / strips through the host's multiplier (launch_frame_ssim: exact for
-    // first < 2^31), then the step between its items, gridDim.x * kSsimWaves of them, as segments and a rest
-    const uint32_t first = blockIdx.x * (uint32_t)kSsimWaves + wave;
-    uint32_t segment = (uint32_t)(((unsigned long long)first * divMagic) >> divShift);
-    uint32_t strip = first - segment * strips;
+    RecordCursor<uint32_t> at = record_cursor<uint32_t>(blockIdx.x * (uint32_t)kSsimWaves + wave, strips, divMagic, divShift);      // (segment, strip)
 
     unsigned long long sum[4] = {0ull, 0ull, 0ull, 0ull};    // this lane's windows, two's complement
     unsigned long long best = ~0ull;                         // this lane's smallest key
     uint32_t identical = 0u;                                 // this wave's windows in bin 64 (wave-uniform)
     for (uint32_t t = 0; t < trips; ++t) {
-        if (segment < segments) {                            // wave-uniform
-            const uint32_t wx = strip * (uint32_t)kSsimStripWindows + lane;
+        if (at.major < segments) {                           // wave-uniform
+            const uint32_t wx = at.minor * (uint32_t)kSsimStripWindows + lane;
             const uint32_t bx = min(wx, bw - 1u);
             const bool column = lane < (uint32_t)kSsimStripWindows && wx + 1u < bw;
-            const uint32_t by0 = segment * (uint32_t)kSsimSegmentRows;
+            const uint32_t by0 = at.major * (uint32_t)kSsimSegmentRows;
             const uint32_t rows = min((uint32_t)kSsimSegmentRows + 1u, bh - by0);          // block rows: at least 2
             size_t aOff = (size_t)by0 * 4u * aPitch + (size_t)bx * 16u, bOff = (size_t)by0 * 4u * bPitch + (size_t)bx * 16u;
             uint32_t above[kSsimSums];
@@ -185,17 +180,12 @@ __global__ __launch_bounds__(kSsimThreads) void frame_ssim_kernel(
                 for (int i = 0; i < kSsimSums; ++i) above[i] = pair[i];
             }
         }
-        strip += stepStrip;
-        segment += stepSegment;
-        if (strip >= strips) { strip -= strips; ++segment; }
+        at.advance(stepSegment, stepStrip, strips);
     }
 
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum[c] += __shfl_xor(sum[c], o, 64);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
+    for (int c = 0; c < 4; ++c) sum[c] = wave_sum_u64(sum[c]);
+    best = wave_min_u64(best);
     if (lane == 0u) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) part[c][wave] = sum[c];
@@ -203,62 +193,43 @@ __global__ __launch_bounds__(kSsimThreads) void frame_ssim_kernel(
         if (identical != 0u) atomicAdd(&bins[64], identical);
     }
     __syncthreads();
-    // the record: windows, sum[4], hist[65], worst.  Empty sums and bins add nothing; results unused
+    // the record: windows, sum[4], hist[65], worst
     if (tid < 4u) {
-        unsigned long long s = 0ull;
-#pragma unroll
-        for (int w = 0; w < kSsimWaves; ++w) s += part[tid][w];
-        if (s != 0ull) atomicAdd(stats + 1 + tid, s);
+        record_add(stats + 1 + tid, group_sum_u64(part[tid]));
     } else if (tid == 4u) {
-        unsigned long long s = ~0ull;
-#pragma unroll
-        for (int w = 0; w < kSsimWaves; ++w) s = min(s, part[4][w]);
+        const unsigned long long s = group_min_u64(part[4]);
         if (s != ~0ull) atomicMin(stats + 5 + kSsimBins, s);
     } else if (tid == 5u) {
         if (blockIdx.x == 0) atomicAdd(stats, windows);      // onto the cleared word, or onto the record's own count
     }
     if (tid >= 64u && tid < 64u + (uint32_t)kSsimBins) {
-        const uint32_t n = bins[tid - 64u];
-        if (n != 0u) atomicAdd(stats + 5 + (tid - 64u), (unsigned long long)n);
+        record_add(stats + 5 + (tid - 64u), bins[tid - 64u]);
     }
 }
 
 }  // namespace
 
-// The clear unless the call accumulates (zeros, then all ones into `worst`), then one launch.  Workgroups: kSsimGroupsPerCu per
-// CU, never more than there are items -- and never so few that one of them would see more than kSsimGroupWindows windows.
+// The clear (zeros, then all ones into `worst`), then one launch of the fixed grid.
 hipError_t launch_frame_ssim(hipStream_t s, const lfg_frame &a, const lfg_frame &b, uint32_t channelMask, bool accumulate,
                              int deviceCus, void *stats) {
     const uint32_t bw = a.width >> 2, bh = a.height >> 2;
     if (bw < 2u || bh < 2u) return hipErrorInvalidValue;
-    const bool wide = (((uintptr_t)a.data | (uintptr_t)b.data | (uintptr_t)a.pitch | (uintptr_t)b.pitch) % 16u) == 0;
+    const bool wide = multiples_of_16(a.data, b.data, a.pitch, b.pitch);
     const unsigned long long windows = (unsigned long long)(bw - 1u) * (bh - 1u);
     const uint32_t strips = (bw - 1u + kSsimStripWindows - 1u) / kSsimStripWindows;
     const uint32_t segments = (bh - 1u + kSsimSegmentRows - 1u) / kSsimSegmentRows;
-    const unsigned long long items = (unsigned long long)strips * segments;
-    // a workgroup takes at most items / (grid * kSsimWaves) + 1 trips of kSsimWaves items of 63 x 8 windows each
-    const unsigned long long perTrip = (unsigned long long)kSsimWaves * kSsimStripWindows * kSsimSegmentRows;
-    const unsigned long long atLeast = items / (kSsimWaves * (kSsimGroupWindows / perTrip - 1ull)) + 1ull;
-    const unsigned long long fixed = (unsigned long long)std::max(deviceCus, 1) * kSsimGroupsPerCu;
-    const unsigned long long grid = std::max(std::min((items + kSsimWaves - 1) / kSsimWaves, fixed), atLeast);
-    const unsigned long long stride = grid * kSsimWaves;
-    const unsigned long long trips = (items + stride - 1) / stride;
-    if (stride + items > 0x80000000ull || trips > 0xffffffffull) return hipErrorInvalidValue;      // (no frame a device holds comes near)
-    // n / strips for every n < 2^31 as (n * magic) >> shift: with 2^(l-1) < strips <= 2^l, magic = ceil(2^(31+l) / strips)
-    // <= 2^32 and shift = 31 + l <= 63 (Granlund and Montgomery 1994, theorem 4.2); n * magic < 2^63
-    uint32_t l = 0;
-    while ((1ull << l) < (unsigned long long)strips) ++l;
-    const uint32_t divShift = 31u + l;
-    const unsigned long long divMagic = ((1ull << divShift) + strips - 1ull) / strips;
-    if (!accumulate) {
-        hipError_t e = hipMemsetAsync(stats, 0, offsetof(lfg_frame_ssim_stats, worst), s);
-        if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)stats + offsetof(lfg_frame_ssim_stats, worst), 0xFF, sizeof(uint64_t), s);
-        if (e != hipSuccess) return e;
-    }
+    RecordGrid g;                                            // an item is at most 63 x 8 windows
+    if (!record_fixed_grid<uint32_t>(strips, segments, kSsimWaves, 1, kSsimGroupsPerCu, deviceCus,
+                                     kSsimGroupWindows / (kSsimStripWindows * kSsimSegmentRows), g))
+        return hipErrorInvalidValue;
+    const RecordDivisor d = record_divisor(strips);
+    hipError_t e = record_clear(s, stats, offsetof(lfg_frame_ssim_stats, worst), accumulate);
+    if (e == hipSuccess && !accumulate) e = hipMemsetAsync((uint8_t *)stats + offsetof(lfg_frame_ssim_stats, worst), 0xFF, sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
     const auto kernel = wide ? frame_ssim_kernel<true> : frame_ssim_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(kSsimThreads), 0, s, (const uint8_t *)a.data, (size_t)a.pitch,
-                       (const uint8_t *)b.data, (size_t)b.pitch, bw, bh, strips, segments, divMagic, divShift,
-                       (uint32_t)(stride / strips), (uint32_t)(stride % strips), (uint32_t)trips, channelMask, windows,
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(kSsimThreads), 0, s, (const uint8_t *)a.data, (size_t)a.pitch,
+                       (const uint8_t *)b.data, (size_t)b.pitch, bw, bh, strips, segments, d.magic, d.shift,
+                       (uint32_t)(g.stride / strips), (uint32_t)(g.stride % strips), g.trips, channelMask, windows,
                        (unsigned long long *)stats);
     return hipGetLastError();
 }

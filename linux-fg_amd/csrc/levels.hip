@@ -7,25 +7,22 @@
 // levels_match_kernel     one workgroup: both records' running sums, both maps by bisection, the gate.
 // levels_apply_kernel     a map through every pixel of a frame, its 768 bytes staged (and for LFG_LEVELS_AT combined) in LDS.
 //
-// The histogram is frame_diff.hip's shape -- a FIXED grid, 32-bit workgroup-private LDS bins, one merge per workgroup with
-// 64-bit atomics whose results are unused -- with another walk and another answer to the one hazard of an LDS histogram:
-//   * The workgroup is a rectangle of lanes, bx wide and 1024 / bx high (launch_frame_histogram picks the power of two bx >= 64
-//     that wastes the fewest lanes on the frame's width), so a wave lies in ONE row, neither the walk nor a lane's address takes
-//     a division, and every lane of a wave runs the same trips: the ballots below see the whole wave.
+// The histogram is a record kernel: its row layout, its rectangle and its refusal are lfg_record_plan.hpp's (hist_row,
+// hist_grid), the LDS bins' one-lane add and the merge lfg_record.hpp's.  What is this file's:
+//   * The workgroup is a rectangle of lanes, bx wide and 1024 / bx high, so a wave lies in ONE row, neither the walk nor a
+//     lane's address takes a division, and every lane of a wave runs the same trips: the ballots see the whole wave.
 //   * An item is four pixels of one row through one 16-byte load where the row's base allows it, one pixel through a dword
 //     load otherwise.  With a pitch that is a multiple of 16 every row has the same 0 .. 3 pixels in front of its first
 //     16-byte boundary and the same 0 .. 3 behind its last: those are items of one pixel at the end of the row's items, in
 //     the same launch.  With any other pitch every item is one pixel.
-//   * All 64 lanes of a wave may hit one LDS word -- flat content, letterbox bars, an alpha channel that is 255 everywhere --
-//     and ds_add_u32 to one address serialises.  Per pixel and channel the wave therefore asks with one ballot whether all of
-//     its pixels share the level of the first; then one lane adds their number.  Only otherwise does every lane add 1 to its
-//     own bin.  The test is per channel because alpha is uniform in nearly every frame while colour is not.
+//   * The one-lane add is asked per pixel AND channel, because alpha is uniform in nearly every frame while colour is not.
 // No float anywhere but the one conversion of LFG_LEVELS_AT's factor on the host.  All results are integers: neither the walk
 // nor the order of the atomics changes them.
 #include <algorithm>
 
 #include "lfg_internal.hpp"
-#include "lfg_device.hpp"
+#include "lfg_record.hpp"
+#include "lfg_record_plan.hpp"
 #include "lfg_levels.hpp"
 
 namespace lfg {
@@ -42,23 +39,9 @@ constexpr unsigned long long kHistGroupPixels = 1ull << 31;
 __device__ __forceinline__ void count_word(uint32_t *__restrict__ bins, uint32_t p, bool valid, uint32_t lane) {
     const unsigned long long all = __ballot(valid);
     if (all == 0ull) return;                                 // wave-uniform
-    const int lead = __ffsll((long long)all) - 1;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const uint32_t b = (p >> (8 * c)) & 0xffu;
-        const uint32_t shared = (uint32_t)__builtin_amdgcn_readlane((int)b, lead);
-        if (__ballot(valid && b == shared) == all) {         // wave-uniform
-            if ((int)lane == lead) atomicAdd(&bins[c * kLevels + shared], (uint32_t)__popcll(all));
-        } else if (valid) {
-            atomicAdd(&bins[c * kLevels + b], 1u);
-        }
-    }
+    for (int c = 0; c < 4; ++c) bins_add(bins + c * kLevels, (p >> (8 * c)) & 0xffu, valid, valid, all, lane);
 }
-
-// Item g of a row: the 16-byte items first, then the pixels in front of them and behind them.
-struct HistRow {
-    uint32_t W, itemsX, wideItems, head, tail;              // head + 4 * wideItems + tail = W
-};
 
 __global__ __launch_bounds__(kHistThreads) void frame_histogram_kernel(
         const uint8_t *__restrict__ frame, size_t pitch, uint32_t H, HistRow r, uint32_t lgBx, unsigned long long pixels,
@@ -75,9 +58,7 @@ __global__ __launch_bounds__(kHistThreads) void frame_histogram_kernel(
     for (unsigned long long g0 = (unsigned long long)blockIdx.x * bx; g0 < r.itemsX; g0 += gStep) {
         const unsigned long long g = g0 + tx;
         const bool inRow = g < r.itemsX, wide = g < r.wideItems;
-        // the item's first pixel: 16-byte item g, or pixel e of the head and the tail
-        const uint32_t e = (uint32_t)g - r.wideItems;
-        const uint32_t x = wide ? r.head + 4u * (uint32_t)g : (e < r.head ? e : r.W - r.tail + (e - r.head));
+        const uint32_t x = hist_item_x(r, (uint32_t)g, wide);                   // the item's first pixel
         for (unsigned long long y0 = (unsigned long long)blockIdx.y * by * kHistUnroll; y0 < H; y0 += rowStep) {
             uint32_t p[kHistUnroll][4];
             bool item[kHistUnroll];
@@ -106,11 +87,8 @@ __global__ __launch_bounds__(kHistThreads) void frame_histogram_kernel(
     }
 
     __syncthreads();
-    // the record: pixels, hist[4][256].  Empty bins add nothing; results unused: global_atomic_add_x2
-    for (uint32_t i = tid; i < (uint32_t)kHistBins; i += kHistThreads) {
-        const uint32_t n = bins[i];
-        if (n != 0u) atomicAdd(stats + 1 + i, (unsigned long long)n);
-    }
+    // the record: pixels, hist[4][256]
+    for (uint32_t i = tid; i < (uint32_t)kHistBins; i += kHistThreads) record_add(stats + 1 + i, bins[i]);
     if (tid == 0u && blockIdx.x == 0 && blockIdx.y == 0) atomicAdd(stats, pixels);   // onto the cleared word, or the record's own count
 }
 
@@ -122,7 +100,7 @@ __global__ __launch_bounds__(kMatchThreads) void levels_match_kernel(const unsig
                                                                      const unsigned long long *__restrict__ to, int minShift16,
                                                                      uint8_t *__restrict__ map) {
     __shared__ uint64_t cdf[2][kLevelChannels][kLevels];     // [0]: from, [1]: to; the histograms, then their running sums
-    __shared__ uint64_t part[kMatchThreads / 64];
+    __shared__ unsigned long long part[kMatchThreads / 64];
     const uint32_t v = threadIdx.x;
     uint64_t own[kLevelChannels];                            // from's histogram at this thread's level
 #pragma unroll
@@ -145,13 +123,10 @@ __global__ __launch_bounds__(kMatchThreads) void levels_match_kernel(const unsig
         inv[c] = levels_rank(cdf[0][c], cdf[1][c][v]);
         shift += levels_shift(own[c], fwd[c], v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) shift += __shfl_xor((unsigned long long)shift, o, 64);
+    shift = wave_sum_u64(shift);
     if ((v & 63u) == 0u) part[v >> 6] = shift;
     __syncthreads();
-    uint64_t shiftSum = 0;
-#pragma unroll
-    for (int w = 0; w < kMatchThreads / 64; ++w) shiftSum += part[w];
+    const uint64_t shiftSum = group_sum_u64(part);
     const uint64_t pixels = from[0];
     const bool active = levels_active(pixels, to[0], shiftSum, minShift16);
     uint8_t *forward = map + kMapHeadBytes, *inverse = forward + kLevelChannels * kLevels;
@@ -172,13 +147,6 @@ __global__ __launch_bounds__(kMatchThreads) void levels_match_kernel(const unsig
 
 constexpr int kApplyThreads = 256;
 constexpr int kApplyGroups = 2048;                          // workgroups of the grid at most: each stages the table once
-
-// A 16-byte store and the wait states a store of more than 8 bytes needs before its data registers may be rewritten
-// (lfg_device.hpp: store_b128_guarded has the story; sharpen.hip stores the same way, through a 64-bit address).
-__device__ __forceinline__ void store_16_guarded(uint8_t *p, uint4 q) {
-    *reinterpret_cast<uint4 *>(p) = q;
-    asm volatile("s_nop 1" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w) : "memory");
-}
 
 // `in` and `out` may be the same frame: every pixel is read before it is written, by the lane that writes it.
 // wideItems: the 16-byte items of a row (the host passes 0 unless base and pitch of both frames are multiples of 16); the
@@ -213,41 +181,16 @@ __global__ __launch_bounds__(kApplyThreads) void levels_apply_kernel(const uint8
 
 }  // namespace
 
-// The clear unless the call accumulates, then one launch of the fixed grid.
+// The clear, then one launch of the fixed grid.
 hipError_t launch_frame_histogram(hipStream_t s, const lfg_frame &frame, bool accumulate, int deviceCus, void *stats) {
     const uint32_t W = frame.width, H = frame.height;
-    HistRow r{};
-    r.W = W;
-    if (frame.pitch % 16u == 0u) {                           // every row meets its first 16-byte boundary after the same pixels
-        r.head = std::min<uint32_t>((uint32_t)((0u - (uintptr_t)frame.data) & 15u) / 4u, W);
-        r.wideItems = (W - r.head) / 4u;
-        r.tail = W - r.head - 4u * r.wideItems;
-    } else {
-        r.head = W;
-    }
-    r.itemsX = r.wideItems + r.head + r.tail;
-    // the workgroup's rectangle: the power of two bx in [64, 1024] whose multiples cover itemsX with the fewest idle lanes
-    uint32_t lgBx = 6;
-    unsigned long long best = ~0ull;
-    for (uint32_t lg = 6; lg <= 10; ++lg) {
-        const unsigned long long bx = 1ull << lg, cover = ((unsigned long long)r.itemsX + bx - 1) / bx * bx;
-        if (cover <= best) { best = cover; lgBx = lg; }       // ties: the wider one, whose workgroup reads longer runs
-    }
-    const unsigned long long bx = 1ull << lgBx, by = (unsigned long long)kHistThreads >> lgBx;
-    const unsigned long long fixed = (unsigned long long)std::max(deviceCus, 1) * kHistGroupsPerCu;
-    const unsigned long long groupsX = std::min(((unsigned long long)r.itemsX + bx - 1) / bx, fixed);
-    const unsigned long long rowTrips = ((unsigned long long)H + by * kHistUnroll - 1) / (by * kHistUnroll);
-    unsigned long long groupsY = std::min(std::max(fixed / groupsX, 1ull), std::min(rowTrips, 65535ull));
-    // a workgroup sees at most its trips along the row times its trips down the frame times its lanes, of at most 4 pixels each
-    const unsigned long long tripsX = ((unsigned long long)r.itemsX + groupsX * bx - 1) / (groupsX * bx);
-    const unsigned long long tripsY = (rowTrips + groupsY - 1) / groupsY;
-    if (tripsX * tripsY > kHistGroupPixels / (4ull * kHistThreads * kHistUnroll)) return hipErrorInvalidValue;   // (no frame a device holds comes near)
-    if (!accumulate) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(lfg_frame_histogram_stats), s);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(frame_histogram_kernel, dim3((uint32_t)groupsX, (uint32_t)groupsY), dim3(kHistThreads), 0, s,
-                       (const uint8_t *)frame.data, (size_t)frame.pitch, H, r, lgBx, (unsigned long long)W * H, (unsigned long long *)stats);
+    const HistRow r = hist_row(frame.data, frame.pitch, W);
+    HistGrid g;
+    if (!hist_grid(r.itemsX, H, kHistThreads, kHistUnroll, kHistGroupsPerCu, deviceCus, kHistGroupPixels, g)) return hipErrorInvalidValue;
+    const hipError_t e = record_clear(s, stats, sizeof(lfg_frame_histogram_stats), accumulate);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(frame_histogram_kernel, dim3(g.groupsX, g.groupsY), dim3(kHistThreads), 0, s, (const uint8_t *)frame.data,
+                       (size_t)frame.pitch, H, r, g.lgBx, (unsigned long long)W * H, (unsigned long long *)stats);
     return hipGetLastError();
 }
 
@@ -259,8 +202,7 @@ hipError_t launch_levels_match(hipStream_t s, const void *from, const void *to, 
 
 hipError_t launch_levels_apply(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const void *map, int mode, int tq) {
     const uint32_t W = in.width, H = in.height;
-    const bool wide = (((uintptr_t)in.data | (uintptr_t)out.data | (uintptr_t)in.pitch | (uintptr_t)out.pitch) % 16u) == 0;
-    const uint32_t wideItems = wide ? W / 4u : 0u;
+    const uint32_t wideItems = wide_columns(multiples_of_16(in.data, out.data, in.pitch, out.pitch), W) / 4u;
     const unsigned long long itemsX = (unsigned long long)wideItems + (W - 4u * wideItems);
     const unsigned long long groupsX = std::min((itemsX + kApplyThreads - 1) / kApplyThreads, (unsigned long long)kApplyGroups);
     const unsigned long long groupsY = std::min<unsigned long long>(H, std::max((unsigned long long)kApplyGroups / groupsX, 1ull));

@@ -124,6 +124,14 @@ __device__ __forceinline__ void store_b128_guarded(u32x4_store q, __amdgpu_buffe
 #endif
 }
 
+// The same store and wait states through a 64-bit address instead of a buffer descriptor and its 32-bit offset (sharpen.hip,
+// levels.hip).  The data registers are an input of the wait states here too, and the "memory" clobber keeps the store in
+// front of them.
+__device__ __forceinline__ void store_16_guarded(uint8_t *p, uint4 q) {
+    *reinterpret_cast<uint4 *>(p) = q;
+    asm volatile("s_nop 1" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w) : "memory");
+}
+
 // Orders this wave's LDS traffic for cross-lane exchange inside ONE wave: a wavefront-scope fence
 // keeps the compiler from moving a lane's LDS reads above its own LDS write (they never alias for
 // the same lane, but they do across lanes); the hardware executes one wave's LDS ops in order.

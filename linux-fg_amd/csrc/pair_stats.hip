@@ -6,20 +6,21 @@
 // cut_fallback_kernel reads that record on the device; a pair that is no cut costs the launch and one load per wave, a cut
 //                     copies prev or curr over every output.  The host never learns the verdict here.
 //
-// pair_match_kernel has a FIXED grid (a few workgroups per CU, launch_pair_match), not one workgroup per tile: a workgroup's
-// cost at the end is two 64-bit atomics into the same two words, and at 4K a grid of tiles would be 32,400 of them.  Each
-// workgroup walks the 64 x 4 tiles blockIdx.x, blockIdx.x + gridDim.x, ...; a wave is 64 pixels of one row.  Per tile every
-// lane loads its vector, then curr and the gathered prev texel -- unconditionally, from clamped positions, the outside value
-// selected afterwards (lfg_device.hpp: texel_or_zero), two tiles per trip so that four waves keep sixteen loads in flight.
-// Partial sums stay in registers: the SAD per lane, the matched count per wave (ballot + population count, a scalar).  Both
-// are 64-bit, so no frame size can wrap them.  At the end: wave reduction, four values through LDS, one pair of atomicAdd.
+// pair_match_kernel is a record kernel with a FIXED grid (lfg_record_plan.hpp: pair_grid), not one workgroup per tile: a
+// workgroup's cost at the end is two 64-bit atomics into the same two words, and at 4K a grid of tiles would be 32,400 of
+// them.  Each workgroup walks the 64 x 4 tiles blockIdx.x, blockIdx.x + gridDim.x, ...; a wave is 64 pixels of one row.  Per
+// tile every lane loads its vector, then curr and the gathered prev texel -- unconditionally, from clamped positions, the
+// outside value selected afterwards (lfg_device.hpp: texel_or_zero), two tiles per trip so that four waves keep sixteen loads
+// in flight.  Partial sums stay in registers: the SAD per lane, the matched count per wave (ballot + population count, a
+// scalar).  Both are 64-bit, so no frame size can wrap them.  The wave sum and the merge are lfg_record.hpp's.
 // All three results are integers: neither the walk nor the order of the atomics changes them.
 //
 // Traffic per pixel: 2 (mv) + 4 (curr) + 4 (gathered prev) = 10 bytes, 83 MB at 4K.
 #include <algorithm>
 
 #include "lfg_internal.hpp"
-#include "lfg_device.hpp"
+#include "lfg_record.hpp"
+#include "lfg_record_plan.hpp"
 #include "lfg_vector_word.hpp"
 
 namespace lfg {
@@ -71,17 +72,13 @@ __global__ __launch_bounds__(kPairBlockX * kPairBlockY) void pair_match_kernel(
             hits += (unsigned long long)__popcll(__ballot(inTile[k] && s <= matchSad));
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sad += __shfl_xor(sad, o, 64);
+    sad = wave_sum_u64(sad);
     if (threadIdx.x == 0) { part[0][threadIdx.y] = hits; part[1][threadIdx.y] = sad; }
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) {
-        unsigned long long m = 0ull, s = 0ull;
-#pragma unroll
-        for (int w = 0; w < kPairBlockY; ++w) { m += part[0][w]; s += part[1][w]; }
         if (blockIdx.x == 0) stats[0] = (unsigned long long)W * (unsigned long long)H;
-        atomicAdd(stats + 1, m);                             // results unused: two global_atomic_add_x2
-        atomicAdd(stats + 2, s);
+        atomicAdd(stats + 1, group_sum_u64(part[0]));        // results unused: two global_atomic_add_x2
+        atomicAdd(stats + 2, group_sum_u64(part[1]));
     }
 }
 
@@ -122,18 +119,16 @@ __global__ __launch_bounds__(kCutThreads) void cut_fallback_kernel(
 
 }  // namespace
 
-// Workgroups of pair_match_kernel: kPairGroupsPerCu per CU, never more than there are tiles (pairs of tiles per trip).
+// The clear, then one launch of the fixed grid.
 hipError_t launch_pair_match(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, const lfg_frame &mv, int matchSad,
                              int deviceCus, void *stats) {
     const int W = (int)curr.width, H = (int)curr.height;
-    const uint32_t tilesX = (uint32_t)((W + kPairBlockX - 1) / kPairBlockX), tiles = tilesX * (uint32_t)((H + kPairBlockY - 1) / kPairBlockY);
-    const uint32_t trips = (tiles + kPairUnroll - 1) / kPairUnroll;
-    const uint32_t grid = std::min<uint32_t>(trips, (uint32_t)std::max(deviceCus, 1) * kPairGroupsPerCu);
-    hipError_t e = hipMemsetAsync(stats, 0, sizeof(lfg_pair_stats), s);
+    const PairGrid g = pair_grid(curr.width, curr.height, kPairBlockX, kPairBlockY, kPairUnroll, kPairGroupsPerCu, deviceCus);
+    const hipError_t e = record_clear(s, stats, sizeof(lfg_pair_stats), false);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pair_match_kernel, dim3(grid), dim3(kPairBlockX, kPairBlockY), 0, s, (const uint8_t *)prev.data,
+    hipLaunchKernelGGL(pair_match_kernel, dim3(g.grid), dim3(kPairBlockX, kPairBlockY), 0, s, (const uint8_t *)prev.data,
                        (size_t)prev.pitch, (const uint8_t *)curr.data, (size_t)curr.pitch, (const uint8_t *)mv.data, (size_t)mv.pitch,
-                       W, H, tilesX, tiles, (uint32_t)matchSad, (unsigned long long *)stats);
+                       W, H, g.tilesX, g.tiles, (uint32_t)matchSad, (unsigned long long *)stats);
     return hipGetLastError();
 }
 

@@ -8,7 +8,7 @@
 //   * An item is four pixels of one row through one 16-byte load and one 16-byte store (kWide), chosen by the host when base
 //     and pitch of BOTH frames are multiples of 16; otherwise an item is one pixel through dword accesses.  An item is never
 //     partial: of a width that is no multiple of 4 the wide launch takes the columns up to the last multiple, and a second
-//     launch of the dword kernel the 1 .. 3 columns that remain (launch_sharpen; frame_diff.hip has the same arrangement).
+//     launch of the dword kernel the 1 .. 3 columns that remain (launch_sharpen; lfg_record_plan.hpp: wide_columns).
 //   * A lane takes a STRIP of kSharpenRows rows of its item, top to bottom: the kSharpenRows + 2 rows it needs (one halo row
 //     above and one below, clamped to the frame) are each loaded once, all of them before the first use of any, so a lane has
 //     its whole strip in flight at once; rows y - 1, y, y + 1 of an output row are then registers.  Per strip 10 rows are
@@ -28,6 +28,7 @@
 #include "lfg_internal.hpp"                                 // own stand-ins for what these two headers and the HIP runtime give them
 #include "lfg_device.hpp"
 #endif
+#include "lfg_record_plan.hpp"                              // (standard library only: the host build takes it as well)
 
 namespace lfg {
 namespace {
@@ -70,17 +71,6 @@ __host__ __device__ __forceinline__ uint32_t sharpen_texel(uint32_t c, uint32_t 
                                         (int)((e >> k) & 255u), strength) << k;
     return px;
 }
-
-#ifndef LFG_SHARPEN_ON_HOST
-// A 16-byte store and the wait states a store of more than 8 bytes needs before its data registers may be rewritten
-// (lfg_device.hpp: store_b128_guarded has the story; that one goes through a buffer descriptor and its 32-bit offset, this
-// one through a 64-bit address).  The data registers are an input of the wait states, and the "memory" clobber keeps the
-// store in front of them.
-__device__ __forceinline__ void store_16_guarded(uint8_t *p, uint4 q) {
-    *reinterpret_cast<uint4 *>(p) = q;
-    asm volatile("s_nop 1" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w) : "memory");
-}
-#endif
 
 #ifndef LFG_SHARPEN_ON_HOST
 // threadIdx.y is the same for the 64 lanes of a wave (the workgroup is 64 wide), which the compiler cannot know: said
@@ -159,8 +149,7 @@ inline SharpenPart sharpen_part(bool wide, uint32_t xFirst, uint32_t cols, uint3
 }
 
 inline int sharpen_parts(const void *in, size_t inPitch, const void *out, size_t outPitch, uint32_t W, uint32_t H, SharpenPart (&parts)[2]) {
-    const bool wide = (((uintptr_t)in | (uintptr_t)out | (uintptr_t)inPitch | (uintptr_t)outPitch) % 16u) == 0 && W >= 4u;
-    const uint32_t wideW = wide ? W & ~3u : 0u;
+    const uint32_t wideW = wide_columns(multiples_of_16(in, out, inPitch, outPitch), W);
     int n = 0;
     if (wideW != 0u) parts[n++] = sharpen_part(true, 0u, wideW, H);
     if (wideW != W) parts[n++] = sharpen_part(false, wideW, W - wideW, H);

@@ -3,14 +3,15 @@
 //
 // static_mask_kernel  a thread takes four adjacent pixels of one row: one v_sad_u8 per pixel against the tolerance, and the four
 //                     mask bytes leave as one dword where the mask's row puts them on a 4-byte boundary, as four bytes
-//                     otherwise.  kWide -- chosen by the host when the base and the pitch of BOTH frames are multiples of 16,
-//                     as frame_diff.hip chooses -- loads the four texels of a frame with one 16-byte load, otherwise with four
-//                     dword loads.  The last 1 .. 3 columns of a width that is no multiple of 4 go pixel by pixel on either path.
+//                     otherwise.  kWide -- chosen by the host when the base and the pitch of BOTH frames are multiples of 16
+//                     (lfg_record_plan.hpp: multiples_of_16) -- loads the four texels of a frame with one 16-byte load, otherwise
+//                     with four dword loads.  The last 1 .. 3 columns of a width that is no multiple of 4 go pixel by pixel on either path.
 // No store wider than 4 bytes.  Integer arithmetic only.
 //
 // Traffic per pixel: 4 (prev) + 4 (curr) + 1 (mask) = 9 bytes, 75 MB at 4K.
 #include "lfg_internal.hpp"
 #include "lfg_device.hpp"
+#include "lfg_record_plan.hpp"
 
 namespace lfg {
 namespace {
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kMaskBlockX * kMaskBlockY) void static_mask_kernel(
 
 hipError_t launch_static_mask(hipStream_t s, const lfg_frame &prev, const lfg_frame &curr, int tolerance, const lfg_mask &out) {
     const int W = (int)curr.width, H = (int)curr.height;
-    const bool wide = (((uintptr_t)prev.data | (uintptr_t)curr.data | (uintptr_t)prev.pitch | (uintptr_t)curr.pitch) % 16u) == 0;
+    const bool wide = multiples_of_16(prev.data, curr.data, prev.pitch, curr.pitch);
     const int perBlock = kMaskBlockX * kMaskPixels;
     const dim3 block(kMaskBlockX, kMaskBlockY), grid((unsigned)((W + perBlock - 1) / perBlock), (unsigned)((H + kMaskBlockY - 1) / kMaskBlockY));
     const auto kernel = wide ? static_mask_kernel<true> : static_mask_kernel<false>;
