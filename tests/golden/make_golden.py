@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Generates tests/golden/golden_small.npz from the CPU oracle (oracle/lfg_oracle.c).
 
-The reference has no golden vectors of its own and cannot run in this image, so
-these fixtures pin the ORACLE'S OWN behaviour, not the reference's: they catch accidental changes
-of the oracle and give the GPU tests a fixed target that does not depend on rebuilding it.
+The reference has no golden vectors of its own and cannot run as Vulkan in this image.  These fixtures are
+written by the oracle, and they are also what the reference's own shaders give: tests/test_reference_shaders.py runs the shader
+text on the CPU (oracle/ref_recipe.py) and holds every output in this file to a fresh run of it.  So they catch accidental
+changes of the oracle, pin it to the executed shaders, and give the GPU tests a fixed target that needs neither rebuilt.
+What golden_small.npz lacks is in ref_shaders.npz (make_ref_golden.py).
 Inputs: 64x36 seeded synthetic frames (linux-fg_amd/synth.py).  Outputs: scale to 128x72,
 motion (blockSize 8, searchRadius 16) and interpolate (t = 0.25, 0.5, 0.75) on the 128x72 frames.
 

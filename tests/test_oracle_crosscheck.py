@@ -1,7 +1,8 @@
 """oracle/lfg_oracle.c against the independently written numpy restatement: bit-for-bit.
 
-Two separately written restatements of the same shader text agreeing exactly is the
-strongest pin available while the reference itself cannot run here.  CPU only.
+Two separately written restatements of the same shader text agreeing exactly was the
+strongest pin while nothing of the reference ran here; the shader text itself
+now runs on the CPU, and tests/test_reference_shaders.py holds the oracle to it.  CPU only.
 """
 import numpy as np
 import pytest
