@@ -45,6 +45,9 @@ __device__ __forceinline__ uint32_t pack_rgba8_unorm(float r, float g, float b, 
     return pack_rgba8_255(r * 255.0f, g * 255.0f, b * 255.0f, a * 255.0f);
 }
 
+// What follows up to wave_lds_sync, and wave_max_u32 below, is gfx950's own (format loads, buffer stores, inline assembly, wave
+// lockstep) and is left out where tests/cpp/hip_on_host compiles this header for the CPU; under hipcc the guard does nothing.
+#ifndef LFG_ON_HOST
 // ---- typed buffer loads: the texture-address unit converts RGBA8 UNORM to four floats on the way in.
 // Measured on gfx950 (tools/probe_unorm.hip): the conversion is bit-exact (float)k / 255.0f for all
 // 256 byte values, i.e. oracle choice (1), at zero VALU cost.  hipcc exposes no builtin for the format
@@ -140,6 +143,8 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+#endif  // LFG_ON_HOST
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // A packed RGBA8 texel as one dword, what the opt-in stages compare with v_sad_u8: img(x, y), 0 outside the image, two ways.
@@ -158,6 +163,7 @@ __device__ __forceinline__ uint32_t texel_or_zero(const uint8_t *__restrict__ im
     return in ? t : 0u;
 }
 
+#ifndef LFG_ON_HOST
 // The largest of a wave's 64 unsigned values, as a wave-uniform (scalar) result.  Six DPP steps in the VALU -- within
 // quads (quad_perm), within half rows and rows (row_half_mirror, row_mirror), then across rows (row_bcast15, row_bcast31:
 // lane 63 ends up with everything) -- instead of six ds_bpermute round trips through the LDS pipeline, which is what
@@ -177,5 +183,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     v = step(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xC>{});   // row_bcast31 into rows 2 and 3
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
+
+#endif  // LFG_ON_HOST
 
 }  // namespace lfg
