@@ -1028,6 +1028,58 @@ int  lfg_yuv_coefficients(int matrix, int range, int32_t to_rgb[5], int32_t to_y
  * padding. */
 int  lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int strength);
 
+/* Debanding with dithered output of a presented frame, opt-in.  No reference counterpart.  Captured games and 8-bit video
+ * carry gradients quantised to one level per band; upscaling widens the bands, lfg_sharpen leaves ramps alone and
+ * lfg_denoise_temporal removes the noise that hid the steps.  This replaces a pixel by the average of four random taps
+ * around it where that average is close to the pixel -- with two more bits than a byte has -- and dithers the result back to
+ * 8 bits.  Integer arithmetic only; it depends on no setting of the context.
+ *   Inputs: in, out RGBA8, both W x H with W, H >= 1;
+ *     iterations I: 1 <= I <= 4;  threshold T: 0 <= T <= 64, in quarters of a level;  radius R: 1 <= R <= 32;
+ *     grain G: 0 <= G <= 16, in quarters of a level;  seed: any value.
+ *   The random source is h(k), all in uint32 arithmetic:
+ *     k ^= k >> 16;  k *= 0x7feb352d;  k ^= k >> 15;  k *= 0x846ca68b;  k ^= k >> 16.
+ *   For pixel (x, y) -- coordinates relative to the frame the caller described: a view made with lfg_frame_wrap is its own
+ *   image, and nothing outside it is read -- r0 = h(x ^ h(y ^ h(seed))) and r_j = h(r0 + j).
+ *   Channels 0, 1 and 2 are processed as follows; channel 3 is copied.
+ *     1. v = 4 in(x, y)_c.
+ *     2. For i = 1 .. I, with S = R i:
+ *          ox = (((r_i & 0xFFFF) (2 S + 1)) >> 16) - S,  oy = (((r_i >> 16) (2 S + 1)) >> 16) - S;
+ *          s = the sum of in_c at (x + ox, y + oy), (x - ox, y - oy), (x - oy, y + ox) and (x + oy, y - ox), every
+ *          coordinate clamped to the frame;
+ *          T_i = T / i (integer division);  if |s - v| <= T_i then v = s.
+ *        The taps always come from `in`, never from a partial result: no pixel depends on another pixel's output, and no
+ *        tiling or evaluation order changes a byte.
+ *     3. Noise: b_c = byte c of r_5;  n_c = ((b_c (4 + 2 G)) >> 8) - G, which lies in [-G, G + 3] with mean 1.5.  At G = 0
+ *        it is the unbiased stochastic rounding of a value with two fractional bits.
+ *     4. out(x, y)_c = clamp((v + n_c) >> 2, 0, 255), >> the arithmetic shift (floor).
+ *   The multiplies are 16 bits x at most 257 and 8 bits x at most 36: every intermediate but h's fits 24 bits.
+ * Hence: a pixel whose v was never replaced comes out as it went in when G = 0 (v = 4 in, n in 0 .. 3).  T = 0 with G = 0
+ * copies the frame (s = v = 4 in is the only sum accepted).  Flat areas and hard steps do not move: in a flat area every s
+ * equals v, and between two flat areas more than T levels apart a sum with a tap on the other side differs from v by at least
+ * that step and is refused.  After the iterations
+ * |v - 4 in| <= T_1 + ... + T_I, so every output lies within ceil((sum T_i + G + 3) / 4) levels of its input.  Alpha never
+ * changes.  The same seed repeats the same bytes; the caller changes it per presented frame so that the dither does not
+ * stand still.
+ * Where: at the presentation end only, after lfg_sharpen, on a copy.  A frame that a motion, mask, cut, level, denoise or
+ * interpolation call will read must stay as it is: dither noise defeats the exact-match shortcut and exhausts every threshold
+ * on per-pixel differences.
+ * Frames: in and out both RGBA8 and both W x H with W, H >= 1; rows 4-byte aligned, the pitch a multiple of 4; out overlaps no
+ * byte of in (every output depends on taps up to R I pixels away, so the call cannot run in place); frames of 2 GiB and more
+ * are addressed with size_t offsets.  Any violation, a NULL pointer or NULL data, a wrong format or a parameter outside its
+ * range returns LFG_ERR_INVALID before anything is enqueued, and latches a message.  Enqueued on the selected lane (one launch
+ * through 16-byte accesses where base and pitch of both frames are multiples of 16, with a second one for the 1 .. 3 columns
+ * past the last multiple of 4; one launch through 4-byte accesses otherwise); keeps no device memory; outside the stage
+ * timers (like a conversion it is no stage of the path).  Only the W * 4 bytes of each output row are written, never the row
+ * padding.
+ *   lfg_deband_draw writes the draw of one pixel: offsets = ox_1, oy_1, ... ox_4, oy_4 exactly as above (zeros past I) and
+ *   noise_bytes = b_0, b_1, b_2.  Pure host code, no context: it holds the rule to a model without a GPU.  A NULL pointer or
+ *   iterations or radius outside their ranges: LFG_ERR_INVALID.
+ * Not built, on purpose: a disc instead of the square draw; blue-noise or ordered dither; debanding fused into lfg_sharpen or
+ * into the NV12 store; a switch of lfg_interpolate_frames. */
+int  lfg_deband(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int iterations, int threshold, int radius, int grain,
+                uint32_t seed);
+int  lfg_deband_draw(uint32_t seed, uint32_t x, uint32_t y, int iterations, int radius, int32_t offsets[8], int32_t noise_bytes[3]);
+
 /* Motion-compensated temporal denoising, opt-in, in the caller's loop.  No reference counterpart.  Every frame-taking stage
  * thresholds per-pixel differences (the full search's exact-match shortcut, the match gate, the static mask, the cut
  * statistics), and sensor or encoder noise is what exhausts those thresholds; this averages each pixel of the current frame

@@ -230,6 +230,8 @@ SIGNATURES = {
     "lfg_nv12_to_rgba": (_i, [_vp, ctypes.POINTER(Nv12), _FP, _i, _i, _i]),
     "lfg_rgba_to_nv12": (_i, [_vp, _FP, ctypes.POINTER(Nv12), _i, _i, _i]),
     "lfg_sharpen": (_i, [_vp, _FP, _FP, _i]),
+    "lfg_deband": (_i, [_vp, _FP, _FP, _i, _i, _i, _i, _u32]),
+    "lfg_deband_draw": (_i, [_u32, _u32, _u32, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "lfg_denoise_temporal": (_i, [_vp, _FP, ctypes.POINTER(_FP), ctypes.POINTER(_FP), _i, _FP, _i, _i, _i, _i]),
     "lfg_resample": (_i, [_vp, _FP, _FP, _i]),
     "lfg_resample_taps": (_i, [_i, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int16)]),
@@ -357,6 +359,16 @@ def upscale_edge_shapes() -> np.ndarray:
     if rc != 0:
         raise LfgError(f"lfg_upscale_edge_shapes failed ({rc})")
     return t
+
+
+def deband_draw(seed: int, x: int, y: int, iterations: int, radius: int):
+    """(offsets[8] int32, noise_bytes[3] int32) of lfg_deband_draw: ox, oy of each of lfg_deband's iterations at pixel (x, y)
+    (zeros past `iterations`) and the three noise bytes.  Needs no context and no GPU.  Raises LfgError where the call refuses."""
+    offsets, noise = (ctypes.c_int32 * 8)(), (ctypes.c_int32 * 3)()
+    rc = load().lfg_deband_draw(int(seed) & 0xFFFFFFFF, int(x) & 0xFFFFFFFF, int(y) & 0xFFFFFFFF, int(iterations), int(radius), offsets, noise)
+    if rc != 0:
+        raise LfgError(f"lfg_deband_draw failed ({rc}): iterations outside 1 .. 4 or radius outside 1 .. 32")
+    return np.array(offsets, np.int32), np.array(noise, np.int32)
 
 
 def sampling_weights() -> np.ndarray:
@@ -1039,6 +1051,13 @@ class Context:
         """lfg_sharpen: `src` sharpened into `dst` (both RGBA8, one size, no overlap), strength 0 .. MAX_SHARPEN, limited to
         the range of each pixel and its four neighbours; for presented frames only, never for one a motion stage reads."""
         self._check(self.lib.lfg_sharpen(self.h, ctypes.byref(src), ctypes.byref(dst), int(strength)), "lfg_sharpen")
+
+    def deband(self, src: Frame, dst: Frame, iterations: int = 1, threshold: int = 4, radius: int = 16, grain: int = 0, seed: int = 0):
+        """lfg_deband: `src` debanded into `dst` (both RGBA8, one size, no overlap): 1 .. 4 iterations of a four-tap average at
+        a random offset within radius * i, accepted within threshold / i quarter levels, then grain and the dither back to 8
+        bits; `seed` is the presented-frame counter.  For presented frames only, never for one a motion stage reads."""
+        self._check(self.lib.lfg_deband(self.h, ctypes.byref(src), ctypes.byref(dst), int(iterations), int(threshold), int(radius),
+                                        int(grain), int(seed) & 0xFFFFFFFF), "lfg_deband")
 
     def denoise_temporal(self, curr: Frame, refs, mvs, dst: Frame, radius: int = 1, tolerance: int = 32, strength: int = 192,
                          limit: int = 255):

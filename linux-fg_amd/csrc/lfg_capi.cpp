@@ -10,6 +10,7 @@
 #include <new>
 
 #include "lfg_bicubic.hpp"
+#include "lfg_deband.hpp"
 #include "lfg_denoise.hpp"
 #include "lfg_internal.hpp"
 #include "lfg_levels.hpp"
@@ -2239,6 +2240,42 @@ LFG_EXPORT int lfg_sharpen(lfg_context *ctx, const lfg_frame *in, lfg_frame *out
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_sharpen: the output overlaps the input");
     hipError_t e = lfg::launch_sharpen(ctx->cur().stream, *in, *out, strength);
     if (e != hipSuccess) return fail_hip(ctx, e, "sharpen kernel launch");
+    return LFG_OK;
+}
+
+// ---- debanding with dithered output of presented frames (deband.hip)
+
+LFG_EXPORT int lfg_deband(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int iterations, int threshold, int radius, int grain,
+                          uint32_t seed) {
+    if (!ctx) return LFG_ERR_INVALID;
+    LFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!frame_ok(in, LFG_FORMAT_RGBA8_UNORM) || !frame_ok(out, LFG_FORMAT_RGBA8_UNORM))
+        return fail(ctx, LFG_ERR_INVALID, "lfg_deband: in and out must be non-empty RGBA8");
+    if (!same_size(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_deband: in and out differ in size");
+    if ((in->pitch | out->pitch) % 4u || ((uintptr_t)in->data | (uintptr_t)out->data) % 4u)
+        return fail(ctx, LFG_ERR_INVALID, "lfg_deband: RGBA8 frames must be 4-byte aligned with a pitch that is a multiple of 4");
+    if (iterations < 1 || iterations > lfg::kDebandMaxIterations) return fail(ctx, LFG_ERR_INVALID, "lfg_deband: iterations must be in [1, 4]");
+    if (threshold < 0 || threshold > lfg::kDebandMaxThreshold) return fail(ctx, LFG_ERR_INVALID, "lfg_deband: threshold must be in [0, 64]");
+    if (radius < 1 || radius > lfg::kDebandMaxRadius) return fail(ctx, LFG_ERR_INVALID, "lfg_deband: radius must be in [1, 32]");
+    if (grain < 0 || grain > lfg::kDebandMaxGrain) return fail(ctx, LFG_ERR_INVALID, "lfg_deband: grain must be in [0, 16]");
+    if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, "lfg_deband: the output overlaps the input");
+    hipError_t e = lfg::launch_deband(ctx->cur().stream, *in, *out, iterations, threshold, radius, grain, seed);
+    if (e != hipSuccess) return fail_hip(ctx, e, "deband kernel launch");
+    return LFG_OK;
+}
+
+// The draw of one pixel, through the functions the kernel draws with (lfg_deband.hpp).
+LFG_EXPORT int lfg_deband_draw(uint32_t seed, uint32_t x, uint32_t y, int iterations, int radius, int32_t offsets[8], int32_t noise_bytes[3]) {
+    if (!offsets || !noise_bytes || iterations < 1 || iterations > lfg::kDebandMaxIterations || radius < 1 || radius > lfg::kDebandMaxRadius)
+        return LFG_ERR_INVALID;
+    const uint32_t r0 = lfg::deband_r0(lfg::deband_row_key(lfg::deband_seed_key(seed), y), x);
+    for (int i = 0; i < lfg::kDebandMaxIterations; ++i) {
+        const lfg::DebandOffset o = i < iterations ? lfg::deband_offset(lfg::deband_r(r0, (uint32_t)(i + 1)), radius * (i + 1)) : lfg::DebandOffset{0, 0};
+        offsets[2 * i] = o.x;
+        offsets[2 * i + 1] = o.y;
+    }
+    const uint32_t noise = lfg::deband_r(r0, lfg::kDebandNoiseDraw);
+    for (int c = 0; c < 3; ++c) noise_bytes[c] = (int32_t)((noise >> (8 * c)) & 255u);
     return LFG_OK;
 }
 

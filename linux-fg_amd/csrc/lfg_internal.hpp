@@ -466,6 +466,9 @@ hipError_t launch_rgba_to_nv12(hipStream_t s, const lfg_frame &in, const lfg_nv1
 // Contrast-limited sharpening (sharpen.hip): the 16-byte kernel where base and pitch of both frames allow, with the dword
 // kernel behind it for the 1 .. 3 columns past the last multiple of 4; the dword kernel alone otherwise.
 hipError_t launch_sharpen(hipStream_t s, const lfg_frame &in, const lfg_frame &out, int strength);
+// Debanding with dithered output (deband.hip): the same two routes and the same remainder launch as launch_sharpen.
+hipError_t launch_deband(hipStream_t s, const lfg_frame &in, const lfg_frame &out, int iterations, int threshold, int radius, int grain,
+                         uint32_t seed);
 // Temporal denoising (denoise.hip): out = curr mixed with refs[i] displaced by mvs[i], i < count (1 or 2); one launch.
 hipError_t launch_denoise_temporal(hipStream_t s, const lfg_frame &curr, const lfg_frame *const *refs, const lfg_frame *const *mvs,
                                    int count, const lfg_frame &out, int radius, int tolerance, int strength, int limit);
