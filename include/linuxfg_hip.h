@@ -1189,6 +1189,40 @@ int  lfg_resample_antiring(lfg_context *ctx, const lfg_frame *in, lfg_frame *out
  * 2^31 or more. */
 int  lfg_resample_brackets(uint32_t in_size, uint32_t out_size, int32_t *lo, int32_t *hi);
 
+/* lfg_resample with its sums formed in linear or in sigmoidal light.  No reference counterpart.  The bytes of an RGBA8 frame
+ * are sRGB-encoded, and lfg_resample weights them as if they were light: one-pixel stripes 0 | 255 shrunk 2 : 1 come out 128,
+ * where half the light is the byte 188 ("the gamma error in picture scaling").  Here each colour byte is decoded to 14 bits of
+ * light, the sums are formed there and the result is encoded again.  In linear light an upscaling filter's undershoot on the
+ * dark side of an edge reaches black, so players upscale through a sigmoidal curve on top of linear light that compresses both
+ * ends of the range; a downscale averages and belongs in linear light.  Everything said of lfg_resample holds: frames, checks,
+ * tables, taps, edge folding, LFG_ERR_INVALID / LFG_ERR_UNSUPPORTED before anything is enqueued, ONE launch on the selected lane,
+ * timed under LFG_STAGE_SCALE, integer arithmetic past the tables, no branch on the content.
+ *   Tables (lfg_light_tables), in double: E(c) = c / 12.92 for c <= 0.04045, else ((c + 0.055) / 1.055)^2.4;
+ *   S(L) = 0.75 - ln(1 / (L scale + offset) - 1) / 6.5 with offset = 1 / (1 + e^(6.5 * 0.75)) and
+ *   scale = 1 / (1 + e^(6.5 (0.75 - 1))) - offset (centre 0.75 and slope 6.5, as mpv and libplacebo have them; S(0) = 0, S(1) = 1).
+ *     forward[b]       = floor(16383 f(b / 255) + 0.5),  f = E for LFG_LIGHT_LINEAR and S o E for LFG_LIGHT_SIGMOID;
+ *     threshold[k - 1] = (forward[k - 1] + forward[k] + 1) >> 1  for k = 1 .. 255;
+ *     to_byte(L)       = the number of thresholds <= L: monotone, and to_byte(forward[b]) = b.
+ *   forward increases strictly (by at least 5 and 48), and no value comes nearer a rounding tie than 3.6e-4: every libm agrees.
+ *   Pixels, horizontal first, per colour channel c (R, G, B), >> the arithmetic shift (floor):
+ *     h (y, p)_c = sum_j wx[p][j] forward[in(y, fx[p] + j)_c]   exact in 32 bits, |h| < 2^29
+ *     h'(y, p)_c = (h + 8192) >> 14                             in [-8192, 24575]
+ *     v (q, p)_c = sum_j wy[q][j] h'(fy[q] + j, p)_c            |v| <= 32768 * 24575 < 2^31 - 8192
+ *     out(q, p)_c = to_byte(clamp((v + 8192) >> 14, 0, 16383))
+ *   Alpha is not light: its byte is lfg_resample's, by lfg_resample's formula.
+ *   Where it is something else: light == LFG_LIGHT_GAMMA, or filter == LFG_FILTER_NEAREST (the tables round-trip), IS
+ *   lfg_resample: the same kernel, the same launch, the same bytes.  LFG_LIGHT_SIGMOID with an axis that shrinks (out < in) is
+ *   LFG_ERR_UNSUPPORTED and launches nothing.  Any other value of `light` is LFG_ERR_INVALID.
+ *   So a constant frame stays constant, with in == out an interpolating filter (every one but Mitchell) returns the input
+ *   bytes, and the alpha plane equals lfg_resample's byte for byte.
+ * The first call in a mode builds its tables with lfg_light_tables and uploads them (1 KiB); the context keeps both modes'
+ * until it is destroyed.  For presented frames: a picture control. */
+typedef enum { LFG_LIGHT_GAMMA = 0, LFG_LIGHT_LINEAR = 1, LFG_LIGHT_SIGMOID = 2 } lfg_light;
+int  lfg_resample_light(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int light);
+/* The tables above -- the one builder: lfg_resample_light uploads what this returns.  A pure host function: no context, no
+ * GPU.  LFG_ERR_INVALID for a NULL pointer, for LFG_LIGHT_GAMMA, which has no tables, and for any other value of `light`. */
+int  lfg_light_tables(int light, uint16_t forward[256], uint16_t threshold[255]);
+
 /* Edge-adaptive upscaling.  No reference counterpart.  Every filter of lfg_resample is separable and cannot tell along an edge
  * from across it; this call analyses, per output pixel, the direction and the strength of the luma gradient over the 2 x 2
  * texels that bracket it, weighs 12 taps with a window rotated to that gradient -- narrow across the edge, wide along it -- and

@@ -35,6 +35,7 @@ COMM_ID_BYTES = 128
 MAX_LANES = 4
 MAX_SHARPEN = 64
 FILTER_NEAREST, FILTER_BILINEAR, FILTER_CATMULL_ROM, FILTER_MITCHELL, FILTER_LANCZOS2, FILTER_LANCZOS3 = range(6)
+LIGHT_GAMMA, LIGHT_LINEAR, LIGHT_SIGMOID = range(3)
 RESAMPLE_MAX_TAPS = 64
 ERR_INVALID, ERR_UNSUPPORTED = -1, -4
 
@@ -237,6 +238,8 @@ SIGNATURES = {
     "lfg_resample_taps": (_i, [_i, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int16)]),
     "lfg_resample_antiring": (_i, [_vp, _FP, _FP, _i, _i]),
     "lfg_resample_brackets": (_i, [_u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "lfg_resample_light": (_i, [_vp, _FP, _FP, _i, _i]),
+    "lfg_light_tables": (_i, [_i, ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint16)]),
     "lfg_upscale_edge": (_i, [_vp, _FP, _FP]),
     "lfg_upscale_edge_positions": (_i, [_u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)]),
     "lfg_upscale_edge_shapes": (_i, [ctypes.POINTER(ctypes.c_int16)]),
@@ -333,6 +336,20 @@ def resample_brackets(n_in: int, n_out: int):
         err.code = rc
         raise err
     return lo, hi
+
+
+def light_tables(light: int):
+    """(forward[256] uint16, threshold[255] uint16) of lfg_light_tables: a colour byte's 14 bits of light under LIGHT_LINEAR or
+    LIGHT_SIGMOID, and the midpoints that take 14 bits back to a byte, which lfg_resample_light uploads.  Needs no context and no
+    GPU.  Raises LfgError, with the code as `.code`."""
+    forward, threshold = np.zeros(256, np.uint16), np.zeros(255, np.uint16)
+    rc = load().lfg_light_tables(int(light), forward.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
+                                 threshold.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)))
+    if rc != 0:
+        err = LfgError(f"lfg_light_tables failed ({rc}): LIGHT_GAMMA has no tables, and no other light is known")
+        err.code = rc
+        raise err
+    return forward, threshold
 
 
 def upscale_edge_positions(n_in: int, n_out: int):
@@ -1087,6 +1104,11 @@ class Context:
         at strength 0 and under FILTER_NEAREST."""
         self._check(self.lib.lfg_resample_antiring(self.h, ctypes.byref(src), ctypes.byref(dst), int(filt), int(strength)),
                     "lfg_resample_antiring")
+
+    def resample_light(self, src: Frame, dst: Frame, filt: int, light: int):
+        """lfg_resample_light: lfg_resample with the colour channels' sums formed in linear (LIGHT_LINEAR) or sigmoidal
+        (LIGHT_SIGMOID, no axis may shrink) light; lfg_resample itself under LIGHT_GAMMA and under FILTER_NEAREST."""
+        self._check(self.lib.lfg_resample_light(self.h, ctypes.byref(src), ctypes.byref(dst), int(filt), int(light)), "lfg_resample_light")
 
     def set_fused_motion_interpolate(self, on: bool):
         """lfg_interpolate_frames in the north-star order: the motion kernels write the generated frame themselves."""

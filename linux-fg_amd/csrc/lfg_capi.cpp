@@ -500,6 +500,7 @@ LFG_EXPORT void lfg_context_destroy(lfg_context *ctx) {
     ctx->tables.release_all(); ctx->uv_tables.release_all(); ctx->resample_tables.release_all();
     ctx->resample_brackets.release_all(); ctx->edge_positions.release_all();
     if (ctx->edge_shapes) (void)hipFree(ctx->edge_shapes);
+    for (uint32_t *t : ctx->light_tables) if (t) (void)hipFree(t);
     if (ctx->motion_tables) (void)hipFree(ctx->motion_tables);
     delete ctx;
 }
@@ -2407,6 +2408,21 @@ LFG_EXPORT int lfg_resample_taps(int filter, uint32_t in_size, uint32_t out_size
     return LFG_OK;
 }
 
+LFG_EXPORT int lfg_light_tables(int light, uint16_t *forward, uint16_t *threshold) {
+    if (!forward || !threshold || (light != LFG_LIGHT_LINEAR && light != LFG_LIGHT_SIGMOID)) return LFG_ERR_INVALID;
+    constexpr double kCentre = 0.75, kSlope = 6.5;              // the sigmoid of mpv and libplacebo
+    const double offset = 1.0 / (1.0 + std::exp(kSlope * kCentre));
+    const double scale = 1.0 / (1.0 + std::exp(kSlope * (kCentre - 1.0))) - offset;
+    for (int b = 0; b < 256; ++b) {
+        const double c = (double)b / 255.0;
+        double f = c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4);
+        if (light == LFG_LIGHT_SIGMOID) f = kCentre - std::log(1.0 / (f * scale + offset) - 1.0) / kSlope;
+        forward[b] = (uint16_t)std::floor(16383.0 * f + 0.5);
+    }
+    for (int k = 1; k < 256; ++k) threshold[k - 1] = (uint16_t)(((uint32_t)forward[k - 1] + (uint32_t)forward[k] + 1u) >> 1);
+    return LFG_OK;
+}
+
 LFG_EXPORT int lfg_resample_brackets(uint32_t in_size, uint32_t out_size, int32_t *lo, int32_t *hi) {
     if (!lo || !hi || in_size == 0 || out_size == 0 || in_size > 0x7fffffffu) return LFG_ERR_INVALID;
     const __int128 in = in_size, out = out_size, D = 2 * out;
@@ -2497,17 +2513,39 @@ int resample_frames(lfg_context *ctx, const lfg_frame *in, const lfg_frame *out,
     return LFG_OK;
 }
 
-// lfg_resample (strength 0) and lfg_resample_antiring: the checks, the tables and the one launch.  A pass is anti-ringed where
-// the strength is positive, the filter has weights to ring with and the pass's axis grows; where no pass is, this is
+// The tables of one mode of lfg_resample_light on the device -- forward[256] | threshold[255], 0xFFFF as uint16_t, 1 KiB --
+// built with lfg_light_tables and uploaded at the mode's first use; the context keeps both until it is destroyed.
+int light_table(lfg_context *ctx, int light, const uint32_t **out) {
+    uint32_t *&slot = ctx->light_tables[light - LFG_LIGHT_LINEAR];
+    if (!slot) {
+        uint16_t host[2 * lfg::kLightLevels];
+        if (lfg_light_tables(light, host, host + lfg::kLightLevels) != LFG_OK) return fail(ctx, LFG_ERR_INVALID, "lfg_resample_light: no tables for this light");
+        host[2 * lfg::kLightLevels - 1] = 0xFFFFu;
+        uint8_t *d = nullptr;
+        const int rc = upload_table(ctx, host, sizeof host, "light tables", &d);
+        if (rc != LFG_OK) return rc;
+        slot = reinterpret_cast<uint32_t *>(d);
+    }
+    *out = slot;
+    return LFG_OK;
+}
+
+// lfg_resample (strength 0, LFG_LIGHT_GAMMA), lfg_resample_antiring and lfg_resample_light: the checks, the tables and the one
+// launch.  A pass is anti-ringed where the strength is positive, the filter has weights to ring with and the pass's axis grows;
+// the sums are formed in another light where one is asked for and the filter has sums to form; where neither holds, this is
 // lfg_resample: the same kernel and the same launch.
-int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength, const char *who) {
+int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength, int light, const char *who) {
     if (!ctx) return LFG_ERR_INVALID;
     LFG_HIP(ctx, hipSetDevice(ctx->device));
     const int frames = resample_frames(ctx, in, out, who);
     if (frames != LFG_OK) return frames;
     if (!resample_filter_known(filter)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": unknown filter");
     if (strength < 0 || strength > 64) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": strength must be in [0, 64]");
+    if (light < LFG_LIGHT_GAMMA || light > LFG_LIGHT_SIGMOID) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": unknown light");
     if (frames_overlap(in, out)) return fail(ctx, LFG_ERR_INVALID, std::string(who) + ": the output overlaps the input");
+    if (filter == LFG_FILTER_NEAREST) light = LFG_LIGHT_GAMMA;          // one tap: the tables round-trip
+    if (light == LFG_LIGHT_SIGMOID && (out->width < in->width || out->height < in->height))
+        return fail(ctx, LFG_ERR_UNSUPPORTED, std::string(who) + ": sigmoidal light is for upscaling; an axis that shrinks is averaged in linear light");
     trim_tables(ctx, ctx->resample_tables);
     trim_tables(ctx, ctx->resample_brackets);
     lfg::ResampleTable tx, ty;
@@ -2519,10 +2557,13 @@ int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int fil
     lfg::ResampleBracket bx{}, by{};
     if (sx) rc = resample_bracket_table(ctx, in->width, out->width, &bx);
     if (sy && rc == LFG_OK) rc = resample_bracket_table(ctx, in->height, out->height, &by);
+    const uint32_t *lt = nullptr;
+    if (light != LFG_LIGHT_GAMMA && rc == LFG_OK) rc = light_table(ctx, light, &lt);
     if (rc != LFG_OK) return rc;
     StageTimer timer(ctx, LFG_STAGE_SCALE);
-    const hipError_t e = sx || sy ? lfg::launch_resample_antiring(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan, bx, by, sx, sy)
-                                  : lfg::launch_resample(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan);
+    const hipError_t e = lt       ? lfg::launch_resample_light(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan, lt)
+                         : sx || sy ? lfg::launch_resample_antiring(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan, bx, by, sx, sy)
+                                    : lfg::launch_resample(ctx->cur().stream, *in, *out, tx.axis, ty.axis, ty.plan);
     if (e != hipSuccess) return fail_hip(ctx, e, "resample kernel launch");
     return LFG_OK;
 }
@@ -2530,11 +2571,15 @@ int resample_call(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int fil
 }  // namespace
 
 LFG_EXPORT int lfg_resample(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter) {
-    return resample_call(ctx, in, out, filter, 0, "lfg_resample");
+    return resample_call(ctx, in, out, filter, 0, LFG_LIGHT_GAMMA, "lfg_resample");
 }
 
 LFG_EXPORT int lfg_resample_antiring(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int strength) {
-    return resample_call(ctx, in, out, filter, strength, "lfg_resample_antiring");
+    return resample_call(ctx, in, out, filter, strength, LFG_LIGHT_GAMMA, "lfg_resample_antiring");
+}
+
+LFG_EXPORT int lfg_resample_light(lfg_context *ctx, const lfg_frame *in, lfg_frame *out, int filter, int light) {
+    return resample_call(ctx, in, out, filter, 0, light, "lfg_resample_light");
 }
 
 // ---- edge-adaptive upscaling (upscale_edge.hip)

@@ -270,6 +270,7 @@ struct lfg_context {
     lfg::TableCache<lfg::ResampleBracketTable, lfg::HipDevice> resample_brackets;
     lfg::TableCache<lfg::EdgePositionTable, lfg::HipDevice> edge_positions;
     lfg::EdgeShape *edge_shapes = nullptr;     // lfg_upscale_edge_shapes on the device, made by the first lfg_upscale_edge
+    uint32_t *light_tables[2] = {nullptr, nullptr};   // lfg_light_tables of LFG_LIGHT_LINEAR / _SIGMOID on the device (1 KiB each), made by the mode's first lfg_resample_light
     int motion_slots = 0;                      // prefilter workgroups resident at once on this device (0 = not queried yet)
     int rim_split_env = 0;                     // LFG_MOTION_RIM_SPLIT at context creation (0: unset -- the plan follows the lane count)
     int motion_mode = 0;                       // 0: prefilter + exact fallback, 1: exact kernel only
@@ -479,6 +480,10 @@ hipError_t launch_resample(hipStream_t s, const lfg_frame &in, const lfg_frame &
 // 0 where that pass is not anti-ringed (its bracket is then not read), and not both are 0.
 hipError_t launch_resample_antiring(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const ResampleAxis &x, const ResampleAxis &y,
                                     const ResamplePlan &plan, const ResampleBracket &bx, const ResampleBracket &by, int sx, int sy);
+// ... in linear or sigmoidal light (resample_light.hip): the same launch shape with 1 KiB more LDS; `tables` is the mode's
+// forward[256] | threshold[255], 0xFFFF on the device, as uint16_t.
+hipError_t launch_resample_light(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const ResampleAxis &x, const ResampleAxis &y,
+                                 const ResamplePlan &plan, const uint32_t *tables);
 // Edge-adaptive upscaling (upscale_edge.hip): one launch; `shapes` is the table on the device, 528 rows.
 hipError_t launch_upscale_edge(hipStream_t s, const lfg_frame &in, const lfg_frame &out, const EdgeAxis &x, const EdgeAxis &y,
                                const EdgeShape *shapes);

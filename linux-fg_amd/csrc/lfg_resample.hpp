@@ -322,4 +322,131 @@ __host__ __device__ inline void resample_antiring_phase2(const ResampleAntiringA
     }
 }
 
+// ---- linear and sigmoidal light (lfg_resample_light, include/linuxfg_hip.h; resample_light.hip; tests/cpp/light_on_host.cpp)
+//
+// The same tile plan, LDS row layout and thread roles as above.  The three colour bytes of a texel go through forward[256] into
+// 14 bits of light before they are weighted and the sum goes back through threshold[255]; alpha keeps lfg_resample's formula.
+// Both tables (lfg_light_tables) follow the tile's rows in LDS as uint16_t, forward then threshold, the 256th threshold slot
+// holding 0xFFFF: kLightTableBytes behind span * 512 bytes of rows.  A workgroup stages them once (resample_light_stage), before
+// its loop over tiles.  Everything above stays as it is: resample_kernel's machine code is what section 4.16 measured.
+//
+// What the sums can be, with forward in [0, 16383], sum q = 16384 and sum |q| <= 32768 of a table row:
+//   h  = sum qx forward  in [-8192 * 16383, 24576 * 16383]: |h| < 2^29;
+//   h' = (h + 8192) >> 14  in [-8192, 24575]: the int16 of the LDS word;
+//   v  = sum qy h'  with |v| <= 32768 * 24575 < 2^31 - 8192;  L = clamp((v + 8192) >> 14, 0, 16383).
+
+constexpr uint32_t kLightLevels = 256;                         // entries of each table in LDS
+constexpr uint32_t kLightTableBytes = 2u * kLightLevels * sizeof(uint16_t);
+constexpr int kLightOne = 16383;                               // forward[255]
+
+struct ResampleLightArgs {
+    ResampleArgs r;
+    const uint32_t *tables;                    // forward[256] | threshold[255], 0xFFFF: 256 dwords on the device
+    uint32_t span;                             // the plan's: the tables start span * 64 words into LDS
+};
+
+__host__ __device__ inline uint16_t *resample_light_tables(ResampleWord *lds, uint32_t span) {
+    return reinterpret_cast<uint16_t *>(lds + (size_t)span * kResampleColumns);
+}
+
+// Staging for thread t of kResampleThreads = 256: one dword, two entries, of the 256 that both tables are.
+__host__ __device__ inline void resample_light_stage(const ResampleLightArgs &la, uint32_t t, ResampleWord *lds) {
+    reinterpret_cast<uint32_t *>(resample_light_tables(lds, la.span))[t] = la.tables[t];
+}
+
+__host__ __device__ inline void resample_light_accumulate(int (&acc)[4], int w, uint32_t texel, const uint16_t *forward) {
+    acc[0] += w * (int)forward[texel & 255u];
+    acc[1] += w * (int)forward[(texel >> 8) & 255u];
+    acc[2] += w * (int)forward[(texel >> 16) & 255u];
+    acc[3] += w * (int)(texel >> 24);
+}
+
+// to_byte: the number of thresholds <= L, found in eight steps without a branch.  Step s reads threshold[pos + s - 1] with pos a
+// multiple of 2 s that is at most 256 - 2 s: index 254 at the most.
+__host__ __device__ inline int resample_light_byte(int v, const uint16_t *threshold) {
+    int L = (v + 8192) >> 14;                                           // (arithmetic shift: floor)
+    L = L < 0 ? 0 : L > kLightOne ? kLightOne : L;
+    uint32_t pos = 0;
+#pragma unroll
+    for (uint32_t s = kLightLevels / 2u; s > 0u; s /= 2u) pos += (int)threshold[pos + s - 1u] <= L ? s : 0u;
+    return (int)pos;
+}
+
+// Phase 1 for thread (c, g), as resample_phase1: h' of its column for the source rows of the group's blocks, the colour bytes
+// looked up in forward[] per tap.
+__host__ __device__ inline void resample_light_phase1(const ResampleLightArgs &la, uint32_t tileX, uint32_t tileY, uint32_t c, uint32_t g,
+                                                      ResampleWord *lds) {
+    const ResampleArgs &a = la.r;
+    const uint32_t p = tileX * kResampleColumns + c;
+    if (p >= a.outW) return;
+    const uint16_t *forward = resample_light_tables(lds, la.span);
+    const ResampleTile t = resample_tile(a, tileY);
+    const size_t x0 = (size_t)a.x.first[p] * 4u;
+    const uint32_t n = a.x.count[p];
+    const int16_t *w = a.x.weights + (size_t)p * a.x.stride;
+    for (int32_t r0 = t.rowLo + (int32_t)(g * kResampleBlock); r0 < t.rowHi; r0 += (int32_t)(kResampleGroups * kResampleBlock)) {
+        const uint8_t *row[kResampleBlock];
+        int acc[kResampleBlock][4];
+#pragma unroll
+        for (uint32_t k = 0; k < kResampleBlock; ++k) {
+            const int32_t r = r0 + (int32_t)k < t.rowHi ? r0 + (int32_t)k : t.rowHi - 1;
+            row[k] = a.in + (size_t)r * a.inPitch + x0;
+            acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0;
+        }
+        uint32_t j = 0;
+        for (; j + 4u <= n; j += 4u) {
+            const ResampleWeights4 w4 = *reinterpret_cast<const ResampleWeights4 *>(w + j);
+            const int wj[4] = {(int)(int16_t)(w4.w[0] & 0xffffu), (int)w4.w[0] >> 16, (int)(int16_t)(w4.w[1] & 0xffffu), (int)w4.w[1] >> 16};
+#pragma unroll
+            for (uint32_t k = 0; k < kResampleBlock; ++k) {
+                const ResampleTexels4 t4 = *reinterpret_cast<const ResampleTexels4 *>(row[k] + (size_t)j * 4u);
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) resample_light_accumulate(acc[k], wj[i], t4.t[i], forward);
+            }
+        }
+        for (; j < n; ++j) {
+            const int wj = w[j];
+#pragma unroll
+            for (uint32_t k = 0; k < kResampleBlock; ++k)
+                resample_light_accumulate(acc[k], wj, *reinterpret_cast<const uint32_t *>(row[k] + (size_t)j * 4u), forward);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kResampleBlock; ++k) {
+            if (r0 + (int32_t)k >= t.rowHi) break;
+            ResampleWord h;
+            h.lo = ((uint32_t)((acc[k][0] + 8192) >> 14) & 0xffffu) | ((uint32_t)((acc[k][1] + 8192) >> 14) << 16);
+            h.hi = ((uint32_t)((acc[k][2] + 8192) >> 14) & 0xffffu) | ((uint32_t)((acc[k][3] + 128) >> 8) << 16);
+            lds[(size_t)(r0 + (int32_t)k - t.rowLo) * kResampleColumns + c] = h;
+        }
+    }
+}
+
+// Phase 2 for thread (c, g), as resample_phase2: the three colour sums go back to bytes through threshold[], alpha through
+// resample_byte.
+__host__ __device__ inline void resample_light_phase2(const ResampleLightArgs &la, uint32_t tileX, uint32_t tileY, uint32_t c, uint32_t g,
+                                                      const ResampleWord *lds) {
+    const ResampleArgs &a = la.r;
+    const uint32_t p = tileX * kResampleColumns + c;
+    if (p >= a.outW) return;
+    const uint16_t *threshold = reinterpret_cast<const uint16_t *>(lds + (size_t)la.span * kResampleColumns) + kLightLevels;
+    const ResampleTile t = resample_tile(a, tileY);
+    for (uint32_t q = t.q0 + g; q < t.q1; q += kResampleGroups) {
+        const uint32_t n = a.y.count[q];
+        const int16_t *w = a.y.weights + (size_t)q * a.y.stride;
+        const ResampleWord *col = lds + (size_t)(a.y.first[q] - t.rowLo) * kResampleColumns + c;
+        int v[4] = {0, 0, 0, 0};
+        for (uint32_t j = 0; j < n; ++j) {
+            const int wj = w[j];
+            const ResampleWord h = col[(size_t)j * kResampleColumns];
+            v[0] += wj * (int)(int16_t)(h.lo & 0xffffu);
+            v[1] += wj * ((int)h.lo >> 16);
+            v[2] += wj * (int)(int16_t)(h.hi & 0xffffu);
+            v[3] += wj * ((int)h.hi >> 16);
+        }
+        const uint32_t px = (uint32_t)resample_light_byte(v[0], threshold) | ((uint32_t)resample_light_byte(v[1], threshold) << 8) |
+                            ((uint32_t)resample_light_byte(v[2], threshold) << 16) | ((uint32_t)resample_byte(v[3]) << 24);
+        *reinterpret_cast<uint32_t *>(a.out + (size_t)q * a.outPitch + (size_t)p * 4u) = px;
+    }
+}
+
 }  // namespace lfg
